@@ -5,7 +5,7 @@ One "step" = one pass of the hot path over one synthetic clip: pixels already in
 with the 512-token prompt (S = 8*576 + 512 = 5120) -> 32-layer Vicuna-7B-shaped decoder prefill on a paged KV cache ->
 last-position logits -> greedy first token. Everything runs through libvitron_hip.so.
 
-  python bench.py --gpus 1 --steps 5 --warmup 2
+  python bench.py --gpus 1 --steps 5 --warmup 2 [--dump-outputs DIR]   (DIR: what the last timed step returned, as .npy)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
   python bench.py --gpus N ...        (plain python, N > 1: re-launches itself under torch.distributed.run on a free port; on a box
                                        with fewer than N GPUs it prints one JSON error line and exits 2)
@@ -1019,6 +1019,17 @@ def self_launch(n_gpus: int) -> int:
     return subprocess.call(cmd, env=env)
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs DIR: each array as DIR/<name>.npy, integers as float64 (exact for token ids), everything else as float32.
+    The inputs are seeded, so two builds run with the same arguments can be compared output for output."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype.kind in "iub" or a.dtype == np.float64 else np.float32)
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+
+
 def stub_main(args):
     """VT_BENCH_STUB=1: the launch / fence / max-over-ranks / one-JSON-line skeleton of main() with a stub step on the host (gloo).
     A plumbing check of the multi-process contract that runs without a GPU (tests/test_bench_launcher.py); never a measurement."""
@@ -1029,11 +1040,11 @@ def stub_main(args):
         import torch.distributed as dist
         dist.init_process_group(backend="gloo")
     S = args.frames * (args.image_size // 14) ** 2 + args.text_len
-    x = torch.randn(64, 64)
+    x = torch.randn(64, 64, generator=torch.Generator().manual_seed(args.seed + rank))
 
     def step():
         time.sleep(0.002 * (1 + rank))                 # ranks differ: the reported time must be the slowest rank's
-        return float((x @ x).sum())
+        return x @ x
 
     def fence():
         if dist is not None:
@@ -1044,9 +1055,11 @@ def stub_main(args):
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        y = step()
     fence()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"product": y})
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1166,7 +1179,12 @@ def main():
     ap.add_argument("--no-parity", action="store_true",
                     help="N=1 only: skip the `parity` object (one full-depth prefill of BASELINE configs[2] with all logit rows per mode -- the timed "
                          "mode and the at-tolerance mode -- against the reference's stored output, tests/golden/fulldepth_c3.npz)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned (rank 0) as DIR/<name>.npy: the last-position fp32 "
+                         "logits [1, V] (logits.npy) and the greedy token id (next_token.npy, float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus))
@@ -1255,8 +1273,7 @@ def main():
             torch.cuda.synchronize()
 
     for _ in range(args.warmup):
-        tok, s_len, _ = step()
-    assert s_len == S, (s_len, S)
+        step()
     # ---- the timed region: EXACTLY args.steps steps, barrier + synchronize on both sides, nothing else inside. Each step boundary
     # also gets a HIP event on the stream the kernels run on (torch's current stream): per-step device times for the median.
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
@@ -1264,10 +1281,13 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for k in range(args.steps):
-        tok, _, _ = step()
+        tok, s_len, logits = step()
         marks[k + 1].record()
     fence()
     dt = time.perf_counter() - t0
+    assert s_len == S, (s_len, S)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": logits.cpu(), "next_token": tok.cpu()})
     step_ms = sorted(marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps))
     if use_dist:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)

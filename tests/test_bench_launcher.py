@@ -49,3 +49,21 @@ def test_more_gpus_than_the_box_has_is_one_json_error_line_and_exit_2():
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["value"] is None and d["n_gpus"] == have + 3 and "GPU(s) visible" in d["error"]
+
+
+def test_dump_outputs_writes_the_last_timed_steps_result_the_same_on_every_run(tmp_path):
+    """--dump-outputs DIR: what the last timed step returned, as DIR/<name>.npy in float32 / float64, from seeded inputs (two runs give the
+    same arrays); --steps below 1 is refused."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = _run(["--gpus", "1", "--steps", "3", "--warmup", "0", "--dump-outputs", str(d)], {"VT_BENCH_STUB": "1"})
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])["steps"] == 3
+        runs.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    assert list(runs[0]) == ["product.npy"]
+    a, b = runs[0]["product.npy"], runs[1]["product.npy"]
+    assert a.dtype in (np.float32, np.float64) and a.shape == (64, 64) and np.array_equal(a, b)
+    r = _run(["--gpus", "1", "--steps", "0"], {"VT_BENCH_STUB": "1"})
+    assert r.returncode == 2 and "--steps" in r.stderr
