@@ -75,7 +75,7 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
 
 #define VT_PAGE_TOKENS 64 /* tokens per KV-cache page == keys per attention tile */
 
-#define VT_ABI_VERSION 113
+#define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
 enum { VT_OPERAND_BF16 = 0, VT_OPERAND_FP16 = 1 };
@@ -114,6 +114,29 @@ int vt_layernorm(float* x, const float* temb, int T, int tokens_per_frame, const
 
 /* y_bf16[r] = w * x[idx ? idx[r] : r] * rsqrt(mean(x^2) + eps) : transformers-4.31 LlamaRMSNorm. */
 int vt_rmsnorm(const float* x, const int* idx, const float* w, uint16_t* y, int rows, int D, float eps, void* stream);
+
+/* ---- NF4 weight-only Linears: load_pretrained_model(..., load_4bit=True) (reference vitron/model/builder.py:36-45: bitsandbytes
+ * BitsAndBytesConfig(load_in_4bit=True, bnb_4bit_quant_type="nf4", bnb_4bit_compute_dtype=float16)), restated from bitsandbytes' algorithm:
+ *   - the weight W [N][K] (K % 64 == 0) is taken as fp16 (an fp32 or operand-format source is rounded to fp16 first), in blocks of 64
+ *     consecutive elements of a row; absmax[b] = fp32 max |x| of block b; x * (1.0f / absmax) goes to the NF4 code whose bitsandbytes
+ *     midpoints (dQuantizeNF4) it lies strictly above; an all-zero block stores absmax 0 and code 7 (0.0) everywhere;
+ *   - codes uint8 [N][K/2]: element 2j in the HIGH nibble of byte j, 2j+1 in the low one; absmax fp32 [N][K/64] (bitsandbytes' layout);
+ *   - dequantised weight = op16(fp32(NF4[code]) * absmax) -- in the fp16 library bit-equal to bitsandbytes' fp16 dequantisation;
+ *   - DEVIATION: absmax stays exact fp32. The reference also sets bnb_4bit_use_double_quant=True (absmax 8-bit quantised); not done here.
+ * The GEMM reads this layout as it is (there is no separate kernel layout). */
+int vt_nf4_quant(const void* W, int src_dtype /* VT_DTYPE_OP16 | VT_DTYPE_F32 */, int ldw, int N, int K, uint8_t* codes, float* absmax,
+                 void* stream);
+/* W [N][ldw] op16 = dequant(codes, absmax) */
+int vt_nf4_dequant(const uint8_t* codes, const float* absmax, int N, int K, uint16_t* W, int ldw, void* stream);
+/* C = epi(A[M,K] . dequant(W)[N,K]^T), fp32 accumulation, the weights streamed once at 4 bits and dequantised in registers (never a 16-bit copy):
+ * 1 <= M <= 32, N % 32 == 0, K % 128 == 0; epi = VT_EPI_BF16 / VT_EPI_F32 / VT_EPI_F32_RESID (C += ...) / VT_EPI_SWIGLU_BF16 (W rows interleaved
+ * in blocks of 16, C [M][N/2]). The folded RMSNorm of the decode step, as in vt_llama_forward:
+ *   consumer (in_partials != NULL): row m is scaled by rsqrt(sum(in_partials[m][0..in_n)) * inv_dim + eps) (in_n % 16 == 0);
+ *   producer (out_partials != NULL, VT_EPI_F32_RESID only): also out_xw[m][n] = op16(x_new * out_w[n]) and out_partials[m][n / 16] = the sum
+ *   of x_new^2 over each 16 columns. NULL pointers = no fold. */
+int vt_gemm_nf4(const uint16_t* A, int lda, const uint8_t* codes, const float* absmax, void* C, int ldc, int M, int N, int K, int epi,
+                const float* in_partials, int in_n, float inv_dim, float eps, const float* out_w, uint16_t* out_xw, int ld_xw,
+                float* out_partials, void* stream);
 
 /* ---- precise level 3: the rounding remainder of a GEMM's A operand on the MX-FP4 pipe (no reference counterpart: the reference computes
  * every Linear in ONE 16-bit format, vitron/model/builder.py:47; north_star's 1e-3 against its fp32 CPU path is what these serve) ----------
@@ -407,6 +430,14 @@ typedef struct vt_llama_layer {
   const uint8_t* wo4;    const uint8_t* wo_e;
   const uint8_t* wgu4;   const uint8_t* wgu_e;
   const uint8_t* wdown4; const uint8_t* wdown_e;
+  /* NF4 weights (load_4bit; vt_nf4_quant on the packed matrices above, same row order), else NULL. A layer with these set and wqkv / wo / wgu /
+   * wdown NULL runs its Linears on vt_gemm_nf4 when a launch has <= 32 rows (with the decode step's norm folding), and otherwise dequantises
+   * each matrix into one reusable workspace buffer in front of the unchanged tile GEMMs (prefill logits bit-equal to a 16-bit model built from
+   * the dequantised weights). Precise levels 1-3 refuse NF4 layers. */
+  const uint8_t* wqkv_nf4;  const float* wqkv_absmax;
+  const uint8_t* wo_nf4;    const float* wo_absmax;
+  const uint8_t* wgu_nf4;   const float* wgu_absmax;
+  const uint8_t* wdown_nf4; const float* wdown_absmax;
 } vt_llama_layer;
 
 typedef struct vt_llama_model {

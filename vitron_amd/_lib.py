@@ -18,7 +18,7 @@ PKG_DIR = Path(__file__).resolve().parent
 LIB_PATH = PKG_DIR / "libvitron_hip.so"
 LIB_PATHS = {"bf16": LIB_PATH, "fp16": PKG_DIR / "libvitron_hip_f16.so"}
 OPERAND_BF16, OPERAND_FP16 = 0, 1
-ABI_VERSION = 113   # == VT_ABI_VERSION of include/vitron_hip.h; load() refuses a library that reports anything else
+ABI_VERSION = 114   # == VT_ABI_VERSION of include/vitron_hip.h; load() refuses a library that reports anything else
 
 # ---- enums (mirror include/vitron_hip.h) ---------------------------------------------------------------------
 EPI_BF16, EPI_BF16_GELU, EPI_BF16_QGELU, EPI_BF16_RELU, EPI_F32_RESID, EPI_F32, EPI_SWIGLU_BF16 = range(7)
@@ -57,7 +57,8 @@ class VtVitModel(C.Structure):
 
 class VtLlamaLayer(C.Structure):
     _fields_ = [(n, vp) for n in ("rms1", "wqkv", "wo", "rms2", "wgu", "wdown",
-                                  "wqkv4", "wqkv_e", "wo4", "wo_e", "wgu4", "wgu_e", "wdown4", "wdown_e")]
+                                  "wqkv4", "wqkv_e", "wo4", "wo_e", "wgu4", "wgu_e", "wdown4", "wdown_e",
+                                  "wqkv_nf4", "wqkv_absmax", "wo_nf4", "wo_absmax", "wgu_nf4", "wgu_absmax", "wdown_nf4", "wdown_absmax")]
 
 
 class VtLlamaModel(C.Structure):
@@ -124,6 +125,9 @@ SIGNATURES = {
     "vt_layernorm_mx": (_i, [vp, vp, vp, vp, vp, vp, _i, _i, _f, vp]),
     "vt_gemm_mx_resid": (_i, [vp, _i, vp, vp, vp, _i, vp, vp, vp, _i, _i, _i, _i, vp, _sz, vp]),
     "vt_flash_attn_mx": (_i, [vp, _i, vp, vp, vp, vp, _i, _i, vp, _i, vp, vp, _i, _f, vp]),
+    "vt_nf4_quant": (_i, [vp, _i, _i, _i, _i, vp, vp, vp]),
+    "vt_nf4_dequant": (_i, [vp, vp, _i, _i, vp, _i, vp]),
+    "vt_gemm_nf4": (_i, [vp, _i, vp, vp, vp, _i, _i, _i, _i, _i, vp, _i, _f, _f, vp, vp, _i, vp, vp]),
 }
 PROF_CLASSES = ("gemm_tile", "flash_attn", "gemm_skinny", "attn_decode")
 

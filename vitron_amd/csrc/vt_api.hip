@@ -264,6 +264,26 @@ int vt_attn_decode(const uint16_t* Q, int ldq, const uint16_t* k_tiles, const ui
                                head_dim, scale, max_kv_len, (float*)scratch, scratch_bytes, S(stream));
 }
 
+int vt_nf4_quant(const void* W, int src_dtype, int ldw, int N, int K, uint8_t* codes, float* absmax, void* stream) {
+  return vt_nf4_quant_launch(W, src_dtype, ldw, N, K, codes, absmax, S(stream));
+}
+int vt_nf4_dequant(const uint8_t* codes, const float* absmax, int N, int K, uint16_t* W, int ldw, void* stream) {
+  return vt_nf4_dequant_launch(codes, absmax, N, K, W, ldw, S(stream));
+}
+int vt_gemm_nf4(const uint16_t* A, int lda, const uint8_t* codes, const float* absmax, void* C, int ldc, int M, int N, int K, int epi,
+                const float* in_partials, int in_n, float inv_dim, float eps, const float* out_w, uint16_t* out_xw, int ld_xw,
+                float* out_partials, void* stream) {
+  VtGemmNormFuse nf;
+  nf.in_partials = in_partials;
+  nf.in_n = in_n;
+  nf.inv_dim = inv_dim;
+  nf.eps = eps;
+  nf.out_w = out_w;
+  nf.out_xw = out_xw;
+  nf.ld_xw = ld_xw;
+  nf.out_partials = out_partials;
+  return vt_gemm_nf4_launch(A, lda, codes, absmax, C, ldc, M, N, K, epi, nf, S(stream));
+}
 int vt_mx4_quant_weights(const uint16_t* W, int ldw, int N, int K, uint8_t* W4, uint8_t* wexp, void* stream) {
   return vt_mx4_quant_weights_launch(W, ldw, N, K, W4, wexp, S(stream));
 }
@@ -678,6 +698,8 @@ struct LlamaWs {
   // precise level 3: MX-FP4 images (codes + block exponents) of the rounding remainders of the norm output, the attention output and the
   // SwiGLU output (vt_mx4.hip); ynlo above for the lm_head's pair
   uint8_t *y4, *yexp, *att4, *attexp, *h4, *hexp;
+  // NF4 layers, launches of > 32 rows: one Linear's dequantised weights at a time (max(3H, 2I) x H op16), in front of the tile GEMMs
+  bf16_t* wdq;
   size_t total;
 };
 LlamaWs llama_carve(const vt_llama_model* m, int rows, int n_logit, int nseq, int max_kv_len, void* p, size_t n) {
@@ -705,6 +727,10 @@ LlamaWs llama_carve(const vt_llama_model* m, int rows, int n_logit, int nseq, in
   w.attlo = w.hlo = w.ynlo = nullptr;
   w.gu32 = nullptr;
   w.y4 = w.yexp = w.att4 = w.attexp = w.h4 = w.hexp = nullptr;
+  w.wdq = nullptr;
+  bool nf4 = false;
+  for (int l = 0; l < m->num_layers && m->layers; ++l) nf4 = nf4 || m->layers[l].wqkv_nf4 != nullptr;
+  if (nf4 && rows > 32) w.wdq = (bf16_t*)ws.take((size_t)std::max(3 * H, 2 * I) * H * 2);
   if (m->precise_qk == 3 && m->head_dim == 128 && rows > 1) {
     w.y4 = (uint8_t*)ws.take((size_t)rows * (H / 2));
     w.yexp = (uint8_t*)ws.take(vt_mx4_aexp_bytes(rows, H));
@@ -794,6 +820,19 @@ int vt_llama_forward(const vt_llama_model* m, const vt_kv_cache* kv, const uint1
   if (m->precise_qk >= 1 && m->precise_qk <= 2 && max_q_len > 1 && !fold_norm)
     VT_REQUIRE(precise, "vt_llama_forward: precise level %d was requested and cannot run here (head_dim %d, %d new tiles per sequence against %d slots)", m->precise_qk, HD, max_new_tiles, w.klo_tiles);
   const bool precise2 = precise && m->precise_qk >= 2 && w.gu32 != nullptr;
+  for (int l = 0; l < m->num_layers; ++l) {   // NF4 layers: all four matrices in 4 bits, nothing else
+    const vt_llama_layer& L = m->layers[l];
+    if (!L.wqkv_nf4 && !L.wo_nf4 && !L.wgu_nf4 && !L.wdown_nf4) {
+      VT_REQUIRE(L.wqkv && L.wo && L.wgu && L.wdown, "vt_llama_forward: layer %d has no weights", l);
+      continue;
+    }
+    VT_REQUIRE(L.wqkv_nf4 && L.wqkv_absmax && L.wo_nf4 && L.wo_absmax && L.wgu_nf4 && L.wgu_absmax && L.wdown_nf4 && L.wdown_absmax,
+               "vt_llama_forward: layer %d has only some of its NF4 matrices", l);
+    VT_REQUIRE(!L.wqkv && !L.wo && !L.wgu && !L.wdown, "vt_llama_forward: layer %d carries both 16-bit and NF4 weights", l);
+    VT_REQUIRE(m->precise_qk == 0, "vt_llama_forward: precise level %d cannot run on NF4 weights (layer %d)", m->precise_qk, l);
+    VT_REQUIRE((H % 128) == 0 && (I % 128) == 0, "vt_llama_forward: NF4 layers need hidden and intermediate %% 128 == 0 (H=%d I=%d)", H, I);
+    VT_REQUIRE(rows <= 32 || w.wdq != nullptr, "vt_llama_forward: NF4 dequantisation buffer missing");
+  }
   if (fuse_qkv) VT_TRY(vt_row_slot_launch((const VtAttnSeq*)seq_desc, nseq, max_q_len, tile_table, w.row_slot, s));
   for (int l = 0; l < m->num_layers; ++l) {
     const vt_llama_layer& L = m->layers[l];
@@ -801,12 +840,19 @@ int vt_llama_forward(const vt_llama_model* m, const vt_kv_cache* kv, const uint1
       VT_HIP(hipMemcpyAsync(m->hidden_trace + (size_t)l * rows * H, w.x, (size_t)rows * H * 4, hipMemcpyDeviceToDevice, s));
     bf16_t* kt = kv->k + l * layer_stride;
     bf16_t* vt = kv->vt + l * layer_stride;
+    const bool nf4 = L.wqkv_nf4 != nullptr;
+    // one decoder Linear of <= 32 rows: the 16-bit weight-streaming kernel, or its NF4 counterpart on an NF4 layer (same norm folding)
+    auto skinny = [&](const bf16_t* A, int lda, const bf16_t* W16, const uint8_t* W4, const float* absmax, void* C, int ldc, int N, int K, int epi,
+                      const VtGemmNormFuse& nf) -> int {
+      if (nf4) return vt_gemm_nf4_launch(A, lda, W4, absmax, C, ldc, rows, N, K, epi, nf, s);
+      return vt_gemm_skinny_norm_launch(A, lda, W16, K, C, ldc, rows, N, K, epi, nf, s);
+    };
     if (fold_norm) {
       if (l == 0) {
         VT_TRY(vt_rmsnorm_launch(w.x, nullptr, L.rms1, w.y, rows, H, m->rms_eps, s));
-        VT_TRY(vt_gemm_skinny_norm_launch(w.y, H, L.wqkv, H, w.qkv, 3 * H, rows, 3 * H, H, VT_EPI_BF16, none, s));
+        VT_TRY(skinny(w.y, H, L.wqkv, L.wqkv_nf4, L.wqkv_absmax, w.qkv, 3 * H, 3 * H, H, VT_EPI_BF16, none));
       } else {
-        VT_TRY(vt_gemm_skinny_norm_launch(w.y, H, L.wqkv, H, w.qkv, 3 * H, rows, 3 * H, H, VT_EPI_BF16, consume_a, s));
+        VT_TRY(skinny(w.y, H, L.wqkv, L.wqkv_nf4, L.wqkv_absmax, w.qkv, 3 * H, 3 * H, H, VT_EPI_BF16, consume_a));
       }
       VT_TRY(vt_attn_decode_fused_launch(w.qkv, 3 * H, 0, H, 2 * H, kt, vt, tile_table, (const VtAttnSeq*)seq_desc, nseq, w.att, H,
                                          heads, HD, scale, m->rope_cos, m->rope_sin, positions, s));
@@ -815,20 +861,47 @@ int vt_llama_forward(const vt_llama_model* m, const vt_kv_cache* kv, const uint1
       prod_b.out_xw = w.y;
       prod_b.ld_xw = H;
       prod_b.out_partials = w.rs_b;
-      VT_TRY(vt_gemm_skinny_norm_launch(w.att, H, L.wo, H, w.x, H, rows, H, H, VT_EPI_F32_RESID, prod_b, s));
-      VT_TRY(vt_gemm_skinny_norm_launch(w.y, H, L.wgu, H, w.h, I, rows, 2 * I, H, VT_EPI_SWIGLU_BF16, consume_b, s));
+      VT_TRY(skinny(w.att, H, L.wo, L.wo_nf4, L.wo_absmax, w.x, H, H, H, VT_EPI_F32_RESID, prod_b));
+      VT_TRY(skinny(w.y, H, L.wgu, L.wgu_nf4, L.wgu_absmax, w.h, I, 2 * I, H, VT_EPI_SWIGLU_BF16, consume_b));
       if (l + 1 < m->num_layers) {
         VtGemmNormFuse prod_a;   // x += h Wdown^T ; y = bf16(x .* next layer's rms1) ; partial sums -> rs_a
         prod_a.out_w = m->layers[l + 1].rms1;
         prod_a.out_xw = w.y;
         prod_a.ld_xw = H;
         prod_a.out_partials = w.rs_a;
-        VT_TRY(vt_gemm_skinny_norm_launch(w.h, I, L.wdown, I, w.x, H, rows, H, I, VT_EPI_F32_RESID, prod_a, s));
+        VT_TRY(skinny(w.h, I, L.wdown, L.wdown_nf4, L.wdown_absmax, w.x, H, H, I, VT_EPI_F32_RESID, prod_a));
       } else {
-        VT_TRY(vt_gemm_skinny_norm_launch(w.h, I, L.wdown, I, w.x, H, rows, H, I, VT_EPI_F32_RESID, none, s));
+        VT_TRY(skinny(w.h, I, L.wdown, L.wdown_nf4, L.wdown_absmax, w.x, H, H, I, VT_EPI_F32_RESID, none));
       }
       continue;
     }
+    if (nf4 && rows <= 32) {   // NF4, <= 32 rows without the fold (17..32 decode rows, padded-batch fix-ups, short prefills): norms as launches
+      VT_TRY(vt_rmsnorm_launch(w.x, nullptr, L.rms1, w.y, rows, H, m->rms_eps, s));
+      VT_TRY(skinny(w.y, H, nullptr, L.wqkv_nf4, L.wqkv_absmax, w.qkv, 3 * H, 3 * H, H, VT_EPI_BF16, none));
+      if (max_q_len == 1) {
+        VT_TRY(vt_attn_decode_fused_launch(w.qkv, 3 * H, 0, H, 2 * H, kt, vt, tile_table, (const VtAttnSeq*)seq_desc, nseq, w.att, H,
+                                           heads, HD, scale, m->rope_cos, m->rope_sin, positions, s));
+      } else {
+        VT_TRY(vt_kv_tiles_launch(w.qkv, 3 * H, 0, H, 2 * H, kt, vt, tile_table, (const VtAttnSeq*)seq_desc, nseq,
+                                  max_new_tiles, heads, HD, m->rope_cos, m->rope_sin, positions, s));
+        VT_TRY(vt_flash_attn_launch(w.qkv, 3 * H, kt, vt, tile_table, (const VtAttnSeq*)seq_desc, nseq, max_q_len, w.att, H,
+                                    heads, HD, 1, scale, s));
+      }
+      VT_TRY(skinny(w.att, H, nullptr, L.wo_nf4, L.wo_absmax, w.x, H, H, H, VT_EPI_F32_RESID, none));
+      VT_TRY(vt_rmsnorm_launch(w.x, nullptr, L.rms2, w.y, rows, H, m->rms_eps, s));
+      VT_TRY(skinny(w.y, H, nullptr, L.wgu_nf4, L.wgu_absmax, w.h, I, 2 * I, H, VT_EPI_SWIGLU_BF16, none));
+      VT_TRY(skinny(w.h, I, nullptr, L.wdown_nf4, L.wdown_absmax, w.x, H, H, I, VT_EPI_F32_RESID, none));
+      continue;
+    }
+    // NF4 layer, > 32 rows: each Linear dequantised into w.wdq right in front of its (unchanged) tile GEMM -- stream order keeps the one
+    // buffer safe to reuse. 16-bit layer: the weights as they are.
+    auto dq = [&](const bf16_t* W16, const uint8_t* W4, const float* absmax, int N, int K, const bf16_t** out) -> int {
+      *out = W16;
+      if (!nf4) return VT_OK;
+      *out = w.wdq;
+      return vt_nf4_dequant_launch(W4, absmax, N, K, w.wdq, K, s);
+    };
+    const bf16_t *Wqkv, *Wo, *Wgu, *Wdown;
     // Prefill (rows > 64): the same fold on the MFMA tile kernels -- the residual GEMMs (o_proj, down_proj) also store
     // y = bf16(x .* w_next) and per-row sums of x^2 per 32-column group, one small launch turns those into rstd[row], and the GEMM
     // that consumes y (gate_up, the next layer's qkv) scales its accumulator rows by rstd. Saves the 84 MB read of x per norm
@@ -887,8 +960,9 @@ int vt_llama_forward(const vt_llama_model* m, const vt_kv_cache* kv, const uint1
       VT_TRY(vt_gemm_resid_launch(w.h, I, L.wdown, I, w.x, H, nullptr, rows, H, I, 0, w.splitk, w.splitk_bytes, s));
       continue;
     }
+    VT_TRY(dq(L.wqkv, L.wqkv_nf4, L.wqkv_absmax, 3 * H, H, &Wqkv));
     if (fold_tile && l > 0) {
-      VT_TRY(vt_gemm_launch(w.y, H, L.wqkv, H, w.qkv, 3 * H, nullptr, rows, 3 * H, H, VT_EPI_BF16, AUTO, s, &cons_t));
+      VT_TRY(vt_gemm_launch(w.y, H, Wqkv, H, w.qkv, 3 * H, nullptr, rows, 3 * H, H, VT_EPI_BF16, AUTO, s, &cons_t));
     } else if (fuse_qkv) {
       VT_TRY(vt_rmsnorm_launch(w.x, nullptr, L.rms1, w.y, rows, H, m->rms_eps, s));
       VtQkvFuse qf;
@@ -899,10 +973,10 @@ int vt_llama_forward(const vt_llama_model* m, const vt_kv_cache* kv, const uint1
       qf.rope_cos = m->rope_cos;
       qf.rope_sin = m->rope_sin;
       qf.heads = heads;
-      VT_TRY(vt_gemm_qkv_fused_launch(w.y, H, L.wqkv, H, w.qkv, 3 * H, rows, H, qf, s));
+      VT_TRY(vt_gemm_qkv_fused_launch(w.y, H, Wqkv, H, w.qkv, 3 * H, rows, H, qf, s));
     } else {
       VT_TRY(vt_rmsnorm_launch(w.x, nullptr, L.rms1, w.y, rows, H, m->rms_eps, s));
-      VT_TRY(vt_gemm_launch(w.y, H, L.wqkv, H, w.qkv, 3 * H, nullptr, rows, 3 * H, H, VT_EPI_BF16, AUTO, s));
+      VT_TRY(vt_gemm_launch(w.y, H, Wqkv, H, w.qkv, 3 * H, nullptr, rows, 3 * H, H, VT_EPI_BF16, AUTO, s));
     }
     if (max_q_len == 1) {   // decode step: rotary + append + attention + combine in one launch
       VT_TRY(vt_attn_decode_fused_launch(w.qkv, 3 * H, 0, H, 2 * H, kt, vt, tile_table, (const VtAttnSeq*)seq_desc, nseq, w.att, H,
@@ -922,22 +996,28 @@ int vt_llama_forward(const vt_llama_model* m, const vt_kv_cache* kv, const uint1
       prod.out_np = H / 32;
       prod.out_ldp = rows;
       prod.out_w = L.rms2;
-      VT_TRY(vt_gemm_resid_launch(w.att, H, L.wo, H, w.x, H, nullptr, rows, H, H, 0, w.splitk, w.splitk_bytes, s, &prod));
+      VT_TRY(dq(L.wo, L.wo_nf4, L.wo_absmax, H, H, &Wo));
+      VT_TRY(vt_gemm_resid_launch(w.att, H, Wo, H, w.x, H, nullptr, rows, H, H, 0, w.splitk, w.splitk_bytes, s, &prod));
       VT_TRY(vt_rowscale_finalize_launch(w.rs_a, H / 32, rows, rows, 1.0f / (float)H, m->rms_eps, w.rstd, s));
-      VT_TRY(vt_gemm_launch(w.y, H, L.wgu, H, w.h, I, nullptr, rows, 2 * I, H, VT_EPI_SWIGLU_BF16, AUTO, s, &cons_t));
+      VT_TRY(dq(L.wgu, L.wgu_nf4, L.wgu_absmax, 2 * I, H, &Wgu));
+      VT_TRY(vt_gemm_launch(w.y, H, Wgu, H, w.h, I, nullptr, rows, 2 * I, H, VT_EPI_SWIGLU_BF16, AUTO, s, &cons_t));
+      VT_TRY(dq(L.wdown, L.wdown_nf4, L.wdown_absmax, H, I, &Wdown));
       if (l + 1 < m->num_layers) {
         prod.out_w = m->layers[l + 1].rms1;
-        VT_TRY(vt_gemm_resid_launch(w.h, I, L.wdown, I, w.x, H, nullptr, rows, H, I, 0, w.splitk, w.splitk_bytes, s, &prod));
+        VT_TRY(vt_gemm_resid_launch(w.h, I, Wdown, I, w.x, H, nullptr, rows, H, I, 0, w.splitk, w.splitk_bytes, s, &prod));
         VT_TRY(vt_rowscale_finalize_launch(w.rs_a, H / 32, rows, rows, 1.0f / (float)H, m->rms_eps, w.rstd, s));
       } else {
-        VT_TRY(vt_gemm_resid_launch(w.h, I, L.wdown, I, w.x, H, nullptr, rows, H, I, 0, w.splitk, w.splitk_bytes, s));
+        VT_TRY(vt_gemm_resid_launch(w.h, I, Wdown, I, w.x, H, nullptr, rows, H, I, 0, w.splitk, w.splitk_bytes, s));
       }
       continue;
     }
-    VT_TRY(vt_gemm_resid_launch(w.att, H, L.wo, H, w.x, H, nullptr, rows, H, H, 0, w.splitk, w.splitk_bytes, s));
+    VT_TRY(dq(L.wo, L.wo_nf4, L.wo_absmax, H, H, &Wo));
+    VT_TRY(vt_gemm_resid_launch(w.att, H, Wo, H, w.x, H, nullptr, rows, H, H, 0, w.splitk, w.splitk_bytes, s));
     VT_TRY(vt_rmsnorm_launch(w.x, nullptr, L.rms2, w.y, rows, H, m->rms_eps, s));
-    VT_TRY(vt_gemm_launch(w.y, H, L.wgu, H, w.h, I, nullptr, rows, 2 * I, H, VT_EPI_SWIGLU_BF16, AUTO, s));
-    VT_TRY(vt_gemm_resid_launch(w.h, I, L.wdown, I, w.x, H, nullptr, rows, H, I, 0, w.splitk, w.splitk_bytes, s));
+    VT_TRY(dq(L.wgu, L.wgu_nf4, L.wgu_absmax, 2 * I, H, &Wgu));
+    VT_TRY(vt_gemm_launch(w.y, H, Wgu, H, w.h, I, nullptr, rows, 2 * I, H, VT_EPI_SWIGLU_BF16, AUTO, s));
+    VT_TRY(dq(L.wdown, L.wdown_nf4, L.wdown_absmax, H, I, &Wdown));
+    VT_TRY(vt_gemm_resid_launch(w.h, I, Wdown, I, w.x, H, nullptr, rows, H, I, 0, w.splitk, w.splitk_bytes, s));
   }
   if (out_hidden) VT_HIP(hipMemcpyAsync(out_hidden, w.x, (size_t)rows * H * 4, hipMemcpyDeviceToDevice, s));
   if (n_logit_rows > 0 && (precise2 || precise3)) {   // level 2: the lm_head's operand as a pair too (any number of rows: a last-position-only call included)

@@ -52,6 +52,14 @@ inline VtGemmNormFuse vt_nf_rows(const VtGemmNormFuse& nf, long m0) {
 int vt_gemm_skinny_norm_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, int ldc, int M, int N, int K,
                                int epi, const VtGemmNormFuse& nf, hipStream_t s);
 
+// ---- vt_nf4.hip: NF4 weight-only Linears (load_4bit; format in include/vitron_hip.h) -------------------------------------
+// codes uint8 [N][K/2] (element 2j in the high nibble), absmax fp32 [N][K/64]; src_dtype VT_DTYPE_OP16 or VT_DTYPE_F32
+int vt_nf4_quant_launch(const void* W, int src_dtype, int ldw, int N, int K, uint8_t* codes, float* absmax, hipStream_t s);
+int vt_nf4_dequant_launch(const uint8_t* codes, const float* absmax, int N, int K, bf16_t* W, int ldw, hipStream_t s);
+// M <= 32, N % 32 == 0, K % 128 == 0; epi = VT_EPI_BF16 / F32 / F32_RESID / SWIGLU_BF16; the folded RMSNorm of the skinny kernel (nf)
+int vt_gemm_nf4_launch(const bf16_t* A, int lda, const uint8_t* codes, const float* absmax, void* C, int ldc, int M, int N, int K, int epi,
+                       const VtGemmNormFuse& nf, hipStream_t s);
+
 // ---- fused QKV epilogue (vt_gemm8.hip) ---------------------------------------------------------------------
 // The QKV projection of a prefill writes its result where the attention kernels read it: q rotated in place in the fused-QKV
 // buffer, k rotated into the K pages, v transposed into the V^T pages -- what vt_kv_tiles does as a separate pass over 252 MB

@@ -413,7 +413,13 @@ def interleave_gate_up(gate: torch.Tensor, up: torch.Tensor) -> torch.Tensor:
 class PackedLlama:
     """LLaMA decoder weights in kernel layout (vt_llama_model) + embedding table."""
 
-    def __init__(self, sd: SD, cfg: dict, device, rope_len: Optional[int] = None, dtype=None):
+    def __init__(self, sd: SD, cfg: dict, device, rope_len: Optional[int] = None, dtype=None, weight_format: str = "16bit"):
+        """weight_format "nf4" (load_4bit): the seven Linears of every decoder layer are kept as NF4 codes + fp32 absmax only
+        (ops.nf4_quant on the packed q|k|v and interleaved gate/up matrices, taken from the checkpoint's values as fp16, bitsandbytes'
+        load_in_4bit); embed_tokens, lm_head and the norms stay as they are."""
+        if weight_format not in ("16bit", "nf4"):
+            raise _lib.VitronHipError(f"PackedLlama: weight_format must be '16bit' or 'nf4', got {weight_format!r}")
+        self.weight_format = weight_format
         self.cfg = dict(cfg)
         self.device = torch.device(device)
         self.dtype = dt = _dtype(dtype)
@@ -436,6 +442,8 @@ class PackedLlama:
             raise _lib.VitronHipError("PackedLlama: head_dim must be 64 or 128")
         if self.I % 16:
             raise _lib.VitronHipError("PackedLlama: intermediate_size must be a multiple of 16")
+        if weight_format == "nf4" and (H % 128 or self.I % 128):
+            raise _lib.VitronHipError(f"PackedLlama: NF4 weights need hidden and intermediate sizes % 128 == 0 (got {H}, {self.I})")
         dev = self.device
         self._keep: List[torch.Tensor] = []
 
@@ -462,15 +470,29 @@ class PackedLlama:
             for name, shp in want.items():
                 if tuple(sd[p + name + ".weight"].shape) != shp:
                     raise _lib.VitronHipError(f"PackedLlama: {p}{name}.weight is {tuple(sd[p + name + '.weight'].shape)}, config says {shp}")
-            t = {"rms1": keep(_f32(sd[p + "input_layernorm.weight"], dev)), "rms2": keep(_f32(sd[p + "post_attention_layernorm.weight"], dev)),
-                 "wqkv": keep(torch.cat([_bf(sd[p + "self_attn.q_proj.weight"], dev), _bf(sd[p + "self_attn.k_proj.weight"], dev),
-                                         _bf(sd[p + "self_attn.v_proj.weight"], dev)], 0)),
-                 "wo": keep(_bf(sd[p + "self_attn.o_proj.weight"], dev)),
-                 "wgu": keep(interleave_gate_up(_bf(sd[p + "mlp.gate_proj.weight"], dev), _bf(sd[p + "mlp.up_proj.weight"], dev)).contiguous()),
-                 "wdown": keep(_bf(sd[p + "mlp.down_proj.weight"], dev))}
+            t = {"rms1": keep(_f32(sd[p + "input_layernorm.weight"], dev)), "rms2": keep(_f32(sd[p + "post_attention_layernorm.weight"], dev))}
+            if weight_format == "nf4":
+                # quantised from the checkpoint's own values (fp32 on the way: the kernel rounds them to fp16 as bitsandbytes does), one
+                # matrix at a time -- no 16-bit decoder matrix is kept
+                from . import ops
+                src = {"wqkv": lambda: torch.cat([_f32(sd[p + "self_attn." + n + "_proj.weight"], dev) for n in "qkv"], 0),
+                       "wo": lambda: _f32(sd[p + "self_attn.o_proj.weight"], dev),
+                       "wgu": lambda: interleave_gate_up(_f32(sd[p + "mlp.gate_proj.weight"], dev), _f32(sd[p + "mlp.up_proj.weight"], dev)).contiguous(),
+                       "wdown": lambda: _f32(sd[p + "mlp.down_proj.weight"], dev)}
+                for name, make in src.items():
+                    codes, absmax = ops.nf4_quant(make(), dtype=dt)
+                    t[name + "_nf4"], t[name + "_absmax"] = keep(codes), keep(absmax)
+                    setattr(Ly, name + "_nf4", codes.data_ptr())
+                    setattr(Ly, name + "_absmax", absmax.data_ptr())
+            else:
+                t.update({"wqkv": keep(torch.cat([_bf(sd[p + "self_attn.q_proj.weight"], dev), _bf(sd[p + "self_attn.k_proj.weight"], dev),
+                                                  _bf(sd[p + "self_attn.v_proj.weight"], dev)], 0)),
+                          "wo": keep(_bf(sd[p + "self_attn.o_proj.weight"], dev)),
+                          "wgu": keep(interleave_gate_up(_bf(sd[p + "mlp.gate_proj.weight"], dev), _bf(sd[p + "mlp.up_proj.weight"], dev)).contiguous()),
+                          "wdown": keep(_bf(sd[p + "mlp.down_proj.weight"], dev))})
+                Ly.wqkv, Ly.wo, Ly.wgu, Ly.wdown = t["wqkv"].data_ptr(), t["wo"].data_ptr(), t["wgu"].data_ptr(), t["wdown"].data_ptr()
             self.layer_tensors.append(t)      # the packed tensors by name (engine.padded_batch_fixup runs single rows through the primitive ops)
             Ly.rms1, Ly.rms2 = t["rms1"].data_ptr(), t["rms2"].data_ptr()
-            Ly.wqkv, Ly.wo, Ly.wgu, Ly.wdown = t["wqkv"].data_ptr(), t["wo"].data_ptr(), t["wgu"].data_ptr(), t["wdown"].data_ptr()
         m = _lib.VtLlamaModel()
         m.hidden, m.heads, m.head_dim, m.intermediate, m.num_layers, m.vocab = H, heads, self.hd, self.I, self.L, self.V_pad
         m.rms_eps = float(cfg.get("rms_norm_eps", 1e-5))
@@ -480,8 +502,31 @@ class PackedLlama:
         m.prefill_norm_fold = int(bool(cfg.get("prefill_norm_fold", False)))
         m.qkv_fuse = int(bool(cfg.get("qkv_fuse", False)))
         m.precise_qk = max(int(cfg.get("precise", 0) or 0), int(bool(cfg.get("precise_qk", False))))
+        if m.precise_qk and weight_format == "nf4":
+            raise _lib.VitronHipError("precise modes cannot run on NF4 (load_4bit) weights")
         self.model = m
         self.ws = Workspace(dev)
+
+    def decoder_weight_bytes(self) -> int:
+        """Bytes held for the decoder layers' Linear weights (16-bit matrices, or NF4 codes + absmax)."""
+        return sum(v.numel() * v.element_size() for t in self.layer_tensors for k, v in t.items() if k.startswith("w"))
+
+    def linear(self, a: torch.Tensor, l: int, name: str, epi: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One decoder Linear of layer l ("wqkv" / "wo" / "wgu" / "wdown", packed layout) on the primitive operators: ops.gemm on 16-bit
+        weights, ops.gemm_nf4 (32 rows per launch) on NF4 weights."""
+        from . import ops
+        t = self.layer_tensors[l]
+        if self.weight_format != "nf4":
+            return ops.gemm(a, t[name], None, epi, out=out)
+        codes, absmax = t[name + "_nf4"], t[name + "_absmax"]
+        if out is None:
+            K = a.shape[1]
+            N = codes.numel() * 2 // K
+            out = torch.empty((a.shape[0], N // 2 if epi == ops.EPI_SWIGLU_BF16 else N), device=a.device,
+                              dtype=torch.float32 if epi in (ops.EPI_F32, ops.EPI_F32_RESID) else a.dtype)
+        for r in range(0, a.shape[0], 32):
+            ops.gemm_nf4(a[r:r + 32], codes, absmax, epi, out=out[r:r + 32])
+        return out
 
     def set_qkv_fuse(self, on: bool) -> None:
         """Prefill: rotary + K / V^T page writes inside the QKV GEMM's epilogue instead of the separate vt_kv_tiles pass
@@ -496,6 +541,8 @@ class PackedLlama:
         level = int(level)
         if level not in (0, 1, 2, 3):
             raise _lib.VitronHipError(f"precise level must be 0, 1, 2 or 3, got {level}")
+        if level and self.weight_format == "nf4":
+            raise _lib.VitronHipError(f"precise level {level} cannot run on NF4 (load_4bit) weights: its products need the 16-bit matrices")
         if level and self.hd != 128:
             raise _lib.VitronHipError(f"precise modes need head_dim 128 (got {self.hd})")
         if level == 3:
@@ -525,6 +572,8 @@ class PackedLlama:
         the prefill time. head_dim 128 only; decode steps are unchanged. Default off."""
         if on and self.hd != 128:
             raise _lib.VitronHipError(f"precise_qk needs head_dim 128 (got {self.hd})")
+        if on and self.weight_format == "nf4":
+            raise _lib.VitronHipError("precise_qk cannot run on NF4 (load_4bit) weights")
         self.model.precise_qk = int(bool(on))
 
     def set_prefill_norm_fold(self, on: bool) -> None:
@@ -695,12 +744,12 @@ def padded_batch_fixup(llama: PackedLlama, kv: PagedKVCache, seqs: Sequence[Sequ
         for l, t in enumerate(llama.layer_tensors):
             k_l, vt_l = kv.k[l * lstride:(l + 1) * lstride], kv.vt[l * lstride:(l + 1) * lstride]
             y = ops.rmsnorm(x, t["rms1"], eps, dtype=dt)
-            qkv = ops.gemm(y, t["wqkv"], None, ops.EPI_BF16)             # position 0: the rotary embedding is the identity
+            qkv = llama.linear(y, l, "wqkv", ops.EPI_BF16)                # position 0: the rotary embedding is the identity
             att = ops.attn_decode(qkv[:, :H], k_l, vt_l, table_t, desc_q_t, heads, hd, 1.0 / math.sqrt(hd), max_kv)
             ops.kv_tiles(qkv.index_select(0, rep_t).contiguous(), 0, H, 2 * H, k_l, vt_l, table_t, desc_w_t, max_new_tiles, heads, hd)
-            x = ops.gemm(att, t["wo"], None, ops.EPI_F32_RESID, out=x)
-            h = ops.gemm(ops.rmsnorm(x, t["rms2"], eps, dtype=dt), t["wgu"], None, ops.EPI_SWIGLU_BF16)
-            x = ops.gemm(h, t["wdown"], None, ops.EPI_F32_RESID, out=x)
+            x = llama.linear(att, l, "wo", ops.EPI_F32_RESID, out=x)
+            h = llama.linear(ops.rmsnorm(x, t["rms2"], eps, dtype=dt), l, "wgu", ops.EPI_SWIGLU_BF16)
+            x = llama.linear(h, l, "wdown", ops.EPI_F32_RESID, out=x)
         lg = ops.gemm(ops.rmsnorm(x, llama.final_norm, eps, dtype=dt), llama.lm_head, None, ops.EPI_F32)[:, :llama.V]
         for i, b in enumerate(pads):
             pad_logits[b] = lg[i]

@@ -91,8 +91,12 @@ def _processors(model):
 
 def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, load_4bit=False, device_map="auto",
                           device="cuda", **kwargs):
-    if load_8bit or load_4bit:
-        raise NotImplementedError("bitsandbytes 8/4-bit loading has no MI355X kernel path in vitron_amd")
+    if load_8bit:
+        raise NotImplementedError("bitsandbytes 8-bit loading (LLM.int8 outlier decomposition) has no MI355X kernel path in vitron_amd")
+    # load_4bit (reference builder.py:36-45, bitsandbytes NF4 with fp16 compute): the decoder layers' Linears are packed as NF4 codes + fp32
+    # absmax and run on the 4-bit kernels (vitron_amd/csrc/vt_nf4.hip); embeddings, lm_head, norms, towers, projector and region extractor
+    # stay 16-bit. No double quantisation of the absmax values.
+    weight_format = "nf4" if load_4bit else "16bit"
     if torch.device(device).type != "cuda":
         raise RuntimeError("vitron_amd runs on the GPU only (device must be 'cuda'); there is no CPU path")
     synthetic = kwargs.pop("synthetic", None)
@@ -102,6 +106,7 @@ def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, l
         spec = synthetic or {}
         cfg = LlavaConfig(**spec.get("llm", {}), mm_hidden_size=spec.get("image", spec.get("video", {})).get("hidden_size", 1024))
         model = LlavaLlamaForCausalLM(cfg)
+        model.weight_format = weight_format
         model.init_synthetic(device, seed=spec.get("seed", 1234), vit_image=spec.get("image"), vit_video=spec.get("video"),
                              w_std=spec.get("w_std", 0.02), resize_for=lambda: _add_special_tokens(tokenizer, cfg),
                              dtype=torch_dtype if torch_dtype is not None else spec.get("dtype"))
@@ -116,6 +121,7 @@ def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, l
         from transformers import AutoTokenizer
         tokenizer = AutoTokenizer.from_pretrained(model_base or model_path, use_fast=False)
     model = LlavaLlamaForCausalLM(cfg)
+    model.weight_format = weight_format
     if "lora" in model_name.lower() and model_base is not None:
         sd = _load_weight_files(model_base)
         nl = os.path.join(model_path, "non_lora_trainables.bin")

@@ -118,6 +118,8 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         # inference dtype, builder.py:47); set by config.torch_dtype / .to(dtype=...) / .half() before the weights are packed
         # (a config.json value is advisory: unsupported entries fall back to the default; explicit .to(dtype=) / torch_dtype= arguments are validated)
         self._dtype = _resolve_dtype(getattr(config, "torch_dtype", None), strict=False)
+        # "16bit", or "nf4" (load_pretrained_model(..., load_4bit=True)): the decoder layers' Linears packed as NF4 (engine.PackedLlama)
+        self.weight_format = "16bit"
         self.kv: Optional[PagedKVCache] = None
         self.kv_pages = getattr(config, "kv_pages", None)
         # multi-turn reuse (vitron_amd/prefix_cache.py): generate() keeps the last conversation's KV pages and the encoded
@@ -213,7 +215,7 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         dev = torch.device(device)
         if dev.type == "cuda":
             if self._llama_sd is not None:
-                self.model.llama = PackedLlama(self._llama_sd, self.config.to_dict(), dev, dtype=self._dtype)
+                self.model.llama = PackedLlama(self._llama_sd, self.config.to_dict(), dev, dtype=self._dtype, weight_format=self.weight_format)
                 self._llama_sd = None
             for m in (self.model.mm_projector, self.model.region_extractor, self.model.image_tower, self.model.video_tower):
                 if m is not None:

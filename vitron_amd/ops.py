@@ -439,3 +439,81 @@ def layernorm_mx(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: 
     aexp = torch.zeros((mx4_aexp_bytes(rows, D),), device=x.device, dtype=torch.uint8)
     _lib.check(lib.vt_layernorm_mx(_p(x), _p(gamma), _p(beta), _p(y), _p(a4), _p(aexp), rows, D, eps, _stream()), "vt_layernorm_mx", lib)
     return y, a4, aexp
+
+
+# ---- NF4 weight-only Linears (load_4bit; format: include/vitron_hip.h, vt_nf4_quant) -------------------------------------------
+def nf4_quant(w: torch.Tensor, dtype=None):
+    """(codes uint8 [N*K/2], absmax fp32 [N*K/64]) of a weight [N][K] in bitsandbytes' NF4 order: the weight is taken as fp16, blocks of
+    64 consecutive elements, element 2j in the high nibble. `w` is fp32 or 16-bit; `dtype` (fp32 sources only) picks the library build
+    (the codes do not depend on it)."""
+    if not isinstance(w, torch.Tensor) or not w.is_cuda:
+        raise _lib.VitronHipError("nf4_quant.w: expected a CUDA/HIP tensor (vitron_amd has no CPU path)")
+    if w.dtype == torch.float32:
+        lib, src = _lib.load(operand=_lib.operand_of(dtype or _lib.torch_dtype())), _lib.DTYPE_F32
+    else:
+        lib, _ = _op16(w, "nf4_quant.w")
+        src = _lib.DTYPE_BF16   # VT_DTYPE_OP16: the library's own operand format
+    _chk(w, w.dtype, "nf4_quant.w")
+    N, K = w.shape
+    if K % 64:
+        raise _lib.VitronHipError(f"nf4_quant: K = {K} must be a multiple of 64")
+    codes = torch.empty((N * K // 2,), device=w.device, dtype=torch.uint8)
+    absmax = torch.empty((N * K // 64,), device=w.device, dtype=torch.float32)
+    _lib.check(lib.vt_nf4_quant(_p(w), src, K, N, K, _p(codes), _p(absmax), _stream()), "vt_nf4_quant", lib)
+    return codes, absmax
+
+
+def _nf4_shape(codes: torch.Tensor, absmax: torch.Tensor, K: int, name: str) -> int:
+    _chk(codes, torch.uint8, name + ".codes")
+    _chk(absmax, torch.float32, name + ".absmax")
+    if K <= 0 or K % 64 or (2 * codes.numel()) % K or codes.numel() * 2 // K * (K // 64) != absmax.numel():
+        raise _lib.VitronHipError(f"{name}: {codes.numel()} code bytes / {absmax.numel()} scales do not describe a [N][{K}] NF4 matrix")
+    return codes.numel() * 2 // K
+
+
+def nf4_dequant(codes: torch.Tensor, absmax: torch.Tensor, K: int, dtype) -> torch.Tensor:
+    """W [N][K] in `dtype` (the library's operand format) = op16(NF4[code] * absmax)."""
+    lib = _lib.load(operand=_lib.operand_of(dtype))
+    N = _nf4_shape(codes, absmax, K, "nf4_dequant")
+    out = torch.empty((N, K), device=codes.device, dtype=_lib.torch_dtype(dtype))
+    _lib.check(lib.vt_nf4_dequant(_p(codes), _p(absmax), N, K, _p(out), K, _stream()), "vt_nf4_dequant", lib)
+    return out
+
+
+def gemm_nf4(a: torch.Tensor, codes: torch.Tensor, absmax: torch.Tensor, epi: int = EPI_BF16, out: Optional[torch.Tensor] = None,
+             norm_in: Optional[tuple] = None, norm_out: Optional[tuple] = None) -> torch.Tensor:
+    """out = epi(a[M,K] @ dequant(W)[N,K]^T) on the 4-bit weight-streaming kernel, M <= 32 (EPI_BF16 / EPI_F32 / EPI_F32_RESID into `out` /
+    EPI_SWIGLU_BF16). The decode step's folded RMSNorm (include/vitron_hip.h vt_gemm_nf4):
+      norm_in  = (partials fp32 [M][in_n], inv_dim, eps): row m scaled by rsqrt(sum(partials[m]) * inv_dim + eps);
+      norm_out = (w fp32 [N], xw op16 [M][N], partials fp32 [M][N/16]) with EPI_F32_RESID: xw = op16(x_new * w), partials = sums of x_new^2."""
+    lib, dt = _op16(a, "gemm_nf4.a")
+    _chk(a, dt, "gemm_nf4.a")
+    M, K = a.shape
+    N = _nf4_shape(codes, absmax, K, "gemm_nf4")
+    n_out = N // 2 if epi == EPI_SWIGLU_BF16 else N
+    odt = torch.float32 if epi in (EPI_F32, EPI_F32_RESID) else dt
+    if out is None:
+        if epi == EPI_F32_RESID:
+            raise _lib.VitronHipError("gemm_nf4: EPI_F32_RESID needs `out` (the fp32 residual stream)")
+        out = torch.empty((M, n_out), device=a.device, dtype=odt)
+    _chk(out, odt, "gemm_nf4.out")
+    if tuple(out.shape) != (M, n_out):
+        raise _lib.VitronHipError(f"gemm_nf4: out is {tuple(out.shape)}, expected {(M, n_out)}")
+    pin, in_n, inv_dim, eps = None, 0, 0.0, 0.0
+    if norm_in is not None:
+        pin, inv_dim, eps = norm_in
+        _chk(pin, torch.float32, "gemm_nf4.norm_in")
+        if pin.dim() != 2 or pin.shape[0] < M:
+            raise _lib.VitronHipError("gemm_nf4: norm_in partials must be [M][in_n]")
+        in_n = pin.shape[1]
+    ow = oxw = opart = None
+    if norm_out is not None:
+        ow, oxw, opart = norm_out
+        _chk(ow, torch.float32, "gemm_nf4.norm_out.w")
+        _chk(oxw, dt, "gemm_nf4.norm_out.xw")
+        _chk(opart, torch.float32, "gemm_nf4.norm_out.partials")
+        if ow.numel() != N or tuple(oxw.shape) != (M, N) or opart.numel() < M * (N // 16):
+            raise _lib.VitronHipError("gemm_nf4: norm_out shapes must be w [N], xw [M][N], partials [M][N/16]")
+    _lib.check(lib.vt_gemm_nf4(_p(a), K, _p(codes), _p(absmax), _p(out), n_out, M, N, K, epi, _p(pin), in_n, float(inv_dim), float(eps),
+                               _p(ow), _p(oxw), N, _p(opart), _stream()), "vt_gemm_nf4", lib)
+    return out
