@@ -1,6 +1,9 @@
 """load_4bit on the GPU: the NF4 kernels (vitron_amd/csrc/vt_nf4.hip) against the numpy restatement (tests/nf4_ref.py) and fp64, the 4-bit
 decoder against a 16-bit decoder built from its dequantised weights, and the public surface (load_pretrained_model(..., load_4bit=True),
 generate, ServingEngine, padded batches)."""
+import functools
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -140,6 +143,170 @@ def test_gemm_nf4_folded_norm_both_roles(dev, dt, M):
     assert rel_l2(g.float(), ref) <= TOL
 
 
+# ---- the GEMM against the CPU dequantisation of random NF4 matrices (nf4_ref.random_nf4: no GPU quantiser in the reference) ------------
+FMT = {torch.bfloat16: "bf16", torch.float16: "fp16"}
+PROBE_EPIS = ("EPI_F32", "EPI_BF16", "EPI_F32_RESID")
+BOUND_M = (1, 2, 3, 8, 15, 16, 17, 24, 31, 32)
+BOUND_K = (128, 256, 384, 1024 + 128, 4096, 11008)     # 128: one K step, seven of the eight waves idle; 384, 1152: uneven splits
+SWIGLU_RANGE = (-12, 0)   # gate / up scales small enough that silu(g) * u stays inside fp16 at K = 11008
+
+
+@functools.lru_cache(maxsize=6)
+def _rnd(N, K, seed, log2_range=(-12, 4)):
+    """(codes, absmax, fp32 CPU dequantisation [N][K]) of nf4_ref.random_nf4"""
+    codes, absmax = R.random_nf4(N, K, seed, log2_range)
+    return codes, absmax, R.dequantize_f32(codes, absmax, N, K)
+
+
+def _rnd_dev(N, K, seed, dt, dev, log2_range=(-12, 4)):
+    """(codes, absmax on the GPU, the weight's exact operand values op16(CPU dequantisation) as fp64 numpy [N][K])"""
+    codes, absmax, deq = _rnd(N, K, seed, log2_range)
+    wd = torch.from_numpy(deq).to(dt).double().numpy()
+    return torch.from_numpy(codes).to(dev), torch.from_numpy(absmax).to(dev), wd
+
+
+def _within(got, ref, bound, what):
+    """|got - ref| <= bound element by element (NaN fails); the largest error / bound ratio goes to VT_TOL_REPORT when that is set"""
+    g = got.detach().double().cpu().numpy()
+    err = np.abs(g - ref)
+    bad = ~(err <= bound)
+    if bad.any():
+        i = tuple(np.argwhere(bad)[0])
+        raise AssertionError(f"{what}: {int(bad.sum())} of {bad.size} elements outside the bound, first at {i}: got {g[i]!r} ref {ref[i]!r} "
+                             f"bound {bound[i]!r}")
+    out = os.environ.get("VT_TOL_REPORT")
+    if out:
+        with open(out, "a") as fh:
+            fh.write(f"bound {what}\t{float((err / np.maximum(bound, 1e-300)).max()):.6e}\n")
+
+
+def _probe_ks(K):
+    """k = 0, 1, 63, 64, 127, 128 (nibble order, 64-blocks, the first K steps), each wave's first and last k, and K - 1"""
+    steps = K // 128
+    ks = {0, 1, 63, 64, 127, 128, K - 1}
+    for w in range(8):                          # gemm_nf4_kernel: wave w walks steps [steps * w / 8, steps * (w + 1) / 8)
+        s0, s1 = steps * w // 8, steps * (w + 1) // 8
+        if s0 < s1:
+            ks |= {128 * s0, 128 * s1 - 1}
+    return sorted(k for k in ks if k < K)
+
+
+def _probe(a_rows, codes, absmax, epi, N):
+    """C = epi(a W^T) for unit rows a, as fp32 [M][N] (EPI_F32_RESID onto a zero residual)"""
+    from vitron_amd import ops
+    if epi == ops.EPI_F32_RESID:
+        out = torch.zeros((a_rows.shape[0], N), device=a_rows.device)
+        return ops.gemm_nf4(a_rows, codes, absmax, epi, out=out)
+    return ops.gemm_nf4(a_rows, codes, absmax, epi).float()
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("K", [4096, 11008])
+def test_gemm_nf4_unit_probes_reconstruct_every_weight_exactly(dev, dt, K):
+    """row m of A = e_k: C[m][n] = deq(W)[n][k] is one exact product, so every epilogue must return the CPU dequantisation itself. 32 probe
+    rows per launch, ceil(K / 32) launches: every weight element passes through the kernel's load, LDS table, nibble split and scale."""
+    from vitron_amd import ops
+    N = 64
+    codes, absmax, wd = _rnd_dev(N, K, 400 + K % 97, dt, dev)
+    want = torch.from_numpy(wd.T.copy()).float()
+    eye = torch.eye(K, dtype=dt, device=dev)
+    for epi_name in PROBE_EPIS:
+        epi = getattr(ops, epi_name)
+        got = torch.empty((K, N), device=dev)
+        for k0 in range(0, K, 32):
+            k1 = min(K, k0 + 32)
+            got[k0:k1] = _probe(eye[k0:k1], codes, absmax, epi, N)
+        bad = got.cpu() != want                 # as values: +0 == -0
+        assert not bad.any(), (epi_name, int(bad.sum()), tuple(bad.nonzero()[0].tolist()))
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("N", [32, 96])
+@pytest.mark.parametrize("K", BOUND_K)
+def test_gemm_nf4_unit_probes_at_edge_shapes(dev, dt, N, K):
+    """the exact probes at the k that split K among the waves and steps, in every row-count instantiation and tail (M = 1 .. 32)"""
+    from vitron_amd import ops
+    codes, absmax, wd = _rnd_dev(N, K, 500 + K % 89 + N, dt, dev)
+    want = torch.from_numpy(wd).float()
+    ks = _probe_ks(K)
+    eye = torch.eye(K, dtype=dt, device=dev)
+    for M in (1, 15, 16, 17, 31, 32):
+        for i0 in range(0, len(ks), M):
+            sel = [ks[(i0 + j) % len(ks)] for j in range(M)]
+            a = eye[sel].contiguous()
+            for epi_name in PROBE_EPIS:
+                got = _probe(a, codes, absmax, getattr(ops, epi_name), N).cpu()
+                bad = got != want[:, sel].t()
+                assert not bad.any(), (epi_name, M, sel, int(bad.sum()), tuple(bad.nonzero()[0].tolist()))
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("epi_name", ["EPI_F32", "EPI_BF16", "EPI_F32_RESID", "EPI_SWIGLU_BF16"])
+@pytest.mark.parametrize("K", BOUND_K)
+def test_gemm_nf4_within_per_element_bound_of_fp64(dev, dt, epi_name, K):
+    """random NF4 weights against fp64 on their CPU dequantisation, element by element under nf4_ref.gemm_bound, at every row count
+    1 .. 32 (both instantiations, their tails), K from one step to 86 (uneven splits), N from one block to 4096 + 32 and 2 I for SwiGLU"""
+    from vitron_amd import ops
+    epi = getattr(ops, epi_name)
+    swiglu, resid = epi == ops.EPI_SWIGLU_BF16, epi == ops.EPI_F32_RESID
+    store = FMT[dt] if epi in (ops.EPI_BF16, ops.EPI_SWIGLU_BF16) else None
+    Ns = (32, 96, 4096 + 32) + ((2 * 11008,) if swiglu and K <= 4096 else ())
+    a = _w((32, K), 600 + K % 83, 1.0).to(dt)
+    a64 = a.double().numpy()
+    a_dev = a.to(dev)
+    for N in Ns:
+        codes, absmax, wd = _rnd_dev(N, K, 700 + K % 79 + N % 71, dt, dev, SWIGLU_RANGE if swiglu else (-12, 4))
+        r = _w((32, N), 800 + N % 67, 4.0) if resid else None
+        r64 = r.double().numpy() if resid else None
+        y = a64 @ wd.T
+        ref = R.gemm_ref(a64, wd, resid=r64, swiglu=swiglu, y=y)
+        bnd = R.gemm_bound(a64, wd, K, resid=r64, swiglu=swiglu, store=store, y=y)
+        for M in BOUND_M:
+            out = r[:M].to(dev).clone() if resid else None
+            got = ops.gemm_nf4(a_dev[:M], codes, absmax, epi, out=out)
+            _within(got, ref[:M], bnd[:M], f"{epi_name} {FMT[dt]} M={M} N={N} K={K}")
+            ref_t = torch.from_numpy(ref[:M]).float()
+            assert rel_l2(got.float(), ref_t.to(dt).float() if store else ref_t) <= TOL, (M, N)
+
+
+@pytest.mark.parametrize("dt", DTYPES)
+def test_gemm_nf4_folded_norm_every_role_within_bound(dev, dt):
+    """the decode step's folded RMSNorm at 7B width, every row count of both instantiations: producer (down_proj: x += h Wdown^T,
+    xw = op16(x .* w_next), partial sums of x^2) and both consumers of its output (qkv: EPI_BF16 at N = 3 H; gate/up: SwiGLU), each element
+    against fp64 scaled by the fp64 rstd of the produced x"""
+    from vitron_amd import ops
+    H, I, eps = 4096, 11008, 1e-5
+    fmt = FMT[dt]
+    c_o, s_o, w_o = _rnd_dev(H, I, 21, dt, dev)
+    consumers = [("qkv", ops.EPI_BF16, _rnd_dev(3 * H, H, 22, dt, dev)), ("gate_up", ops.EPI_SWIGLU_BF16, _rnd_dev(2 * I, H, 23, dt, dev, SWIGLU_RANGE))]
+    h = _w((32, I), 24, 1.0).to(dt)
+    x0 = _w((32, H), 25, 4.0)
+    wn = 1.0 + _w((H,), 26, 0.1)
+    h64, x064, wn64 = h.double().numpy(), x0.double().numpy(), wn.double().numpy()
+    y_o = h64 @ w_o.T
+    # the kernel's rstd comes from fp32 sums: 16 squares per partial, H / 256 partials per thread, 16 threads; then * 1/H, + eps, rsqrt
+    rstd_rel = (H // 256 + 16 + 4 + 8) * R.U32
+    for M in (1, 2, 16, 17, 31, 32):
+        x = x0[:M].to(dev).clone()
+        xw = torch.empty((M, H), device=dev, dtype=dt)
+        part = torch.empty((M, H // 16), device=dev)
+        ops.gemm_nf4(h[:M].to(dev), c_o, s_o, ops.EPI_F32_RESID, out=x, norm_out=(wn.to(dev), xw, part))
+        _within(x, R.gemm_ref(h64[:M], w_o, resid=x064[:M], y=y_o[:M]), R.gemm_bound(h64[:M], w_o, I, resid=x064[:M], y=y_o[:M]), f"producer x M={M}")
+        xg = x.cpu().double()
+        p = xg.numpy() * wn64                                # xw = op16(fp32(x * w)): two roundings
+        _within(xw, p, R.U32 * np.abs(p) + R.half_ulp(np.abs(p) * (1 + R.U32), fmt), f"producer xw M={M}")
+        assert rel_l2(part.cpu(), (xg * xg).view(M, H // 16, 16).sum(-1)) <= 1e-6
+        rstd = (1.0 / torch.sqrt((xg * xg).mean(-1) + eps)).numpy()
+        a64 = xw.cpu().double().numpy()
+        for name, epi, (c, s, wd) in consumers:
+            swiglu = epi == ops.EPI_SWIGLU_BF16
+            got = ops.gemm_nf4(xw, c, s, epi, norm_in=(part, 1.0 / H, eps))
+            y = a64 @ wd.T
+            ref = R.gemm_ref(a64, wd, rscale=rstd, swiglu=swiglu, y=y)
+            _within(got, ref, R.gemm_bound(a64, wd, H, rscale=rstd, rscale_rel=rstd_rel, swiglu=swiglu, store=fmt, y=y), f"{name} {fmt} M={M}")
+            assert rel_l2(got.float(), torch.from_numpy(ref).float().to(dt).float()) <= TOL, (name, M)
+
+
 # ---- the 4-bit decoder against the 16-bit decoder of its dequantised weights ------------------------------------------------------------
 def _llama_sd(cfg, seed):
     from vitron_amd import synth
@@ -220,6 +387,97 @@ def test_nf4_prefill_bitwise_equals_dequantised_16bit_and_decode_agrees(dev, pai
     a, _, _ = _run(q, emb2, 0)
     b, _, _ = _run(p16, emb2, 0)
     assert rel_l2(a, b) <= DECODE_TOL
+
+
+def _emb(rows, H, dt, dev, seed):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn((rows, H), generator=g) * 0.5).to(dt).to(dev)
+
+
+def _pasts_on_both(q, p16, pasts, pages, seed):
+    """both decoders prefill the same pasts in one batch (> 32 rows: dequantised weights on the tile GEMMs, so bit-equal caches)"""
+    from vitron_amd.engine import PagedKVCache, SequenceState, llama_forward
+    emb = _emb(sum(pasts), q.H, q.dtype, q.device, seed)
+    out = []
+    for pl in (q, p16):
+        kv = PagedKVCache(pl, pages)
+        seqs = [SequenceState() for _ in pasts]
+        lg = llama_forward(pl, kv, seqs, emb, list(pasts)).float()
+        out.append((kv, seqs, lg))
+    assert torch.equal(out[0][2], out[1][2])
+    return out
+
+
+def _decode_steps(q, p16, state, n_steps):
+    """n_steps decode steps of every sequence on both decoders, both fed the 16-bit decoder's greedy tokens: [(logits4, logits16)] on the CPU"""
+    from vitron_amd.engine import llama_forward
+    (kv4, s4, _), (kv16, s16, last) = state
+    steps = []
+    for _ in range(n_steps):
+        e = p16.embed[last.argmax(-1)].contiguous()
+        a = llama_forward(q, kv4, s4, e, [1] * len(s4)).float()
+        b = llama_forward(p16, kv16, s16, e, [1] * len(s16)).float()
+        steps.append((a.cpu(), b.cpu()))
+        last = b
+    return steps
+
+
+def _agree(a, b, what):
+    """one sequence's logits: DECODE_TOL, and an arg-max flip only where the 16-bit top-2 margin is inside the noise of that bound"""
+    assert rel_l2(a, b) <= DECODE_TOL, what
+    if int(a.argmax()) != int(b.argmax()):
+        top2 = b.topk(2).values
+        assert float(top2[0] - top2[1]) <= 2 * DECODE_TOL * float(b.pow(2).mean().sqrt()), what
+
+
+def _pasts(B):
+    """1, 63, 64, 65 tokens (page edges) and 128 .. 134 (a page edge inside the second page), cycling"""
+    return [(1, 63, 64, 65)[i % 5] if i % 5 < 4 else 128 + i // 5 for i in range(B)]
+
+
+@pytest.mark.parametrize("B", [20, 32])
+def test_nf4_decode_17_to_32_sequences_agree(dev, pair7b, B):
+    """17 .. 32 sequences decoding at once: the NF4 branch without the norm fold (norms as launches, gemm_nf4, fused decode attention)"""
+    dt, cfg, q, p16 = pair7b
+    state = _pasts_on_both(q, p16, _pasts(B), 3 * B + 4, 40 + B)
+    for t, (a, b) in enumerate(_decode_steps(q, p16, state, 4)):
+        for i in range(B):
+            _agree(a[i], b[i], (B, t, i))
+
+
+def test_nf4_decode_40_sequences_bitwise_equals_dequantised_16bit(dev, pair7b):
+    """> 32 decode rows: every Linear dequantised into the workspace in front of the same tile GEMMs the 16-bit decoder runs"""
+    dt, cfg, q, p16 = pair7b
+    state = _pasts_on_both(q, p16, _pasts(40), 124, 80)
+    for t, (a, b) in enumerate(_decode_steps(q, p16, state, 4)):
+        assert torch.equal(a, b), t
+
+
+@pytest.mark.parametrize("n", [40, 64])
+def test_nf4_prefill_33_to_64_rows_bitwise_equals_dequantised_16bit(dev, pair7b, n):
+    dt, cfg, q, p16 = pair7b
+    emb = _emb(n, cfg["hidden_size"], dt, dev, 90 + n)
+    a, _, _ = _run(q, emb, 0)
+    b, _, _ = _run(p16, emb, 0)
+    assert torch.equal(a, b)
+
+
+def test_nf4_chunk_after_a_past_next_to_decodes_agrees(dev, pair7b):
+    """one launch of <= 32 rows mixing a 12-row chunk that goes on from a 200-token past with 3 single-token decodes: the NF4 branch's
+    kv_tiles + flash_attn; then one decode step of all four (the folded 4-launch layer) on the cache that launch wrote"""
+    from vitron_amd.engine import llama_forward
+    dt, cfg, q, p16 = pair7b
+    state = _pasts_on_both(q, p16, [200, 1, 64, 129], 16, 100)
+    emb = _emb(15, cfg["hidden_size"], dt, dev, 101)
+    (kv4, s4, _), (kv16, s16, _) = state
+    a = llama_forward(q, kv4, s4, emb, [12, 1, 1, 1], logit_rows=list(range(15))).float().cpu()
+    b = llama_forward(p16, kv16, s16, emb, [12, 1, 1, 1], logit_rows=list(range(15))).float().cpu()
+    for r in range(15):
+        _agree(a[r], b[r], ("chunk", r))
+    last = b[[11, 12, 13, 14]].to(dev)
+    for t, (a, b) in enumerate(_decode_steps(q, p16, ((kv4, s4, None), (kv16, s16, last)), 1)):
+        for i in range(4):
+            _agree(a[i], b[i], ("after", t, i))
 
 
 # ---- public surface ---------------------------------------------------------------------------------------------------------------

@@ -98,3 +98,90 @@ def test_load_8bit_still_refused_and_4bit_flag_reaches_the_model():
     assert "load_4bit" in inspect.signature(builder.load_pretrained_model).parameters
     from vitron_amd.model import LlavaConfig, LlavaLlamaForCausalLM
     assert LlavaLlamaForCausalLM(LlavaConfig()).weight_format == "16bit"
+
+
+# ---- nf4_ref.random_nf4 and nf4_ref.gemm_bound (the GPU GEMM tests' input and limit) -------------------------------------------------
+def test_random_nf4_covers_every_byte_and_spreads_fp16_scales():
+    codes, absmax = R.random_nf4(64, 1024, 3)
+    assert codes.dtype == np.uint8 and codes.size == 64 * 512 and absmax.dtype == np.float32 and absmax.size == 64 * 16
+    assert np.unique(codes).size == 256                                       # every (high, low) code pair
+    assert np.array_equal(absmax, absmax.astype(np.float16).astype(np.float32))  # fp16 values, as a real absmax
+    e = np.floor(np.log2(absmax))
+    assert e.min() == -12 and e.max() == 3 and np.unique(e).size == 16
+    assert np.abs(np.diff(e)).max() >= 10                                     # neighbouring blocks far apart in scale
+    d = R.dequantize_f32(codes, absmax, 64, 1024)
+    assert np.any((d != 0) & (np.abs(d) < 2.0 ** -14))                         # fp16 subnormal weights at the low end
+    c2, a2 = R.random_nf4(64, 1024, 3)
+    assert np.array_equal(codes, c2) and np.array_equal(absmax, a2)
+
+
+def test_half_ulp():
+    assert R.half_ulp(np.array([1.0]), "bf16")[0] == 2.0 ** -8 and R.half_ulp(np.array([1.0]), "fp16")[0] == 2.0 ** -11
+    assert R.half_ulp(np.array([3.0]), "bf16")[0] == 2.0 ** -7 and R.half_ulp(np.array([2.0 ** -20]), "fp16")[0] == 2.0 ** -25
+
+
+def _op16(x, fmt):
+    import torch
+    dt = {"bf16": torch.bfloat16, "fp16": torch.float16}[fmt]
+    return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dt).double().numpy()
+
+
+def _bound_case(fmt, K, N=96, M=8, seed=5, log2_range=(-12, 4)):
+    codes, absmax = R.random_nf4(N, K, seed, log2_range)
+    wd = _op16(R.dequantize_f32(codes, absmax, N, K), fmt)
+    a = _op16(np.random.default_rng(seed + 1).standard_normal((M, K)), fmt)
+    return codes, absmax, wd, a
+
+
+@pytest.mark.parametrize("fmt", ["bf16", "fp16"])
+@pytest.mark.parametrize("K", [128, 1152, 4096])
+def test_gemm_bound_holds_for_a_cpu_fp32_gemm(fmt, K):
+    """an fp32 product of the same operands (another summation order, then the kernels' epilogue arithmetic in fp32) stays inside the bound,
+    in every epilogue; the bound is far below the values, and the 16-bit store term dominates it"""
+    _, _, wd, a = _bound_case(fmt, K)
+    y32 = a.astype(np.float32) @ wd.astype(np.float32).T
+    # EPI_F32
+    ref = R.gemm_ref(a, wd)
+    bnd = R.gemm_bound(a, wd, K)
+    assert np.all(np.abs(y32 - ref) <= bnd) and np.all(bnd <= 1e-3 * (np.abs(a) @ np.abs(wd).T))
+    # EPI_BF16 (operand out)
+    assert np.all(np.abs(_op16(y32, fmt) - ref) <= R.gemm_bound(a, wd, K, store=fmt))
+    # EPI_F32_RESID
+    r = np.random.default_rng(9).standard_normal(ref.shape).astype(np.float32) * 4
+    assert np.all(np.abs((r + y32) - R.gemm_ref(a, wd, resid=r)) <= R.gemm_bound(a, wd, K, resid=r))
+    # folded RMSNorm consumer: an fp32 rstd one part in 2^20 off the fp64 one
+    rs = np.linspace(0.01, 3.0, a.shape[0])
+    rs32 = (rs * (1 + 2.0 ** -20)).astype(np.float32)
+    assert np.all(np.abs(_op16(y32 * rs32[:, None], fmt) - R.gemm_ref(a, wd, rscale=rs)) <=
+                  R.gemm_bound(a, wd, K, rscale=rs, rscale_rel=2.0 ** -19, store=fmt))
+    # SwiGLU (gate / up scales below 1, as the GPU test's, so that silu(g) * u stays inside fp16)
+    _, _, wd, a = _bound_case(fmt, K, log2_range=(-12, 0))
+    y32 = a.astype(np.float32) @ wd.astype(np.float32).T
+    g32 = y32.reshape(a.shape[0], -1, 2, 16)
+    with np.errstate(over="ignore"):                                           # exp(-g) = inf -> silu = -0, as on the GPU
+        s32 = g32[:, :, 0] * (np.float32(1) / (np.float32(1) + np.exp(-g32[:, :, 0])))
+    sw = _op16((s32 * g32[:, :, 1]).reshape(a.shape[0], -1), fmt)
+    assert np.all(np.abs(sw - R.gemm_ref(a, wd, swiglu=True)) <= R.gemm_bound(a, wd, K, swiglu=True, store=fmt))
+
+
+@pytest.mark.parametrize("fmt", ["bf16", "fp16"])
+def test_gemm_bound_catches_one_wrong_block_scale(fmt):
+    """the weights the kernel would use if it read one block's absmax twice as large, or its neighbour's, fall outside the bound in that
+    block's column -- and only there. (The row's largest block: an error confined to a block 2^16 below its row's largest is inside the
+    accumulation bound of that row; the GPU tests' exact unit probes see every element on its own.)"""
+    K, N = 1152, 96
+    codes, absmax, wd, a = _bound_case(fmt, K)
+    ref, bnd = R.gemm_ref(a, wd), R.gemm_bound(a, wd, K, store=fmt)
+    kpr = K // 64
+    for n in (0, 37, 95):
+        row = absmax[n * kpr:(n + 1) * kpr]
+        b = int(np.argmax(row))
+        for wrong in (row[b] * 2, row[b - 1] if b else row[b + 1]):
+            if wrong == row[b]:
+                continue
+            bad = absmax.copy()
+            bad[n * kpr + b] = wrong
+            got = _op16(R.gemm_ref(a, _op16(R.dequantize_f32(codes, bad, N, K), fmt)), fmt)
+            out = np.abs(got - ref) > bnd
+            assert out[:, n].any(), (n, b)
+            assert not np.delete(out, n, axis=1).any()
