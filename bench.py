@@ -6,6 +6,7 @@ with the 512-token prompt (S = 8*576 + 512 = 5120) -> 32-layer Vicuna-7B-shaped 
 last-position logits -> greedy first token. Everything runs through libvitron_hip.so.
 
   python bench.py --gpus 1 --steps 5 --warmup 2 [--dump-outputs DIR]   (DIR: what the last timed step returned, as .npy)
+  python bench.py --gpus 1 --steps 5 --warmup 2 --full                  (everything else this benchmark measures, see below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
   python bench.py --gpus N ...        (plain python, N > 1: re-launches itself under torch.distributed.run on a free port; on a box
                                        with fewer than N GPUs it prints one JSON error line and exits 2)
@@ -14,9 +15,14 @@ N > 1: one process per GPU, one clip per rank (weak scaling). Clips are encoded 
 visual tokens are exchanged with ONE RCCL all-gather over xGMI (BASELINE config 4) that overlaps the rank's own
 prefill (started asynchronously, waited for before the step ends), and every rank prefills its own sequence. value = (tokens of all ranks) / (max over ranks of the timed region).
 
-Prints ONE JSON line (rank 0) with the driver's contract + "roofline" (dominant kernel class = the MFMA tile GEMM,
-timed live with HIP events on the kernel's stream) + "cpu_baseline" (the CPU oracle on the whole workload at full depth) and,
-at N = 1, the secondary objects config.c2 (BASELINE configs[1]), config.c4 (configs[3], strong scaling) and decode (configs[4]).
+Prints ONE JSON line (rank 0). A plain run does only what that line's headline needs: set up, warm up, time the steps, write
+--dump-outputs, print the driver's contract (value, ms_per_step, ...) with the step's algorithmic rate in `config`.
+--full adds, after the timed region, "roofline" (dominant kernel class = the MFMA tile GEMM, timed with HIP events on the
+kernel's stream in a separate pass; traffic from rocprofv3 child processes) + "cpu_baseline" (the CPU oracle / the reference on
+the whole workload at full depth) + "parity" and, at N = 1, the secondary objects config.c2 (BASELINE configs[1]), config.c4
+(configs[3], strong scaling), the 224 px configurations, config.fp16_ab / at_tolerance and decode (configs[4]); at N > 1,
+config.c4 and config.visual_token_exchange. The options that switch or size those extras (--no-cpu-baseline, --decode-steps,
+--c4-steps, ...) run nothing without --full.
 """
 from __future__ import annotations
 
@@ -1151,33 +1157,37 @@ def main():
     ap.add_argument("--image-size", type=int, default=336)
     ap.add_argument("--frames", type=int, default=8)
     ap.add_argument("--text-len", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, everything else this benchmark measures (per-kernel roofline pass and live PMC traffic, CPU "
+                         "baselines, parity against the reference, the other configurations, fp16 and precise modes, decode, empirical "
+                         "peaks; at N > 1 the strong-scaling batch and the exchange alone) -- minutes of extra work; off: the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full, N=1: skip the CPU baseline")
     ap.add_argument("--cpu-baseline", choices=("full", "sample"), default="full",
-                    help="N=1 only: time the CPU oracle on the whole workload at full depth (~2 min of CPU work) or on a bounded sample")
+                    help="--full, N=1: time the CPU oracle on the whole workload at full depth (~2 min of CPU work) or on a bounded sample")
     ap.add_argument("--cpu-baseline-kind", choices=("auto", "reference", "port"), default="auto",
-                    help="N=1 only: 'reference' = the reference's own modules (staged archive oracle/_ref/vitron_ref.zip) at full depth at 336 and 224 "
+                    help="--full, N=1: 'reference' = the reference's own modules (staged archive oracle/_ref/vitron_ref.zip) at full depth at 336 and 224 "
                          "(~3-4 min of CPU work) with a bounded sample of the port beside it; 'port' = the oracle only; 'auto' = reference when staged")
     ap.add_argument("--decode-steps", type=int, default=1024,
-                    help="N=1 only: after the timed prefill region, BASELINE configs[4]: 4 x (image + box) prefill + this many batch-4 "
-                         "greedy decode steps through generate() (0 = skip)")
+                    help="--full, N=1: after the timed prefill region, BASELINE configs[4]: 4 x (image + box) prefill + this many batch-4 "
+                         "greedy decode steps through generate() (0 = skip; with --c2-reps 0 the image tower is then not built, in any run)")
     ap.add_argument("--c2-reps", type=int, default=10,
-                    help="N=1 only: after the timed region, BASELINE configs[1] (one 336 px image + 512 tokens) this many times (0 = skip)")
+                    help="--full, N=1: after the timed region, BASELINE configs[1] (one 336 px image + 512 tokens) this many times (0 = skip)")
     ap.add_argument("--reps-224", type=int, default=10,
-                    help="N=1 only: after the timed region, configs[2] and configs[1] at the reference-native 224 px (S = 2560 / 768) this many times (0 = skip)")
-    ap.add_argument("--no-empirical-peaks", action="store_true", help="skip the hipBLASLt-8192^3 / D2D-copy empirical peaks")
+                    help="--full, N=1: after the timed region, configs[2] and configs[1] at the reference-native 224 px (S = 2560 / 768) this many times (0 = skip)")
+    ap.add_argument("--no-empirical-peaks", action="store_true", help="--full: skip the hipBLASLt-8192^3 / D2D-copy empirical peaks")
     ap.add_argument("--c4-steps", type=int, default=5,
-                    help="after the timed region: the fixed 8-clip global batch of BASELINE configs[3] for this many steps (0 = skip)")
+                    help="--full: after the timed region, the fixed 8-clip global batch of BASELINE configs[3] for this many steps (0 = skip)")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--dtype", choices=("bf16", "fp16"), default="bf16",
                     help="operand format of the headline run: bf16 (BASELINE.json's dtype, libvitron_hip.so) or fp16 (the reference's own "
                          "inference dtype, libvitron_hip_f16.so)")
     ap.add_argument("--fp16-ab-steps", type=int, default=5,
-                    help="N=1, --dtype bf16 only: after everything else, the SAME workload on the fp16-operand build for this many steps "
+                    help="--full, N=1, --dtype bf16 only: after everything else, the SAME workload on the fp16-operand build for this many steps "
                          "(same box, same seed): step time next to the headline's and the distance of its logits from the bf16 run's (0 = skip)")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="skip the two rocprofv3 --pmc child processes that fill roofline.traffic live (then the committed counter file is quoted)")
+                    help="--full: skip the two rocprofv3 --pmc child processes that fill roofline.traffic live (then the committed counter file is quoted)")
     ap.add_argument("--no-parity", action="store_true",
-                    help="N=1 only: skip the `parity` object (one full-depth prefill of BASELINE configs[2] with all logit rows per mode -- the timed "
+                    help="--full, N=1: skip the `parity` object (one full-depth prefill of BASELINE configs[2] with all logit rows per mode -- the timed "
                          "mode and the at-tolerance mode -- against the reference's stored output, tests/golden/fulldepth_c3.npz)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last one returned (rank 0) as DIR/<name>.npy: the last-position fp32 "
@@ -1219,7 +1229,9 @@ def main():
     n_vis = args.frames * G * G
     S = n_vis + args.text_len
     vit_video = dict(synth.VIT_L14, image_size=args.image_size, add_time_attn=True, num_frames=args.frames)
-    # the image tower is only needed by the secondary C2 / C5 reports (configs[1] / configs[4]) of a single-GPU run
+    # the image tower is only used by the secondary C2 / C5 reports (configs[1] / configs[4]) of a single-GPU --full run, but it is
+    # built by the same rule with or without --full: its weights come from the seeded stream ahead of the video tower's, projector's
+    # and region extractor's, so leaving it out would change the headline's weights and outputs
     want_image = world == 1 and (args.c2_reps > 0 or args.decode_steps > 0)
     vit_image = dict(synth.VIT_L14, image_size=336) if want_image else None
     cfg = LlavaConfig(**synth.VICUNA_7B, mm_hidden_size=1024)
@@ -1295,6 +1307,35 @@ def main():
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
     value = world * S * args.steps / dt
+    fl = algorithmic_flops(S, n_vis, args.frames, G * G + 1, G * G)
+    out = {
+        "metric": "visual-tokens+text-tokens/sec end-to-end prefill, 8-frame 336px clip, 1/2/4/8 GPU",
+        "value": value, "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": args.dtype, "data": "synthetic", "full": args.full,
+        "config": {
+            "workload": (f"BASELINE configs[2]: {args.frames}-frame {args.image_size}x{args.image_size} clip "
+                         f"({n_vis} visual tokens) + {args.text_len}-token prompt -> S={S}; LanguageBind video ViT-L/14 "
+                         "(23 of 24 layers, temporal attention) + mlp2x_gelu projector + Vicuna-7B-shaped decoder prefill "
+                         "(32 layers, paged KV), last-position logits + greedy token; random-init weights"),
+            "clips_per_gpu": 1, "tokens_per_step_per_gpu": S, "parallelism": f"clip-parallel x{world} + all-gather of visual tokens" if world > 1 else "single GPU",
+            "timing": "value / ms_per_step: wall clock over the K timed steps between barrier+synchronize fences (max over ranks); "
+                      "ms_per_step_hipevent_median: median of the K per-step HIP-event intervals on the compute stream of rank 0",
+            "ms_per_step_hipevent_median": step_ms[len(step_ms) // 2], "ms_per_step_hipevent_min": step_ms[0],
+            "ms_per_step_hipevent_max": step_ms[-1],
+            "algorithmic_tflop_per_step": fl["total"] / 1e12,
+            "end_to_end_tflops_per_gpu": fl["total"] / 1e12 / (ms_per_step * 1e-3),
+            "end_to_end_frac_of_mfma_peak": fl["total"] / 1e12 / (ms_per_step * 1e-3) / MFMA_BF16_PEAK_TFLOPS,
+        },
+    }
+    if not args.full:
+        # a plain run ends with its headline: everything below runs passes of its own after the timed region
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # ---- per-kernel-class device times: a SEPARATE pass (an event pair around each of the ~390 instrumented launches of a step
     # perturbs the wall clock, so it must not sit inside the timed region)
     prof_steps = max(2, min(args.steps, 4))
@@ -1328,30 +1369,11 @@ def main():
     if rank == 0:
         gt = prof["gemm_tile"]
         achieved = gt["work"] / (gt["ms"] * 1e-3) / 1e12 if gt["ms"] > 0 else 0.0
-        fl = algorithmic_flops(S, n_vis, args.frames, G * G + 1, G * G)
         traffic, traffic_build, traffic_file = pmc_traffic_per_launch()
         live_traffic, live_note = (None, "skipped (--no-live-traffic)") if (args.no_live_traffic or world > 1) else live_pmc_traffic(args.dtype)
-        out = {
-            "metric": "visual-tokens+text-tokens/sec end-to-end prefill, 8-frame 336px clip, 1/2/4/8 GPU",
-            "value": value, "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": args.dtype, "data": "synthetic",
-            "config": {
-                "workload": (f"BASELINE configs[2]: {args.frames}-frame {args.image_size}x{args.image_size} clip "
-                             f"({n_vis} visual tokens) + {args.text_len}-token prompt -> S={S}; LanguageBind video ViT-L/14 "
-                             "(23 of 24 layers, temporal attention) + mlp2x_gelu projector + Vicuna-7B-shaped decoder prefill "
-                             "(32 layers, paged KV), last-position logits + greedy token; random-init weights"),
-                "clips_per_gpu": 1, "tokens_per_step_per_gpu": S, "parallelism": f"clip-parallel x{world} + all-gather of visual tokens" if world > 1 else "single GPU",
-                "timing": "value / ms_per_step: wall clock over the K timed steps between barrier+synchronize fences (max over ranks); "
-                          "ms_per_step_hipevent_median: median of the K per-step HIP-event intervals on the compute stream of rank 0",
-                "ms_per_step_hipevent_median": step_ms[len(step_ms) // 2], "ms_per_step_hipevent_min": step_ms[0],
-                "ms_per_step_hipevent_max": step_ms[-1],
-                "algorithmic_tflop_per_step": fl["total"] / 1e12,
-                "end_to_end_tflops_per_gpu": fl["total"] / 1e12 / (ms_per_step * 1e-3),
-                "end_to_end_frac_of_mfma_peak": fl["total"] / 1e12 / (ms_per_step * 1e-3) / MFMA_BF16_PEAK_TFLOPS,
-                "kernel_ms_per_step": {k: v["ms"] / prof_steps for k, v in prof.items() if v["launches"]},
-                "kernel_ms_note": f"HIP-event time per kernel class from a separate pass of {prof_steps} steps after the timed region",
-            },
+        out["config"]["kernel_ms_per_step"] = {k: v["ms"] / prof_steps for k, v in prof.items() if v["launches"]}
+        out["config"]["kernel_ms_note"] = f"HIP-event time per kernel class from a separate pass of {prof_steps} steps after the timed region"
+        out.update({
             "roofline": {"bound": "mfma", "kernel": args.dtype + " MFMA tile GEMM class: gemm_w4_kernel<*> (256x256 / 320x256 tile, four waves of 128x128 / 160x128, ~96 % of the class time) + gemm_w4r_kernel<*> (160x128 tile on a four-deep LDS ring: N = 1024 projections) + gemm_p8_kernel<*,0,true> (4-phase ping-pong: activation epilogues on 256-row tiles, split-K) + gemm_bt_kernel<*> (small tiles) + splitk_reduce_resid_kernel, all epilogues",
                          "achieved": achieved, "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": achieved / MFMA_BF16_PEAK_TFLOPS,
@@ -1370,7 +1392,7 @@ def main():
                          "launches_per_step": gt["launches"] / prof_steps,
                          "avg_launch_ms": gt["ms"] / max(gt["launches"], 1),
                          "algorithmic_gflop_per_launch": gt["work"] / max(gt["launches"], 1) / 1e9},
-        }
+        })
         if c4 is not None:
             out["config"]["c4"] = c4
             # SURVEY.md 8(e)'s >= 6x target is defined on THIS quantity (fixed 8-clip batch), not on the weak-scaling `value`

@@ -290,8 +290,9 @@ def test_image_tower_full_size_batch_independence(dev, model7b):
 
 def test_bench_distributed_path_on_one_gpu(dev):
     """bench.py's N > 1 plumbing (RCCL process group, all-gather of the visual tokens, barrier, max-reduce of the time) driven
-    on ONE GPU through `torch.distributed.run --nproc-per-node 1` + VT_BENCH_FORCE_DIST=1: must print exactly one JSON line
-    with the driver's keys. (The collective's cross-rank behaviour is covered on gloo, world size 2, in test_parallel_gloo.py.)"""
+    on ONE GPU through `torch.distributed.run --nproc-per-node 1` + VT_BENCH_FORCE_DIST=1, with --full (the roofline pass, C4 and
+    the exchange step): must print exactly one JSON line with the driver's keys. (The collective's cross-rank behaviour is covered
+    on gloo, world size 2, in test_parallel_gloo.py.)"""
     import json
     import os
     import random
@@ -301,7 +302,7 @@ def test_bench_distributed_path_on_one_gpu(dev):
     env = dict(os.environ, VT_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     port = str(random.randint(20000, 40000))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", port, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
+           "--master-port", port, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--full",
            "--no-cpu-baseline", "--decode-steps", "0", "--c2-reps", "0", "--no-empirical-peaks", "--c4-steps", "1", "--no-parity", "--no-live-traffic",
            "--reps-224", "0", "--fp16-ab-steps", "0"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
@@ -325,6 +326,38 @@ def test_bench_distributed_path_on_one_gpu(dev):
     ex = d["config"]["visual_token_exchange"]
     assert isinstance(ex["rccl_all_gather_ms"], float) and isinstance(ex["direct_p2p_ms"], float), ex
     assert d["config"]["ms_per_step_hipevent_median"] > 0
+
+
+def test_bench_plain_run_is_the_headline_only(dev, tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: one JSON line with the driver's keys and the timed region's own
+    figures, none of the objects that take passes of their own after it (roofline, per-kernel times, CPU baselines, parity, decode,
+    the other configurations), and --dump-outputs still writes what the last timed step returned."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out_dir = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out_dir)],
+                       cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "tokens/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "bf16" and d["full"] is False and d["ms_per_step"] > 0
+    assert abs(d["value"] - 5120 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-9
+    assert d["config"]["ms_per_step_hipevent_median"] > 0 and d["config"]["end_to_end_frac_of_mfma_peak"] > 0
+    for k in ("roofline", "cpu_baseline", "parity", "decode"):
+        assert k not in d, k
+    for k in ("kernel_ms_per_step", "c2", "c4", "c3_224", "c2_224", "fp16_ab", "at_tolerance", "visual_token_exchange"):
+        assert k not in d["config"], k
+    logits, tok = np.load(out_dir / "logits.npy"), np.load(out_dir / "next_token.npy")
+    assert logits.dtype == np.float32 and logits.shape == (1, 32000) and np.isfinite(logits).all()
+    assert tok.dtype == np.float64 and tok.shape == (1,) and 0 <= tok[0] < 32000 and tok[0] == int(tok[0])
 
 
 def test_fused_qkv_epilogue_matches_separate_kv_tiles_pass(dev):

@@ -1,7 +1,7 @@
 """The headline step's dominant launch alone -- gate/up of the C3 prefill, 5120 x 22016 x 4096 with the SwiGLU epilogue, as the dispatcher runs it
 (gemm_w4_kernel<6, 8>) -- eight times over four weight copies, for counter passes:
     rocprofv3 --pmc FETCH_SIZE -f csv -d out -- python tools/one_gemm.py [bf16|fp16]
-bench.py runs exactly this under rocprofv3 (two passes: FETCH_SIZE, WRITE_SIZE) to fill roofline.traffic live. Measurement helper."""
+bench.py --full runs exactly this under rocprofv3 (two passes: FETCH_SIZE, WRITE_SIZE) to fill roofline.traffic live. Measurement helper."""
 import os
 import sys
 
