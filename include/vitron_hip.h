@@ -75,6 +75,10 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
 
 #define VT_PAGE_TOKENS 64 /* tokens per KV-cache page == keys per attention tile */
 
+/* 114 also carries the FP8 KV cache entry points (vt_kv8_quant, vt_kv8_dequant, vt_attn_decode_kv8, vt_attn_decode_fused_kv8,
+ * vt_llama_workspace_bytes_kv8, vt_llama_forward_kv8 and struct vt_kv_cache8) WITHOUT a bump: the change is purely additive -- new
+ * symbols and one new struct, no existing struct gained a field, no existing function a parameter -- so every caller built against
+ * the earlier 114 header keeps working unchanged. A caller that needs the new entry points looks the symbols up. */
 #define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
@@ -502,6 +506,46 @@ int vt_llama_forward(const vt_llama_model* m, const vt_kv_cache* kv, const uint1
                      const int* positions, const int* seq_desc, int nseq, int max_q_len, int max_new_tiles, int max_kv_len,
                      const int* tile_table, const int* logit_rows, int n_logit_rows, float* logits,
                      float* out_hidden, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- FP8 KV CACHE (opt-in: config.kv_cache_dtype = "fp8"; no reference counterpart) -----------------------------------
+ * Page format: the 16-bit layouts with 1-byte elements -- k [num_layers][num_pages][heads][64][head_dim], vt [num_layers][num_pages]
+ * [heads][head_dim][64]; VT_PAGE_TOKENS stays 64, so tile tables and page counts carry over. Element: OCP e4m3fn (gfx950's native fp8;
+ * bias 7, no infinity, 0x7f / 0xff = NaN, largest finite 448), no scale factors. A byte is e4m3_rne(clamp(x16, -448, +448)) where
+ * x16 is exactly what the 16-bit cache holds at that position (K: rotated in fp32, rounded once to the operand format; V: the fp16
+ * page value): for the same inputs  fp8 page == vt_kv8_quant(16-bit page)  byte for byte. Padding rows / columns of a tile are 0x00.
+ * Half the pool bytes per token and half the bytes a decode step streams; the price is e4m3's 3 mantissa bits on K and V. */
+typedef struct vt_kv_cache8 {
+  uint8_t* k;
+  uint8_t* vt;
+  int num_pages;
+} vt_kv_cache8;
+/* whole tiles: 16-bit tile src_table[i] (of k_tiles / vt_tiles, one layer) -> fp8 page dst_table[i] (of k8 / vt8), K and V^T in one launch;
+ * and back. Dequantisation is exact in both operand formats; quantising a dequantised tile is the identity on every finite code. */
+int vt_kv8_quant(const uint16_t* k_tiles, const uint16_t* vt_tiles, const int* src_table, uint8_t* k8, uint8_t* vt8,
+                 const int* dst_table, int ntiles, int heads, int head_dim, void* stream);
+int vt_kv8_dequant(const uint8_t* k8, const uint8_t* vt8, const int* src_table, uint16_t* k_tiles, uint16_t* vt_tiles,
+                   const int* dst_table, int ntiles, int heads, int head_dim, void* stream);
+/* vt_attn_decode on fp8 pages (same arguments, same scratch: vt_attn_decode_scratch_bytes) */
+int vt_attn_decode_kv8(const uint16_t* Q, int ldq, const uint8_t* k8, const uint8_t* vt8, const int* tile_table,
+                       const int* seq_desc, int nseq, uint16_t* O, int ldo, int heads, int head_dim, float scale,
+                       int max_kv_len, void* scratch, size_t scratch_bytes, void* stream);
+/* vt_attn_decode_fused on fp8 pages: the new k row / v column are quantised, stored, and the new token is SCORED FROM ITS QUANTISED
+ * VALUE (what every later step reads), so the step equals vt_attn_decode_kv8 on the cache it leaves behind. */
+int vt_attn_decode_fused_kv8(const uint16_t* qkv, int ldqkv, int q_col0, int k_col0, int v_col0, uint8_t* k8, uint8_t* vt8,
+                             const int* tile_table, const int* seq_desc, int nseq, uint16_t* O, int ldo, int heads, int head_dim,
+                             float scale, const float* rope_cos, const float* rope_sin, const int* positions, void* stream);
+/* vt_llama_forward on an fp8 pool. n_table_tiles = number of entries of tile_table. Decode steps (max_q_len == 1) run
+ * vt_attn_decode_fused_kv8 in place of the 16-bit kernel, nothing else differs. Prefills run the unchanged 16-bit kernels on a
+ * staging pool of n_table_tiles K + V^T tiles of ONE layer carved from the workspace (identity tile table), per layer: dequantise the
+ * past tiles of sequences with kv_len > q_len, vt_kv_tiles + vt_flash_attn on the staging pool, quantise tiles [past / 64, ntiles)
+ * back into the pages. A prefill without a past therefore returns logits bit-equal to the 16-bit cache's; a pass that mixes a chunk
+ * with long decoding sequences stages every sequence's whole past per layer (correct, costly: keep them in separate passes).
+ * precise_qk >= 1 and qkv_fuse == 1 are refused (status -1), never run as a silent 16-bit pass. */
+size_t vt_llama_workspace_bytes_kv8(const vt_llama_model* m, int rows, int n_logit_rows, int nseq, int max_kv_len, int n_table_tiles);
+int vt_llama_forward_kv8(const vt_llama_model* m, const vt_kv_cache8* kv, const uint16_t* x_embeds, int rows,
+                         const int* positions, const int* seq_desc, int nseq, int max_q_len, int max_new_tiles, int max_kv_len,
+                         const int* tile_table, int n_table_tiles, const int* logit_rows, int n_logit_rows, float* logits,
+                         float* out_hidden, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Per-kernel-class timing (the reference has no tracing on this path). Between vt_profile_begin and

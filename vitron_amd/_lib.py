@@ -72,6 +72,10 @@ class VtKvCache(C.Structure):
     _fields_ = [("k", vp), ("vt", vp), ("num_pages", C.c_int)]
 
 
+class VtKvCache8(C.Structure):   # the FP8 (e4m3fn) pool: the same fields, pages of one byte per element
+    _fields_ = [("k", vp), ("vt", vp), ("num_pages", C.c_int)]
+
+
 _i, _f, _sz = C.c_int, C.c_float, C.c_size_t
 # name -> (restype, argtypes); this table is also what tests check against the header
 SIGNATURES = {
@@ -128,6 +132,13 @@ SIGNATURES = {
     "vt_nf4_quant": (_i, [vp, _i, _i, _i, _i, vp, vp, vp]),
     "vt_nf4_dequant": (_i, [vp, vp, _i, _i, vp, _i, vp]),
     "vt_gemm_nf4": (_i, [vp, _i, vp, vp, vp, _i, _i, _i, _i, _i, vp, _i, _f, _f, vp, vp, _i, vp, vp]),
+    "vt_kv8_quant": (_i, [vp, vp, vp, vp, vp, vp, _i, _i, _i, vp]),
+    "vt_kv8_dequant": (_i, [vp, vp, vp, vp, vp, vp, _i, _i, _i, vp]),
+    "vt_attn_decode_kv8": (_i, [vp, _i, vp, vp, vp, vp, _i, vp, _i, _i, _i, _f, _i, vp, _sz, vp]),
+    "vt_attn_decode_fused_kv8": (_i, [vp, _i, _i, _i, _i, vp, vp, vp, vp, _i, vp, _i, _i, _i, _f, vp, vp, vp, vp]),
+    "vt_llama_workspace_bytes_kv8": (_sz, [C.POINTER(VtLlamaModel), _i, _i, _i, _i, _i]),
+    "vt_llama_forward_kv8": (_i, [C.POINTER(VtLlamaModel), C.POINTER(VtKvCache8), vp, _i, vp, vp, _i, _i, _i, _i, vp, _i, vp,
+                                  _i, vp, vp, vp, _sz, vp]),
 }
 PROF_CLASSES = ("gemm_tile", "flash_attn", "gemm_skinny", "attn_decode")
 

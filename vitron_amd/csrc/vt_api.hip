@@ -339,6 +339,28 @@ int vt_attn_decode_fused(const uint16_t* qkv, int ldqkv, int q_col0, int k_col0,
                                      positions, S(stream));
 }
 
+// ---- FP8 KV cache (vt_kv8.hip) ----
+int vt_kv8_quant(const uint16_t* k_tiles, const uint16_t* vt_tiles, const int* src_table, uint8_t* k8, uint8_t* vt8,
+                 const int* dst_table, int ntiles, int heads, int head_dim, void* stream) {
+  return vt_kv8_quant_launch(k_tiles, vt_tiles, src_table, k8, vt8, dst_table, ntiles, heads, head_dim, S(stream));
+}
+int vt_kv8_dequant(const uint8_t* k8, const uint8_t* vt8, const int* src_table, uint16_t* k_tiles, uint16_t* vt_tiles,
+                   const int* dst_table, int ntiles, int heads, int head_dim, void* stream) {
+  return vt_kv8_dequant_launch(k8, vt8, src_table, k_tiles, vt_tiles, dst_table, ntiles, heads, head_dim, S(stream));
+}
+int vt_attn_decode_kv8(const uint16_t* Q, int ldq, const uint8_t* k8, const uint8_t* vt8, const int* tile_table,
+                       const int* seq_desc, int nseq, uint16_t* O, int ldo, int heads, int head_dim, float scale,
+                       int max_kv_len, void* scratch, size_t scratch_bytes, void* stream) {
+  return vt_attn_decode_kv8_launch(Q, ldq, k8, vt8, tile_table, (const VtAttnSeq*)seq_desc, nseq, O, ldo, heads, head_dim, scale,
+                                   max_kv_len, (float*)scratch, scratch_bytes, S(stream));
+}
+int vt_attn_decode_fused_kv8(const uint16_t* qkv, int ldqkv, int q_col0, int k_col0, int v_col0, uint8_t* k8, uint8_t* vt8,
+                             const int* tile_table, const int* seq_desc, int nseq, uint16_t* O, int ldo, int heads, int head_dim,
+                             float scale, const float* rope_cos, const float* rope_sin, const int* positions, void* stream) {
+  return vt_attn_decode_fused_kv8_launch(qkv, ldqkv, q_col0, k_col0, v_col0, k8, vt8, tile_table, (const VtAttnSeq*)seq_desc, nseq, O,
+                                         ldo, heads, head_dim, scale, rope_cos, rope_sin, positions, S(stream));
+}
+
 int vt_kv_tiles(uint16_t* qkv, int ldqkv, int q_col0, int k_col0, int v_col0, uint16_t* k_tiles, uint16_t* vt_tiles,
                 const int* tile_table, const int* seq_desc, int nseq, int max_new_tiles, int heads, int head_dim,
                 const float* rope_cos, const float* rope_sin, const int* positions, void* stream) {
@@ -700,9 +722,13 @@ struct LlamaWs {
   uint8_t *y4, *yexp, *att4, *attexp, *h4, *hexp;
   // NF4 layers, launches of > 32 rows: one Linear's dequantised weights at a time (max(3H, 2I) x H op16), in front of the tile GEMMs
   bf16_t* wdq;
+  // fp8 KV cache, prefills: the 16-bit staging pool of ONE layer (n_stage_tiles K tiles + V^T tiles) and its identity tile table
+  bf16_t* stage_k;
+  uint16_t* stage_vt;
+  int* stage_table;
   size_t total;
 };
-LlamaWs llama_carve(const vt_llama_model* m, int rows, int n_logit, int nseq, int max_kv_len, void* p, size_t n) {
+LlamaWs llama_carve(const vt_llama_model* m, int rows, int n_logit, int nseq, int max_kv_len, void* p, size_t n, int n_stage_tiles = 0) {
   Carver ws(p, n);
   LlamaWs w;
   const int H = m->hidden, I = m->intermediate;
@@ -754,21 +780,25 @@ LlamaWs llama_carve(const vt_llama_model* m, int rows, int n_logit, int nseq, in
       w.gu32 = (float*)ws.take((size_t)rows * 2 * I * 4);
     }
   }
+  w.stage_k = nullptr;
+  w.stage_vt = nullptr;
+  w.stage_table = nullptr;
+  if (n_stage_tiles > 0 && rows > nseq) {   // (rows > nseq: some sequence brings more than one row, i.e. the pass may be a prefill)
+    const size_t tile = (size_t)m->heads * 64 * m->head_dim * 2;
+    w.stage_k = (bf16_t*)ws.take((size_t)n_stage_tiles * tile);
+    w.stage_vt = (uint16_t*)ws.take((size_t)n_stage_tiles * tile);
+    w.stage_table = (int*)ws.take((size_t)n_stage_tiles * 4);
+  }
   w.total = ws.off + 256;
   return w;
 }
-}  // namespace
-
-size_t vt_llama_workspace_bytes(const vt_llama_model* m, int rows, int n_logit_rows, int nseq, int max_kv_len) {
-  if (!m) return 0;
-  return llama_carve(m, rows, n_logit_rows, nseq, max_kv_len, nullptr, 0).total;
-}
-
-int vt_llama_forward(const vt_llama_model* m, const vt_kv_cache* kv, const uint16_t* x_embeds, int rows,
-                     const int* positions, const int* seq_desc, int nseq, int max_q_len, int max_new_tiles, int max_kv_len,
-                     const int* tile_table, const int* logit_rows, int n_logit_rows, float* logits,
-                     float* out_hidden, void* workspace, size_t workspace_bytes, void* stream) {
-  VT_REQUIRE(m && kv && x_embeds && positions && seq_desc && tile_table && workspace, "vt_llama_forward: null pointer");
+// The decoder pass behind vt_llama_forward (kv16) and vt_llama_forward_kv8 (kv8): exactly one of the two pools is given. The two differ
+// only in the "attend" step of a layer: decode steps run the fused kernel of the pool's format; prefills on an fp8 pool run the 16-bit
+// kernels on the workspace's staging pool between a dequantisation of the past tiles and a quantisation of the tiles with new rows.
+int llama_forward_body(const vt_llama_model* m, const vt_kv_cache* kv16, const vt_kv_cache8* kv8, int n_table_tiles, const uint16_t* x_embeds,
+                       int rows, const int* positions, const int* seq_desc, int nseq, int max_q_len, int max_new_tiles, int max_kv_len,
+                       const int* tile_table, const int* logit_rows, int n_logit_rows, float* logits, float* out_hidden, void* workspace,
+                       size_t workspace_bytes, void* stream) {
   VT_REQUIRE(rows > 0 && nseq > 0 && max_q_len > 0 && max_new_tiles > 0 && max_kv_len > 0, "vt_llama_forward: empty batch");
   VT_REQUIRE(m->head_dim == 128 || m->head_dim == 64, "vt_llama_forward: head_dim %d unsupported", m->head_dim);
   VT_REQUIRE(m->hidden == m->heads * m->head_dim, "vt_llama_forward: hidden != heads*head_dim");
@@ -776,7 +806,7 @@ int vt_llama_forward(const vt_llama_model* m, const vt_kv_cache* kv, const uint1
   VT_REQUIRE(m->rope_cos && m->rope_sin, "vt_llama_forward: rope tables missing");
   if (n_logit_rows > 0) VT_REQUIRE(logits && logit_rows, "vt_llama_forward: logits requested but pointer missing");
   hipStream_t s = S(stream);
-  LlamaWs w = llama_carve(m, rows, n_logit_rows, nseq, max_kv_len, workspace, workspace_bytes);
+  LlamaWs w = llama_carve(m, rows, n_logit_rows, nseq, max_kv_len, workspace, workspace_bytes, kv8 ? n_table_tiles : 0);
   if (w.total > workspace_bytes) {
     vt_set_error("vt_llama_forward: workspace too small (%zu < %zu)", workspace_bytes, w.total);
     return VT_ERR_WORKSPACE;
@@ -784,7 +814,14 @@ int vt_llama_forward(const vt_llama_model* m, const vt_kv_cache* kv, const uint1
   const int H = m->hidden, I = m->intermediate, heads = m->heads, HD = m->head_dim;
   const int AUTO = VT_GEMM_CFG_AUTO;
   const float scale = 1.0f / sqrtf((float)HD);
-  const size_t layer_stride = (size_t)kv->num_pages * heads * 64 * HD;
+  const size_t layer_stride = (size_t)(kv8 ? kv8->num_pages : kv16->num_pages) * heads * 64 * HD;
+  if (kv8 && max_q_len > 1) {   // prefill on an fp8 pool: the staging pool and its identity table (slot = table_off + t)
+    VT_REQUIRE(w.stage_k && w.stage_vt && w.stage_table, "vt_llama_forward_kv8: the workspace carries no staging pool (rows %d, nseq %d)", rows, nseq);
+    VT_TRY(vt_kv8_iota_launch(w.stage_table, n_table_tiles, s));
+  }
+  // no sequence has a past when every sequence brings max_q_len rows and none holds more keys than that (sufficient, host-side: seq_desc
+  // lives on the device); the dequantisation launch is skipped then
+  const bool kv8_no_past = (long)nseq * max_q_len == (long)rows && max_kv_len == max_q_len;
 
   VT_TRY(vt_bf16_to_f32_launch(x_embeds, w.x, (size_t)rows * H, s));
   if (m->embeds_lo) VT_TRY(vt_add_op_to_f32_launch(w.x, m->embeds_lo, (size_t)rows * H, s));   // the input embeddings as a pair (precise level 2)
@@ -838,8 +875,33 @@ int vt_llama_forward(const vt_llama_model* m, const vt_kv_cache* kv, const uint1
     const vt_llama_layer& L = m->layers[l];
     if (m->hidden_trace)
       VT_HIP(hipMemcpyAsync(m->hidden_trace + (size_t)l * rows * H, w.x, (size_t)rows * H * 4, hipMemcpyDeviceToDevice, s));
-    bf16_t* kt = kv->k + l * layer_stride;
-    bf16_t* vt = kv->vt + l * layer_stride;
+    // fp8 pool: kt / vt are the staging pool (prefills only; decode steps read k8 / vt8)
+    bf16_t* kt = kv8 ? w.stage_k : kv16->k + l * layer_stride;
+    bf16_t* vt = kv8 ? w.stage_vt : kv16->vt + l * layer_stride;
+    uint8_t* k8 = kv8 ? kv8->k + l * layer_stride : nullptr;
+    uint8_t* vt8 = kv8 ? kv8->vt + l * layer_stride : nullptr;
+    // the "attend" step of a decode pass: rotary + append + attention + combine in one launch, on the pool's format
+    auto attend_decode = [&]() -> int {
+      if (kv8)
+        return vt_attn_decode_fused_kv8_launch(w.qkv, 3 * H, 0, H, 2 * H, k8, vt8, tile_table, (const VtAttnSeq*)seq_desc, nseq, w.att, H,
+                                               heads, HD, scale, m->rope_cos, m->rope_sin, positions, s);
+      return vt_attn_decode_fused_launch(w.qkv, 3 * H, 0, H, 2 * H, kt, vt, tile_table, (const VtAttnSeq*)seq_desc, nseq, w.att, H,
+                                         heads, HD, scale, m->rope_cos, m->rope_sin, positions, s);
+    };
+    // ... and of a standard-mode prefill: vt_kv_tiles (unless the QKV epilogue wrote the pages) + the prefill attention; on an fp8 pool
+    // the same two launches run on the staging pool, between the dequantisation of the past and the quantisation of the new tiles
+    auto attend_prefill = [&](bool tiles) -> int {
+      const int* tt = kv8 ? w.stage_table : tile_table;
+      if (kv8 && !kv8_no_past)
+        VT_TRY(vt_kv8_dequant_past_launch(k8, vt8, kt, vt, tile_table, (const VtAttnSeq*)seq_desc, nseq, max_kv_len, heads, HD, s));
+      if (tiles)
+        VT_TRY(vt_kv_tiles_launch(w.qkv, 3 * H, 0, H, 2 * H, kt, vt, tt, (const VtAttnSeq*)seq_desc, nseq,
+                                  max_new_tiles, heads, HD, m->rope_cos, m->rope_sin, positions, s));
+      VT_TRY(vt_flash_attn_launch(w.qkv, 3 * H, kt, vt, tt, (const VtAttnSeq*)seq_desc, nseq, max_q_len, w.att, H,
+                                  heads, HD, 1, scale, s));
+      if (kv8) VT_TRY(vt_kv8_quant_new_launch(kt, vt, k8, vt8, tile_table, (const VtAttnSeq*)seq_desc, nseq, max_new_tiles, heads, HD, s));
+      return VT_OK;
+    };
     const bool nf4 = L.wqkv_nf4 != nullptr;
     // one decoder Linear of <= 32 rows: the 16-bit weight-streaming kernel, or its NF4 counterpart on an NF4 layer (same norm folding)
     auto skinny = [&](const bf16_t* A, int lda, const bf16_t* W16, const uint8_t* W4, const float* absmax, void* C, int ldc, int N, int K, int epi,
@@ -854,8 +916,7 @@ int vt_llama_forward(const vt_llama_model* m, const vt_kv_cache* kv, const uint1
       } else {
         VT_TRY(skinny(w.y, H, L.wqkv, L.wqkv_nf4, L.wqkv_absmax, w.qkv, 3 * H, 3 * H, H, VT_EPI_BF16, consume_a));
       }
-      VT_TRY(vt_attn_decode_fused_launch(w.qkv, 3 * H, 0, H, 2 * H, kt, vt, tile_table, (const VtAttnSeq*)seq_desc, nseq, w.att, H,
-                                         heads, HD, scale, m->rope_cos, m->rope_sin, positions, s));
+      VT_TRY(attend_decode());
       VtGemmNormFuse prod_b;   // x += att Wo^T ; y = bf16(x .* rms2) ; partial sums -> rs_b
       prod_b.out_w = L.rms2;
       prod_b.out_xw = w.y;
@@ -879,13 +940,9 @@ int vt_llama_forward(const vt_llama_model* m, const vt_kv_cache* kv, const uint1
       VT_TRY(vt_rmsnorm_launch(w.x, nullptr, L.rms1, w.y, rows, H, m->rms_eps, s));
       VT_TRY(skinny(w.y, H, nullptr, L.wqkv_nf4, L.wqkv_absmax, w.qkv, 3 * H, 3 * H, H, VT_EPI_BF16, none));
       if (max_q_len == 1) {
-        VT_TRY(vt_attn_decode_fused_launch(w.qkv, 3 * H, 0, H, 2 * H, kt, vt, tile_table, (const VtAttnSeq*)seq_desc, nseq, w.att, H,
-                                           heads, HD, scale, m->rope_cos, m->rope_sin, positions, s));
+        VT_TRY(attend_decode());
       } else {
-        VT_TRY(vt_kv_tiles_launch(w.qkv, 3 * H, 0, H, 2 * H, kt, vt, tile_table, (const VtAttnSeq*)seq_desc, nseq,
-                                  max_new_tiles, heads, HD, m->rope_cos, m->rope_sin, positions, s));
-        VT_TRY(vt_flash_attn_launch(w.qkv, 3 * H, kt, vt, tile_table, (const VtAttnSeq*)seq_desc, nseq, max_q_len, w.att, H,
-                                    heads, HD, 1, scale, s));
+        VT_TRY(attend_prefill(true));
       }
       VT_TRY(skinny(w.att, H, nullptr, L.wo_nf4, L.wo_absmax, w.x, H, H, H, VT_EPI_F32_RESID, none));
       VT_TRY(vt_rmsnorm_launch(w.x, nullptr, L.rms2, w.y, rows, H, m->rms_eps, s));
@@ -979,14 +1036,9 @@ int vt_llama_forward(const vt_llama_model* m, const vt_kv_cache* kv, const uint1
       VT_TRY(vt_gemm_launch(w.y, H, Wqkv, H, w.qkv, 3 * H, nullptr, rows, 3 * H, H, VT_EPI_BF16, AUTO, s));
     }
     if (max_q_len == 1) {   // decode step: rotary + append + attention + combine in one launch
-      VT_TRY(vt_attn_decode_fused_launch(w.qkv, 3 * H, 0, H, 2 * H, kt, vt, tile_table, (const VtAttnSeq*)seq_desc, nseq, w.att, H,
-                                         heads, HD, scale, m->rope_cos, m->rope_sin, positions, s));
+      VT_TRY(attend_decode());
     } else {
-      if (!fuse_qkv)
-        VT_TRY(vt_kv_tiles_launch(w.qkv, 3 * H, 0, H, 2 * H, kt, vt, tile_table, (const VtAttnSeq*)seq_desc, nseq,
-                                  max_new_tiles, heads, HD, m->rope_cos, m->rope_sin, positions, s));
-      VT_TRY(vt_flash_attn_launch(w.qkv, 3 * H, kt, vt, tile_table, (const VtAttnSeq*)seq_desc, nseq, max_q_len, w.att, H,
-                                  heads, HD, 1, scale, s));
+      VT_TRY(attend_prefill(!fuse_qkv));
     }
     if (fold_tile) {
       VtGemmNormFuse prod;
@@ -1029,6 +1081,41 @@ int vt_llama_forward(const vt_llama_model* m, const vt_kv_cache* kv, const uint1
     VT_TRY(vt_gemm_launch(w.yn, H, m->lm_head, H, logits, m->vocab, nullptr, n_logit_rows, m->vocab, H, VT_EPI_F32, AUTO, s));
   }
   return VT_OK;
+}
+
+}  // namespace
+
+size_t vt_llama_workspace_bytes(const vt_llama_model* m, int rows, int n_logit_rows, int nseq, int max_kv_len) {
+  if (!m) return 0;
+  return llama_carve(m, rows, n_logit_rows, nseq, max_kv_len, nullptr, 0).total;
+}
+
+int vt_llama_forward(const vt_llama_model* m, const vt_kv_cache* kv, const uint16_t* x_embeds, int rows,
+                     const int* positions, const int* seq_desc, int nseq, int max_q_len, int max_new_tiles, int max_kv_len,
+                     const int* tile_table, const int* logit_rows, int n_logit_rows, float* logits,
+                     float* out_hidden, void* workspace, size_t workspace_bytes, void* stream) {
+  VT_REQUIRE(m && kv && x_embeds && positions && seq_desc && tile_table && workspace, "vt_llama_forward: null pointer");
+  return llama_forward_body(m, kv, nullptr, 0, x_embeds, rows, positions, seq_desc, nseq, max_q_len, max_new_tiles, max_kv_len, tile_table,
+                            logit_rows, n_logit_rows, logits, out_hidden, workspace, workspace_bytes, stream);
+}
+
+size_t vt_llama_workspace_bytes_kv8(const vt_llama_model* m, int rows, int n_logit_rows, int nseq, int max_kv_len, int n_table_tiles) {
+  if (!m || n_table_tiles <= 0) return 0;
+  return llama_carve(m, rows, n_logit_rows, nseq, max_kv_len, nullptr, 0, n_table_tiles).total;
+}
+
+int vt_llama_forward_kv8(const vt_llama_model* m, const vt_kv_cache8* kv, const uint16_t* x_embeds, int rows,
+                         const int* positions, const int* seq_desc, int nseq, int max_q_len, int max_new_tiles, int max_kv_len,
+                         const int* tile_table, int n_table_tiles, const int* logit_rows, int n_logit_rows, float* logits,
+                         float* out_hidden, void* workspace, size_t workspace_bytes, void* stream) {
+  VT_REQUIRE(m && kv && x_embeds && positions && seq_desc && tile_table && workspace, "vt_llama_forward_kv8: null pointer");
+  VT_REQUIRE(kv->k && kv->vt, "vt_llama_forward_kv8: null pointer (pages)");
+  VT_REQUIRE(n_table_tiles > 0, "vt_llama_forward_kv8: n_table_tiles must be the number of entries of tile_table");
+  // an error, never a silent 16-bit pass: these modes write or read 16-bit pages directly
+  VT_REQUIRE(m->precise_qk == 0, "vt_llama_forward_kv8: precise level %d cannot run on an fp8 KV cache", m->precise_qk);
+  VT_REQUIRE(m->qkv_fuse == 0, "vt_llama_forward_kv8: qkv_fuse cannot run on an fp8 KV cache (its epilogue writes 16-bit pages)");
+  return llama_forward_body(m, nullptr, kv, n_table_tiles, x_embeds, rows, positions, seq_desc, nseq, max_q_len, max_new_tiles, max_kv_len,
+                            tile_table, logit_rows, n_logit_rows, logits, out_hidden, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

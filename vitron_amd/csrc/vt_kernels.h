@@ -183,6 +183,26 @@ int vt_attn_temporal_launch(const bf16_t* qkv, bf16_t* out, int B, int T, int N,
 // precise level 2 of the towers: the temporal attention on fp32 q | k | v rows (row stride ld), output as an operand pair
 int vt_attn_temporal_f32_launch(const float* qkv, int ld, bf16_t* out, bf16_t* out_lo, int B, int T, int N, int heads, hipStream_t s);
 
+// ---- vt_kv8.hip: the FP8 (e4m3fn) paged KV cache (format in include/vitron_hip.h) -------------------------------------
+// whole tiles, 16-bit tile src_table[i] <-> fp8 page dst_table[i], K and V^T in one launch
+int vt_kv8_quant_launch(const bf16_t* Kt, const uint16_t* Vt, const int* src_table, uint8_t* K8, uint8_t* V8, const int* dst_table,
+                        int ntiles, int heads, int HD, hipStream_t s);
+int vt_kv8_dequant_launch(const uint8_t* K8, const uint8_t* V8, const int* src_table, bf16_t* Kt, uint16_t* Vt, const int* dst_table,
+                          int ntiles, int heads, int HD, hipStream_t s);
+// the same between the pages and a staging pool whose tile table is the identity (slot = table_off + t), tiles derived on the device:
+// quant_new covers tiles [past / 64, ntiles) of every sequence, dequant_past tiles [0, ceil(past / 64)) of sequences with a past
+int vt_kv8_quant_new_launch(const bf16_t* Kt, const uint16_t* Vt, uint8_t* K8, uint8_t* V8, const int* tile_table, const VtAttnSeq* seqs,
+                            int nseq, int max_new_tiles, int heads, int HD, hipStream_t s);
+int vt_kv8_dequant_past_launch(const uint8_t* K8, const uint8_t* V8, bf16_t* Kt, uint16_t* Vt, const int* tile_table,
+                               const VtAttnSeq* seqs, int nseq, int max_kv_len, int heads, int HD, hipStream_t s);
+int vt_kv8_iota_launch(int* table, int n, hipStream_t s);   // table[i] = i: the staging pool's tile table
+int vt_attn_decode_kv8_launch(const bf16_t* Q, int ldq, const uint8_t* K8, const uint8_t* V8, const int* tile_table, const VtAttnSeq* seqs,
+                              int nseq, bf16_t* O, int ldo, int heads, int HD, float scale, int max_kv_len, float* scratch,
+                              size_t scratch_bytes, hipStream_t s);
+int vt_attn_decode_fused_kv8_launch(const bf16_t* qkv, int ldqkv, int q_col0, int k_col0, int v_col0, uint8_t* K8, uint8_t* V8,
+                                    const int* tile_table, const VtAttnSeq* seqs, int nseq, bf16_t* O, int ldo, int heads, int HD,
+                                    float scale, const float* rope_cos, const float* rope_sin, const int* positions, hipStream_t s);
+
 // ---- vt_region.hip --------------------------------------------------------------------------------
 // cell mask / count / masked mean per (box, 64-channel slab); optionally also LocationEncoder layer 0:
 // loc_out[b][n] = op16(relu(coords[b][0..4) . loc_w0[n][0..4) + loc_b0[n])), n < loc_n; coords fp32 [B][4]

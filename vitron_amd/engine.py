@@ -531,6 +531,8 @@ class PackedLlama:
     def set_qkv_fuse(self, on: bool) -> None:
         """Prefill: rotary + K / V^T page writes inside the QKV GEMM's epilogue instead of the separate vt_kv_tiles pass
         (vt_llama_model.qkv_fuse; bit-identical, measured slower at the benchmark shape: default off)."""
+        if on and getattr(self, "kv_dtype", "16bit") == "fp8":
+            raise _lib.VitronHipError("qkv_fuse cannot run on an fp8 KV cache: its epilogue writes 16-bit pages (select kv_cache_dtype '16bit' first)")
         self.model.qkv_fuse = int(bool(on))
 
     def set_precise(self, level: int) -> None:
@@ -541,6 +543,9 @@ class PackedLlama:
         level = int(level)
         if level not in (0, 1, 2, 3):
             raise _lib.VitronHipError(f"precise level must be 0, 1, 2 or 3, got {level}")
+        if level and getattr(self, "kv_dtype", "16bit") == "fp8":
+            raise _lib.VitronHipError(f"precise level {level} cannot run on an fp8 KV cache: its kernels read 16-bit operand pairs from the pages "
+                                      "(select kv_cache_dtype '16bit' first)")
         if level and self.weight_format == "nf4":
             raise _lib.VitronHipError(f"precise level {level} cannot run on NF4 (load_4bit) weights: its products need the 16-bit matrices")
         if level and self.hd != 128:
@@ -574,6 +579,8 @@ class PackedLlama:
             raise _lib.VitronHipError(f"precise_qk needs head_dim 128 (got {self.hd})")
         if on and self.weight_format == "nf4":
             raise _lib.VitronHipError("precise_qk cannot run on NF4 (load_4bit) weights")
+        if on and getattr(self, "kv_dtype", "16bit") == "fp8":
+            raise _lib.VitronHipError("precise_qk cannot run on an fp8 KV cache (select kv_cache_dtype '16bit' first)")
         self.model.precise_qk = int(bool(on))
 
     def set_prefill_norm_fold(self, on: bool) -> None:
@@ -581,20 +588,46 @@ class PackedLlama:
         self.model.prefill_norm_fold = int(bool(on))
 
 
+def parse_kv_cache_dtype(x) -> str:
+    """config.kv_cache_dtype -> '16bit' | 'fp8'. None / 'auto' / '16bit': the 16-bit pool; 'fp8' / 'fp8_e4m3': the e4m3 pool; anything else
+    is a ValueError."""
+    if x is None:
+        return "16bit"
+    if isinstance(x, str) and x.lower() in ("auto", "16bit"):
+        return "16bit"
+    if isinstance(x, str) and x.lower() in ("fp8", "fp8_e4m3"):
+        return "fp8"
+    raise ValueError(f"kv_cache_dtype must be None, 'auto', '16bit', 'fp8' or 'fp8_e4m3', got {x!r}")
+
+
 class PagedKVCache:
     """Paged KV pool: K pages [L][pages][heads][64][hd] in the operand dtype, V^T pages [L][pages][heads][hd][64] fp16; 64 tokens per page.
+    kv_dtype="fp8": the same layouts with one e4m3fn byte per element (include/vitron_hip.h "FP8 KV CACHE"), half the bytes per token.
     A free list hands out pages; sequences own a list of page ids (their block table)."""
 
-    def __init__(self, llama: PackedLlama, num_pages: int):
+    def __init__(self, llama: PackedLlama, num_pages: int, kv_dtype: str = "16bit"):
         self.llama = llama
         self.num_pages = int(num_pages)
+        self.kv_dtype = parse_kv_cache_dtype(kv_dtype)
         n = llama.L * self.num_pages * llama.heads * PAGE_TOKENS * llama.hd
-        self.k = torch.zeros(n, dtype=llama.dtype, device=llama.device)
-        self.vt = torch.zeros(n, dtype=torch.float16, device=llama.device)    # V^T pages hold fp16 (include/vitron_hip.h)
+        if self.kv_dtype == "fp8":
+            if llama.model.precise_qk or llama.model.qkv_fuse:
+                raise _lib.VitronHipError("PagedKVCache(kv_dtype='fp8'): the decoder is in a precise / qkv_fuse mode, which reads or writes 16-bit "
+                                          "pages (set_precise(0) / set_qkv_fuse(False) first)")
+            self.k = torch.zeros(n, dtype=torch.uint8, device=llama.device)
+            self.vt = torch.zeros(n, dtype=torch.uint8, device=llama.device)
+            c = _lib.VtKvCache8()
+        else:
+            self.k = torch.zeros(n, dtype=llama.dtype, device=llama.device)
+            self.vt = torch.zeros(n, dtype=torch.float16, device=llama.device)    # V^T pages hold fp16 (include/vitron_hip.h)
+            c = _lib.VtKvCache()
         self.free = list(range(self.num_pages - 1, -1, -1))
-        c = _lib.VtKvCache()
         c.k, c.vt, c.num_pages = self.k.data_ptr(), self.vt.data_ptr(), self.num_pages
         self.struct = c
+
+    def bytes_per_token(self) -> int:
+        """Pool bytes one cached token occupies (K row + V column of every head and layer)."""
+        return 2 * self.llama.L * self.llama.heads * self.llama.hd * self.k.element_size()
 
     def alloc(self, n: int) -> List[int]:
         if n > len(self.free):
@@ -665,7 +698,10 @@ def llama_forward(llama: PackedLlama, kv: PagedKVCache, seqs: Sequence[SequenceS
     hidden = torch.empty((rows, llama.H), dtype=torch.float32, device=dev) if (return_hidden or return_all_hidden) else None
     trace = torch.empty((llama.L, rows, llama.H), dtype=torch.float32, device=dev) if return_all_hidden else None
     max_kv = max(d[2] for d in desc)
-    ws = llama.ws.get(lib.vt_llama_workspace_bytes(C.byref(llama.model), rows, n_logit, len(desc), max_kv))
+    if getattr(kv, "kv_dtype", "16bit") == "fp8":
+        ws = llama.ws.get(lib.vt_llama_workspace_bytes_kv8(C.byref(llama.model), rows, n_logit, len(desc), max_kv, len(table)))
+    else:
+        ws = llama.ws.get(lib.vt_llama_workspace_bytes(C.byref(llama.model), rows, n_logit, len(desc), max_kv))
     # the per-call pointers travel in a COPY of the model struct (two threads / streams sharing one PackedLlama must not see each
     # other's trace or lo buffer; the C call reads the struct and keeps nothing)
     call_model = _lib.VtLlamaModel.from_buffer_copy(llama.model)
@@ -685,6 +721,14 @@ def llama_forward(llama: PackedLlama, kv: PagedKVCache, seqs: Sequence[SequenceS
 
 
 def _llama_call(lib, model_struct, kv, embeds, rows, pos_t, desc_t, nseq, max_q, max_new_tiles, max_kv, table_t, lr_t, n_logit, logits, hidden, ws):
+    if getattr(kv, "kv_dtype", "16bit") == "fp8":     # the pool's format picks the entry point; it also takes the table's length
+        _lib.check(lib.vt_llama_forward_kv8(C.byref(model_struct), C.byref(kv.struct), embeds.data_ptr(), rows, pos_t.data_ptr(),
+                                            desc_t.data_ptr(), nseq, max_q, max_new_tiles, max_kv, table_t.data_ptr(), int(table_t.numel()),
+                                            None if lr_t is None else lr_t.data_ptr(), n_logit,
+                                            None if logits is None else logits.data_ptr(),
+                                            None if hidden is None else hidden.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+                   "vt_llama_forward_kv8", lib)
+        return
     _lib.check(lib.vt_llama_forward(C.byref(model_struct), C.byref(kv.struct), embeds.data_ptr(), rows, pos_t.data_ptr(),
                                     desc_t.data_ptr(), nseq, max_q, max_new_tiles, max_kv, table_t.data_ptr(),
                                     None if lr_t is None else lr_t.data_ptr(), n_logit,
@@ -710,6 +754,8 @@ def padded_batch_fixup(llama: PackedLlama, kv: PagedKVCache, seqs: Sequence[Sequ
         them) and the ordinary decode kernels run on it: position = compacted length + step, exactly the reference's.
 
     seqs: the sequences after the packed prefill (length = valid spliced rows). Returns {"pad_logits": {b: fp32 [V]}, "holes": {b: n}}."""
+    if getattr(kv, "kv_dtype", "16bit") == "fp8":
+        raise _lib.VitronHipError("padded_batch_fixup edits views of 16-bit pages and cannot run on an fp8 KV cache")
     from . import ops
     dev, H, heads, hd, dt = llama.device, llama.H, llama.heads, llama.hd, llama.dtype
     B = len(seqs)
@@ -851,11 +897,19 @@ class DecodeState:
             if s.length + 1 > len(s.pages) * PAGE_TOKENS:
                 raise _lib.VitronHipError("DecodeState.forward: more steps than pages were reserved for")
         logits = torch.empty((B, llama.V_pad), dtype=torch.float32, device=llama.device)
-        ws = llama.ws.get(lib.vt_llama_workspace_bytes(C.byref(llama.model), B, B, B, self.max_len))
-        _lib.check(lib.vt_llama_forward(C.byref(llama.model), C.byref(self.kv.struct), self.x.data_ptr(), B, self.pos.data_ptr(),
-                                        self.desc.data_ptr(), B, 1, 1, int(self.max_len), self.table.data_ptr(),
-                                        self.rows.data_ptr(), B, logits.data_ptr(), None, ws.data_ptr(), ws.numel(), _stream()),
-                   "vt_llama_forward", lib)
+        if getattr(self.kv, "kv_dtype", "16bit") == "fp8":
+            nt = int(self.table.numel())
+            ws = llama.ws.get(lib.vt_llama_workspace_bytes_kv8(C.byref(llama.model), B, B, B, self.max_len, nt))
+            _lib.check(lib.vt_llama_forward_kv8(C.byref(llama.model), C.byref(self.kv.struct), self.x.data_ptr(), B, self.pos.data_ptr(),
+                                                self.desc.data_ptr(), B, 1, 1, int(self.max_len), self.table.data_ptr(), nt,
+                                                self.rows.data_ptr(), B, logits.data_ptr(), None, ws.data_ptr(), ws.numel(), _stream()),
+                       "vt_llama_forward_kv8", lib)
+        else:
+            ws = llama.ws.get(lib.vt_llama_workspace_bytes(C.byref(llama.model), B, B, B, self.max_len))
+            _lib.check(lib.vt_llama_forward(C.byref(llama.model), C.byref(self.kv.struct), self.x.data_ptr(), B, self.pos.data_ptr(),
+                                            self.desc.data_ptr(), B, 1, 1, int(self.max_len), self.table.data_ptr(),
+                                            self.rows.data_ptr(), B, logits.data_ptr(), None, ws.data_ptr(), ws.numel(), _stream()),
+                       "vt_llama_forward", lib)
         for s in self.seqs:
             s.length += 1
         self.passes += 1

@@ -100,11 +100,17 @@ def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, l
     if torch.device(device).type != "cuda":
         raise RuntimeError("vitron_amd runs on the GPU only (device must be 'cuda'); there is no CPU path")
     synthetic = kwargs.pop("synthetic", None)
+    # kv_cache_dtype: None / "auto" / "16bit" (default) or "fp8" / "fp8_e4m3" -- the paged KV pool's format; unknown values raise
+    kv_cache_dtype = kwargs.pop("kv_cache_dtype", None)
+    from ..engine import parse_kv_cache_dtype
+    parse_kv_cache_dtype(kv_cache_dtype)
     tokenizer = kwargs.pop("tokenizer", None)
     torch_dtype = kwargs.pop("torch_dtype", None)
     if model_path == "synthetic" or synthetic is not None:
         spec = synthetic or {}
         cfg = LlavaConfig(**spec.get("llm", {}), mm_hidden_size=spec.get("image", spec.get("video", {})).get("hidden_size", 1024))
+        if kv_cache_dtype is not None:
+            cfg.kv_cache_dtype = kv_cache_dtype
         model = LlavaLlamaForCausalLM(cfg)
         model.weight_format = weight_format
         model.init_synthetic(device, seed=spec.get("seed", 1234), vit_image=spec.get("image"), vit_video=spec.get("video"),
@@ -115,6 +121,8 @@ def load_pretrained_model(model_path, model_base, model_name, load_8bit=False, l
 
     with open(os.path.join(model_path, "config.json")) as f:
         cfg = LlavaConfig(**json.load(f))
+    if kv_cache_dtype is not None:
+        cfg.kv_cache_dtype = kv_cache_dtype
     if "lora" in model_name.lower() and model_base is None:
         raise ValueError("LoRA checkpoints need `model_base` (reference builder.py:51-52)")
     if tokenizer is None:

@@ -14,7 +14,7 @@ from typing import List, Optional
 import torch
 
 from ... import _lib, ops, synth
-from ...engine import DecodeState, PackedLlama, PagedKVCache, SequenceState, llama_forward, pair_lo
+from ...engine import DecodeState, PackedLlama, PagedKVCache, SequenceState, llama_forward, pair_lo, parse_kv_cache_dtype
 from ..llava_arch import LlavaMetaForCausalLM, LlavaMetaModel
 from ..multimodal_encoder.builder import build_image_tower, build_video_tower
 from ..multimodal_projector.builder import build_vision_projector
@@ -122,6 +122,9 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         self.weight_format = "16bit"
         self.kv: Optional[PagedKVCache] = None
         self.kv_pages = getattr(config, "kv_pages", None)
+        # "16bit" (default) or "fp8": the format of the paged KV pool (config.kv_cache_dtype; engine.PagedKVCache). An opt-in
+        # capacity / throughput mode like load_4bit; anything unknown is a ValueError here, at construction
+        self.kv_cache_dtype = parse_kv_cache_dtype(getattr(config, "kv_cache_dtype", None))
         # multi-turn reuse (vitron_amd/prefix_cache.py): generate() keeps the last conversation's KV pages and the encoded
         # images; config.kv_prefix_reuse / config.vis_cache_entries switch them off (benchmarks do)
         self._prefix = None
@@ -268,6 +271,9 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         GEMM work, and the fp16 build's full-depth logits end below north_star's 1e-3 of the reference's fp32 output (DESIGN.md 4,
         tests/test_gpu_parity_fulldepth.py). Needs the weights on the GPU (call after .to(device)); decode steps are unchanged."""
         level = int(level)
+        if level and "fp8" in (self.kv_cache_dtype, parse_kv_cache_dtype(getattr(self.config, "kv_cache_dtype", None))):
+            raise RuntimeError(f"set_precise({level}): the precise modes cannot run on the fp8 KV cache (their kernels keep 16-bit operand pairs in "
+                               "the pages); call set_kv_cache_dtype('16bit') first")
         llama = self.model.llama
         if llama is None:
             raise RuntimeError("set_precise: move the model to the GPU first (.to(device))")
@@ -279,6 +285,42 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         return self
 
     # ---- KV pool ----------------------------------------------------------------------------------------------
+    def set_kv_cache_dtype(self, kv_cache_dtype):
+        """Format of the paged KV pool: None / 'auto' / '16bit' (default), or 'fp8' / 'fp8_e4m3' -- unscaled OCP e4m3 pages, half the bytes
+        per cached token and per decode step's attention (costs e4m3's 3 mantissa bits on K and V). Drops the kept
+        conversation and the pool (the next call builds one in the new format); refused while pages are live, and together with the
+        precise modes / qkv_fuse, which read or write 16-bit pages."""
+        fmt = parse_kv_cache_dtype(kv_cache_dtype)
+        llama = self.model.llama
+        if fmt == "fp8":
+            if int(getattr(self, "precise_level", 0)) or (llama is not None and llama.model.precise_qk):
+                raise RuntimeError("set_kv_cache_dtype('fp8'): a precise mode is on, and its kernels keep 16-bit operand pairs in the pages; "
+                                   "call set_precise(0) first")
+            if llama is not None and llama.model.qkv_fuse:
+                raise RuntimeError("set_kv_cache_dtype('fp8'): qkv_fuse is on, and its epilogue writes 16-bit pages; call set_qkv_fuse(False) first")
+        self.reset_prefix_cache()
+        if self.kv is not None and len(self.kv.free) != self.kv.num_pages:
+            raise RuntimeError("set_kv_cache_dtype: KV pages are live; release past_key_values / finish the served requests first")
+        self.kv = None
+        self.kv_cache_dtype = fmt
+        self.config.kv_cache_dtype = None if fmt == "16bit" else fmt
+        if llama is not None:
+            llama.kv_dtype = fmt
+        return self
+
+    def _kv_format(self) -> str:
+        """The pool format in force: config.kv_cache_dtype when the caller changed it after construction, else the parsed value."""
+        fmt = parse_kv_cache_dtype(getattr(self.config, "kv_cache_dtype", None))
+        if fmt != self.kv_cache_dtype:
+            self.set_kv_cache_dtype(fmt)
+        if self.model.llama is not None:
+            self.model.llama.kv_dtype = fmt
+        return fmt
+
+    def new_kv_pool(self, num_pages: int) -> PagedKVCache:
+        """A pool of `num_pages` pages in the model's KV format (generate()'s own pool and ServingEngine(kv_pages=...) use this)."""
+        return PagedKVCache(self.model.llama, int(num_pages), kv_dtype=self._kv_format())
+
     def reset_prefix_cache(self):
         """Drop the kept conversation (KV pages go back to the pool) and the encoded-image cache."""
         if self._prefix is not None and self.kv is not None:
@@ -288,6 +330,8 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
             self._vis_cache.clear()
 
     def _ensure_kv(self, pages_needed: int):
+        if self.kv is not None and self.kv.kv_dtype != self._kv_format():
+            raise RuntimeError(f"the KV pool holds {self.kv.kv_dtype} pages but kv_cache_dtype is {self.kv_cache_dtype!r}: use set_kv_cache_dtype()")
         if self.kv is not None and len(self.kv.free) >= pages_needed:
             return
         if self._prefix is not None:            # the kept conversation is the first thing to go when pages run short
@@ -300,7 +344,7 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
             raise RuntimeError("KV pool exhausted while sequences are live; release past_key_values or raise config.kv_pages")
         n = max(pages_needed, int(self.kv_pages or 0))
         self.kv = None
-        self.kv = PagedKVCache(self.model.llama, n)
+        self.kv = self.new_kv_pool(n)
 
     # ---- reference llava_llama.py:57-102 ----------------------------------------------------------------------
     @torch.no_grad()
@@ -421,6 +465,9 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         and every sample gets the ids the reference returns for it ALONE."""
         if num_beams != 1:
             raise NotImplementedError("beam search is not implemented (the reference entry points sample or go greedy)")
+        if padded_batch and parse_kv_cache_dtype(getattr(self.config, "kv_cache_dtype", None)) == "fp8":
+            raise NotImplementedError("generate(padded_batch=True) cannot run on the fp8 KV cache: its fix-up edits views of the 16-bit pages "
+                                      "(engine.padded_batch_fixup); call set_kv_cache_dtype('16bit') first")
         dev = self.device
         input_ids = input_ids.to(dev)
         B = input_ids.shape[0]

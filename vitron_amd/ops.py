@@ -199,6 +199,85 @@ def attn_decode_fused(qkv: torch.Tensor, q_col0: int, k_col0: int, v_col0: int, 
     return out
 
 
+def _pages8(t: torch.Tensor, name: str):
+    """fp8 (e4m3fn) pages travel as one byte per element: uint8 or torch.float8_e4m3fn storage."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.VitronHipError(f"{name}: expected a CUDA/HIP tensor (vitron_amd has no CPU path)")
+    if t.element_size() != 1 or not t.is_contiguous():
+        raise _lib.VitronHipError(f"{name}: expected contiguous 1-byte elements (e4m3 pages), got {t.dtype}")
+
+
+def kv8_quant(k_tiles: torch.Tensor, vt_tiles: torch.Tensor, src_table: torch.Tensor, k8: torch.Tensor, vt8: torch.Tensor,
+              dst_table: torch.Tensor, heads: int, head_dim: int) -> None:
+    """Whole tiles: 16-bit tile src_table[i] of (k_tiles operand dtype, vt_tiles fp16 bits) -> e4m3 page dst_table[i] of (k8, vt8)."""
+    lib, dt = _op16(k_tiles, "kv8_quant.k_tiles")
+    _chk(k_tiles, dt, "kv8_quant.k_tiles")
+    if vt_tiles.element_size() != 2 or not vt_tiles.is_contiguous():
+        raise _lib.VitronHipError("kv8_quant.vt_tiles: expected a contiguous 16-bit tensor (the V^T pages hold fp16 bits)")
+    _pages8(k8, "kv8_quant.k8")
+    _pages8(vt8, "kv8_quant.vt8")
+    _chk(src_table, torch.int32, "kv8_quant.src_table")
+    _chk(dst_table, torch.int32, "kv8_quant.dst_table")
+    if src_table.numel() != dst_table.numel():
+        raise _lib.VitronHipError("kv8_quant: src_table and dst_table differ in length")
+    tile = heads * PAGE_TOKENS * head_dim
+    if src_table.numel() and (int(src_table.max()) + 1) * tile > k_tiles.numel() or src_table.numel() and (int(dst_table.max()) + 1) * tile > k8.numel():
+        raise _lib.VitronHipError("kv8_quant: a table entry points past its pool")
+    _lib.check(lib.vt_kv8_quant(_p(k_tiles), _p(vt_tiles), _p(src_table), _p(k8), _p(vt8), _p(dst_table), src_table.numel(), heads,
+                                head_dim, _stream()), "vt_kv8_quant", lib)
+
+
+def kv8_dequant(k8: torch.Tensor, vt8: torch.Tensor, src_table: torch.Tensor, k_tiles: torch.Tensor, vt_tiles: torch.Tensor,
+                dst_table: torch.Tensor, heads: int, head_dim: int) -> None:
+    """The inverse of kv8_quant (exact): e4m3 page src_table[i] -> 16-bit tile dst_table[i]."""
+    lib, dt = _op16(k_tiles, "kv8_dequant.k_tiles")
+    _chk(k_tiles, dt, "kv8_dequant.k_tiles")
+    if vt_tiles.element_size() != 2 or not vt_tiles.is_contiguous():
+        raise _lib.VitronHipError("kv8_dequant.vt_tiles: expected a contiguous 16-bit tensor (the V^T pages hold fp16 bits)")
+    _pages8(k8, "kv8_dequant.k8")
+    _pages8(vt8, "kv8_dequant.vt8")
+    _chk(src_table, torch.int32, "kv8_dequant.src_table")
+    _chk(dst_table, torch.int32, "kv8_dequant.dst_table")
+    if src_table.numel() != dst_table.numel():
+        raise _lib.VitronHipError("kv8_dequant: src_table and dst_table differ in length")
+    tile = heads * PAGE_TOKENS * head_dim
+    if src_table.numel() and (int(src_table.max()) + 1) * tile > k8.numel() or src_table.numel() and (int(dst_table.max()) + 1) * tile > k_tiles.numel():
+        raise _lib.VitronHipError("kv8_dequant: a table entry points past its pool")
+    _lib.check(lib.vt_kv8_dequant(_p(k8), _p(vt8), _p(src_table), _p(k_tiles), _p(vt_tiles), _p(dst_table), src_table.numel(), heads,
+                                  head_dim, _stream()), "vt_kv8_dequant", lib)
+
+
+def attn_decode_kv8(q: torch.Tensor, k8: torch.Tensor, vt8: torch.Tensor, tile_table: torch.Tensor, seq_desc: torch.Tensor,
+                    heads: int, head_dim: int, scale: float, max_kv_len: int) -> torch.Tensor:
+    """attn_decode on e4m3 pages."""
+    lib, dt = _op16(q, "attn_decode_kv8.q")
+    _pages8(k8, "attn_decode_kv8.k8")
+    _pages8(vt8, "attn_decode_kv8.vt8")
+    out = torch.empty((q.shape[0], heads * head_dim), device=q.device, dtype=dt)
+    nseq = seq_desc.shape[0]
+    scratch = torch.empty(lib.vt_attn_decode_scratch_bytes(nseq, heads, head_dim, int(max_kv_len)), dtype=torch.uint8, device=q.device)
+    _lib.check(lib.vt_attn_decode_kv8(_p(q), q.stride(0), _p(k8), _p(vt8), _p(tile_table), _p(seq_desc), nseq, _p(out),
+                                      out.stride(0), heads, head_dim, float(scale), int(max_kv_len), _p(scratch), scratch.numel(),
+                                      _stream()), "vt_attn_decode_kv8", lib)
+    return out
+
+
+def attn_decode_fused_kv8(qkv: torch.Tensor, q_col0: int, k_col0: int, v_col0: int, k8: torch.Tensor, vt8: torch.Tensor,
+                          tile_table: torch.Tensor, seq_desc: torch.Tensor, heads: int, head_dim: int, scale: float,
+                          rope_cos: Optional[torch.Tensor] = None, rope_sin: Optional[torch.Tensor] = None,
+                          positions: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """attn_decode_fused on e4m3 pages: the new k row / v column are quantised, stored and scored from their quantised values."""
+    lib, dt = _op16(qkv, "attn_decode_fused_kv8.qkv")
+    _chk(qkv, dt, "attn_decode_fused_kv8.qkv")
+    _pages8(k8, "attn_decode_fused_kv8.k8")
+    _pages8(vt8, "attn_decode_fused_kv8.vt8")
+    out = torch.empty((qkv.shape[0], heads * head_dim), device=qkv.device, dtype=dt)
+    _lib.check(lib.vt_attn_decode_fused_kv8(_p(qkv), qkv.stride(0), q_col0, k_col0, v_col0, _p(k8), _p(vt8), _p(tile_table),
+                                            _p(seq_desc), seq_desc.shape[0], _p(out), out.stride(0), heads, head_dim, float(scale),
+                                            _p(rope_cos), _p(rope_sin), _p(positions), _stream()), "vt_attn_decode_fused_kv8", lib)
+    return out
+
+
 def attn_temporal(qkv: torch.Tensor, B: int, T: int, N: int, heads: int) -> torch.Tensor:
     lib, dt = _op16(qkv, "attn_temporal.qkv")
     _chk(qkv, dt, "attn_temporal.qkv")

@@ -32,7 +32,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import ops
-from .engine import PagedKVCache, SequenceState, llama_forward, pair_lo
+from .engine import PagedKVCache, SequenceState, llama_forward, pair_lo, parse_kv_cache_dtype
 
 
 @dataclass
@@ -71,7 +71,11 @@ class ServingEngine:
         self.kv_cap: Optional[int] = None                # upper bound of the pool (pages) when the caller fixed one
         if kv_pages is not None:
             model.reset_prefix_cache()
-            model.kv = PagedKVCache(model.get_model().llama, int(kv_pages))
+            llama = model.get_model().llama
+            if parse_kv_cache_dtype(getattr(model.config, "kv_cache_dtype", None)) == "fp8":    # the pool in the model's KV format
+                model.kv = model.new_kv_pool(int(kv_pages))
+            else:
+                model.kv = PagedKVCache(llama, int(kv_pages))
             self.kv_cap = int(kv_pages)
         from .prefix_cache import VisualFeatureCache
         self._vis_cache = VisualFeatureCache(int(getattr(model.config, "vis_cache_entries", 16)))
