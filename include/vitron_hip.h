@@ -79,6 +79,11 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
  * vt_llama_workspace_bytes_kv8, vt_llama_forward_kv8 and struct vt_kv_cache8) WITHOUT a bump: the change is purely additive -- new
  * symbols and one new struct, no existing struct gained a field, no existing function a parameter -- so every caller built against
  * the earlier 114 header keeps working unchanged. A caller that needs the new entry points looks the symbols up. */
+/* 114 also carries vt_llama_model.last_layer_full and vt_attn_tail_desc WITHOUT a bump. The field sits in what was padding between
+ * precise_qk (offset 88) and embeds_lo (offset 96): the struct's size and the offset of every earlier field are unchanged, and BOTH values
+ * of the field select a correct pass (0 prunes the last layer of a prefill, anything else runs it on all rows as before), so a caller
+ * built against the earlier 114 header keeps working whatever its padding holds. The rule: bump when an existing field moves, the size of
+ * a struct changes or a function gains a parameter. */
 #define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
@@ -246,6 +251,11 @@ int vt_attn_decode(const uint16_t* Q, int ldq, const uint16_t* k_tiles, const ui
 int vt_kv_tiles(uint16_t* qkv, int ldqkv, int q_col0, int k_col0, int v_col0, uint16_t* k_tiles, uint16_t* vt_tiles,
                 const int* tile_table, const int* seq_desc, int nseq, int max_new_tiles, int heads, int head_dim,
                 const float* rope_cos, const float* rope_sin, const int* positions, void* stream);
+/* The single-query problems of the pruned last layer (vt_llama_model.last_layer_full == 0): out [n][4] int32, one descriptor per logit
+ * row r = logit_rows[i] of the sequence s that holds it: {q_row0 = i, q_len = 1, kv_len = kv_len_s - (q_row0_s + q_len_s - 1 - r),
+ * table_off = table_off_s} -- the keys row r sees in the causal pass. Rows in any order, repeats allowed; a row of no sequence gets kv_len 0.
+ * All pointers are device pointers; nothing is read on the host. */
+int vt_attn_tail_desc(const int* seq_desc, int nseq, const int* logit_rows, int n, int* out, void* stream);
 /* temporal attention of the video tower: qkv bf16 [B*T*N][3*heads*64] (row (b*T+t)*N+n, q pre-scaled) ->
  * out bf16 [B*T*N][heads*64]; attends over the T frames at each (b, n). Reference modeling_video.py:105-127. */
 int vt_attn_temporal(const uint16_t* qkv, uint16_t* out, int B, int T, int N, int heads, void* stream);
@@ -477,6 +487,14 @@ typedef struct vt_llama_model {
                                    the softmax amplifies: fp16 full-depth logits 1.3e-3 -> below 1e-3 of the reference's fp32.
                                    Costs two extra GEMM launches, +2 MFMAs per score k-step and the workspace for the pairs; the K pages hold
                                    K_hi (decode steps and later passes are unchanged). Default 0. */
+  int last_layer_full;          /* 0 (default): a standard-mode prefill (max_q_len > 1, rows > 32; prefill_norm_fold and precise_qk 0; with
+                                   qkv_fuse = 1 the layers in front of the last one fuse their page writes, the last one is pruned all the
+                                   same, so qkv_fuse stays bit-identical to the default) that returns no hidden stream (out_hidden NULL) and reads at most 16 logit rows runs its LAST layer on
+                                   those rows only: K | V projection and page writes for every row as before (the KV pool is bit-identical,
+                                   so are the decode steps that follow), but q, the attention, o_proj, the second norm and the MLP only for
+                                   the logit rows, on the weight-streaming GEMMs and the split-KV single-query attention of a decode step
+                                   (same rounding model, a decode step's summation order: logits are as close to the fp32 reference, not
+                                   bit-equal). Any other value: the last layer runs on all rows like the others (A/B, tests). */
   const uint16_t* embeds_lo;    /* optional DEVICE buffer [rows][H] in the operand format: the LOW half of the input embeddings when the caller
                                    carries them as a pair (precise level 2: the projector's output is not rounded to 16 bits on its way into the
                                    residual stream); added to x_embeds in fp32. NULL (default): x_embeds alone. */

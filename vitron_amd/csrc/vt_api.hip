@@ -369,6 +369,10 @@ int vt_kv_tiles(uint16_t* qkv, int ldqkv, int q_col0, int k_col0, int v_col0, ui
                             positions, S(stream));
 }
 
+int vt_attn_tail_desc(const int* seq_desc, int nseq, const int* logit_rows, int n, int* out, void* stream) {
+  return vt_attn_tail_desc_launch((const VtAttnSeq*)seq_desc, nseq, logit_rows, n, (VtAttnSeq*)out, S(stream));
+}
+
 int vt_attn_temporal(const uint16_t* qkv, uint16_t* out, int B, int T, int N, int heads, void* stream) {
   return vt_attn_temporal_launch(qkv, out, B, T, N, heads, S(stream));
 }
@@ -710,6 +714,10 @@ struct LlamaWs {
   float* attn_scratch;
   size_t attn_scratch_bytes;
   int* row_slot;        // prefill: cache slot of every new row (fused QKV epilogue)
+  // pruned last layer of a prefill (<= 16 logit rows): the logit rows as compact [n][.] buffers and their single-query descriptors
+  VtAttnSeq* tail_seq;
+  bf16_t *y_l, *q_l, *att_l, *h_l;
+  float* x_l;
   // precise_qk prefills: the low half of the norm output, the fp32 q | k projection, the low halves of rotated q and of the new keys
   bf16_t *ylo, *qlo, *klo;
   float* qk32;          // level 1: [rows][2H] (q | k); level 2: [rows][3H] (q | k | v)
@@ -728,6 +736,7 @@ struct LlamaWs {
   int* stage_table;
   size_t total;
 };
+constexpr int kTailRows = 16;   // most logit rows the pruned last layer takes (the M <= 16 limit of vt_gemm_skinny_norm_launch)
 LlamaWs llama_carve(const vt_llama_model* m, int rows, int n_logit, int nseq, int max_kv_len, void* p, size_t n, int n_stage_tiles = 0) {
   Carver ws(p, n);
   LlamaWs w;
@@ -744,9 +753,17 @@ LlamaWs llama_carve(const vt_llama_model* m, int rows, int n_logit, int nseq, in
   // tiles * ksplit <= 256 tiles of 256x256 fp32: 64 MiB covers every case the dispatcher splits
   w.splitk_bytes = (rows > 64) ? ((size_t)256 * 256 * 256 * 4) : 0;
   w.splitk = w.splitk_bytes ? (float*)ws.take(w.splitk_bytes) : nullptr;
-  w.attn_scratch_bytes = vt_attn_decode_scratch_bytes(nseq > 0 ? nseq : 1, m->heads, m->head_dim, max_kv_len > 0 ? max_kv_len : 64);
+  // (the pruned last layer runs one single-query problem per logit row, and several logit rows may sit in one sequence)
+  w.attn_scratch_bytes = vt_attn_decode_scratch_bytes(std::max(std::max(nseq, std::min(n_logit, kTailRows)), 1), m->heads, m->head_dim,
+                                                      max_kv_len > 0 ? max_kv_len : 64);
   w.attn_scratch = (float*)ws.take(w.attn_scratch_bytes);
   w.row_slot = (int*)ws.take((size_t)rows * 4);
+  w.tail_seq = (VtAttnSeq*)ws.take((size_t)kTailRows * sizeof(VtAttnSeq));
+  w.y_l = (bf16_t*)ws.take((size_t)kTailRows * H * 2);
+  w.q_l = (bf16_t*)ws.take((size_t)kTailRows * H * 2);
+  w.att_l = (bf16_t*)ws.take((size_t)kTailRows * H * 2);
+  w.h_l = (bf16_t*)ws.take((size_t)kTailRows * I * 2);
+  w.x_l = (float*)ws.take((size_t)kTailRows * H * 4);
   w.ylo = w.qlo = w.klo = nullptr;
   w.qk32 = nullptr;
   w.klo_tiles = 0;
@@ -857,6 +874,15 @@ int llama_forward_body(const vt_llama_model* m, const vt_kv_cache* kv16, const v
   if (m->precise_qk >= 1 && m->precise_qk <= 2 && max_q_len > 1 && !fold_norm)
     VT_REQUIRE(precise, "vt_llama_forward: precise level %d was requested and cannot run here (head_dim %d, %d new tiles per sequence against %d slots)", m->precise_qk, HD, max_new_tiles, w.klo_tiles);
   const bool precise2 = precise && m->precise_qk >= 2 && w.gu32 != nullptr;
+  // The last layer of a prefill, standard mode, when only <= 16 rows are read afterwards (the logit rows; nobody asked for the hidden
+  // stream): K and V of every row still go into the pages, but q, the attention, o_proj, the second norm and the MLP run on the logit
+  // rows alone -- gathered into compact buffers and pushed through what a decode step runs (weight-streaming GEMMs, single-query split-KV
+  // attention with one device-built descriptor per row). The pages are the same bits as on the full path; the logits see the decode
+  // step's summation order. vt_llama_model.last_layer_full = 1 keeps the full path (A/B, tests). qkv_fuse = 1 fuses the page writes of the
+  // layers in front of it and leaves the pruned layer as it is (its q-less page write has nothing to fuse): qkv_fuse stays bit-identical
+  // to the default, pool and logits.
+  const bool prune_last = max_q_len > 1 && rows > 32 && !out_hidden && n_logit_rows >= 0 && n_logit_rows <= kTailRows && m->precise_qk == 0 &&
+                          m->prefill_norm_fold == 0 && m->last_layer_full == 0;
   for (int l = 0; l < m->num_layers; ++l) {   // NF4 layers: all four matrices in 4 bits, nothing else
     const vt_llama_layer& L = m->layers[l];
     if (!L.wqkv_nf4 && !L.wo_nf4 && !L.wgu_nf4 && !L.wdown_nf4) {
@@ -1017,6 +1043,47 @@ int llama_forward_body(const vt_llama_model* m, const vt_kv_cache* kv16, const v
       VT_TRY(vt_gemm_resid_launch(w.h, I, L.wdown, I, w.x, H, nullptr, rows, H, I, 0, w.splitk, w.splitk_bytes, s));
       continue;
     }
+    if (prune_last && l == m->num_layers - 1) {
+      const int n = n_logit_rows;
+      const int* tt = kv8 ? w.stage_table : tile_table;
+      VT_TRY(vt_rmsnorm_launch(w.x, nullptr, L.rms1, w.y, rows, H, m->rms_eps, s));
+      // k | v projection of every row: the fused weight is [3H][H] with q first, so k | v are its last 2H rows (NF4: only those are dequantised)
+      const bf16_t* Wkv = nf4 ? w.wdq : L.wqkv + (size_t)H * H;
+      if (nf4) VT_TRY(vt_nf4_dequant_launch(L.wqkv_nf4 + (size_t)H * (H / 2), L.wqkv_absmax + (size_t)H * (H / 64), 2 * H, H, w.wdq, H, s));
+      VT_TRY(vt_gemm_launch(w.y, H, Wkv, H, w.qkv + H, 3 * H, nullptr, rows, 2 * H, H, VT_EPI_BF16, AUTO, s));
+      if (kv8 && !kv8_no_past)
+        VT_TRY(vt_kv8_dequant_past_launch(k8, vt8, kt, vt, tile_table, (const VtAttnSeq*)seq_desc, nseq, max_kv_len, heads, HD, s));
+      VT_TRY(vt_kv_tiles_launch(w.qkv, 3 * H, -1, H, 2 * H, kt, vt, tt, (const VtAttnSeq*)seq_desc, nseq, max_new_tiles, heads, HD, m->rope_cos,
+                                m->rope_sin, positions, s));
+      // one decoder Linear on the n compact rows. NF4 layer: the matrix is dequantised into w.wdq first, as in front of the tile GEMMs of the
+      // other layers -- a prefill of > 32 rows on NF4 weights stays bit-equal to the 16-bit decoder built from the dequantised weights
+      // (the 4-bit weight-streaming kernel sums in another order)
+      auto tail = [&](const bf16_t* A, int lda, const bf16_t* W16, const uint8_t* W4, const float* absmax, void* C, int ldc, int N, int K,
+                      int epi) -> int {
+        if (nf4) {
+          VT_TRY(vt_nf4_dequant_launch(W4, absmax, N, K, w.wdq, K, s));
+          W16 = w.wdq;
+        }
+        return vt_gemm_skinny_norm_launch(A, lda, W16, K, C, ldc, n, N, K, epi, none, s);
+      };
+      if (n > 0) {   // q of the logit rows (rows 0..H of the fused weight), rotated, against the keys each row sees in the causal pass
+        VT_TRY(vt_gather_rows_launch(w.y, logit_rows, w.y_l, n, (size_t)H * 2, s));
+        VT_TRY(tail(w.y_l, H, L.wqkv, L.wqkv_nf4, L.wqkv_absmax, w.q_l, H, H, H, VT_EPI_BF16));
+        VT_TRY(vt_rope_rows_launch(w.q_l, H, logit_rows, n, positions, m->rope_cos, m->rope_sin, heads, HD, s));
+        VT_TRY(vt_attn_tail_desc_launch((const VtAttnSeq*)seq_desc, nseq, logit_rows, n, w.tail_seq, s));
+        VT_TRY(vt_attn_decode_launch(w.q_l, H, kt, vt, tt, w.tail_seq, n, w.att_l, H, heads, HD, scale, max_kv_len, w.attn_scratch,
+                                     w.attn_scratch_bytes, s));
+      }
+      if (kv8) VT_TRY(vt_kv8_quant_new_launch(kt, vt, k8, vt8, tile_table, (const VtAttnSeq*)seq_desc, nseq, max_new_tiles, heads, HD, s));
+      if (n > 0) {
+        VT_TRY(vt_gather_rows_launch(w.x, logit_rows, w.x_l, n, (size_t)H * 4, s));
+        VT_TRY(tail(w.att_l, H, L.wo, L.wo_nf4, L.wo_absmax, w.x_l, H, H, H, VT_EPI_F32_RESID));
+        VT_TRY(vt_rmsnorm_launch(w.x_l, nullptr, L.rms2, w.y_l, n, H, m->rms_eps, s));
+        VT_TRY(tail(w.y_l, H, L.wgu, L.wgu_nf4, L.wgu_absmax, w.h_l, I, 2 * I, H, VT_EPI_SWIGLU_BF16));
+        VT_TRY(tail(w.h_l, I, L.wdown, L.wdown_nf4, L.wdown_absmax, w.x_l, H, H, I, VT_EPI_F32_RESID));
+      }
+      continue;
+    }
     VT_TRY(dq(L.wqkv, L.wqkv_nf4, L.wqkv_absmax, 3 * H, H, &Wqkv));
     if (fold_tile && l > 0) {
       VT_TRY(vt_gemm_launch(w.y, H, Wqkv, H, w.qkv, 3 * H, nullptr, rows, 3 * H, H, VT_EPI_BF16, AUTO, s, &cons_t));
@@ -1077,7 +1144,8 @@ int llama_forward_body(const vt_llama_model* m, const vt_kv_cache* kv16, const v
     VT_TRY(vt_gemm_launch(w.yn, H, m->lm_head, H, logits, m->vocab, nullptr, n_logit_rows, m->vocab, H, VT_EPI_F32, AUTO, s));
     VT_TRY(vt_gemm_resid_launch(w.ynlo, H, m->lm_head, H, logits, m->vocab, nullptr, n_logit_rows, m->vocab, H, 0, w.splitk, w.splitk_bytes, s));
   } else if (n_logit_rows > 0) {
-    VT_TRY(vt_rmsnorm_launch(w.x, logit_rows, m->final_norm, w.yn, n_logit_rows, H, m->rms_eps, s));
+    // (behind the pruned last layer the logit rows are the compact rows 0..n of x_l)
+    VT_TRY(vt_rmsnorm_launch(prune_last ? w.x_l : w.x, prune_last ? nullptr : logit_rows, m->final_norm, w.yn, n_logit_rows, H, m->rms_eps, s));
     VT_TRY(vt_gemm_launch(w.yn, H, m->lm_head, H, logits, m->vocab, nullptr, n_logit_rows, m->vocab, H, VT_EPI_F32, AUTO, s));
   }
   return VT_OK;

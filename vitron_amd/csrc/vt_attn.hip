@@ -579,11 +579,12 @@ __global__ __launch_bounds__(256, 1) void flash_attn_precise_kernel(const bf16_t
 // (positions past .. kv_len-1) that fall into the tile:
 //   K tile [64][HD]: row = position & 63   (rotary applied when ROPE)
 //   V^T tile [HD][64]: column = position & 63
-//   q rows rotated in place when ROPE.
+//   q rows rotated in place when ROPE (QROT = false: the q columns are neither read nor written -- the pruned last decoder layer of a
+//   prefill, whose q exists only for the logit rows; K and V^T pages are the same bits either way).
 // A tile whose first position is new is written completely (padding rows/cols zero-filled) so the flash
 // kernel never sees non-finite padding.
 // ------------------------------------------------------------------------------------------------------------------
-template <int HD, bool ROPE>
+template <int HD, bool ROPE, bool QROT = true>
 __global__ __launch_bounds__(256) void kv_tiles_kernel(bf16_t* __restrict__ qkv, int ldqkv, int q_col0, int k_col0,
                                                        int v_col0, bf16_t* __restrict__ Kt, bf16_t* __restrict__ Vt,
                                                        const int* __restrict__ tile_table,
@@ -617,9 +618,12 @@ __global__ __launch_bounds__(256) void kv_tiles_kernel(bf16_t* __restrict__ qkv,
         const int rp = positions[row];
         const float* cs = rope_cos + (size_t)rp * (HD / 2) + c * 8;
         const float* sn = rope_sin + (size_t)rp * (HD / 2) + c * 8;
-        bf16_t* qp = qkv + (size_t)row * ldqkv + q_col0 + head * HD;
-        u32x4 qlo = *(const u32x4*)(qp + c * 8);
-        u32x4 qhi = *(const u32x4*)(qp + HD / 2 + c * 8);
+        bf16_t* qp = qkv + (size_t)row * ldqkv + (QROT ? q_col0 : k_col0) + head * HD;
+        u32x4 qlo = {0u, 0u, 0u, 0u}, qhi = {0u, 0u, 0u, 0u};
+        if constexpr (QROT) {
+          qlo = *(const u32x4*)(qp + c * 8);
+          qhi = *(const u32x4*)(qp + HD / 2 + c * 8);
+        }
         u32x4 klo_o, khi_o, qlo_o, qhi_o;
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
@@ -630,7 +634,7 @@ __global__ __launch_bounds__(256) void kv_tiles_kernel(bf16_t* __restrict__ qkv,
             klo_o[w] = pack_op2(rope_lo(a0, b0, c0, s0), rope_lo(a1, b1, c1, s1));
             khi_o[w] = pack_op2(rope_hi(a0, b0, c0, s0), rope_hi(a1, b1, c1, s1));
           }
-          {
+          if constexpr (QROT) {
             const float a0 = oplo_to_f32(qlo[w]), a1 = ophi_to_f32(qlo[w]);
             const float b0 = oplo_to_f32(qhi[w]), b1 = ophi_to_f32(qhi[w]);
             qlo_o[w] = pack_op2(rope_lo(a0, b0, c0, s0), rope_lo(a1, b1, c1, s1));
@@ -639,8 +643,10 @@ __global__ __launch_bounds__(256) void kv_tiles_kernel(bf16_t* __restrict__ qkv,
         }
         lo = klo_o;
         hi = khi_o;
-        *(u32x4*)(qp + c * 8) = qlo_o;
-        *(u32x4*)(qp + HD / 2 + c * 8) = qhi_o;
+        if constexpr (QROT) {
+          *(u32x4*)(qp + c * 8) = qlo_o;
+          *(u32x4*)(qp + HD / 2 + c * 8) = qhi_o;
+        }
       }
       *(u32x4*)(kt + r * HD + c * 8) = lo;
       *(u32x4*)(kt + r * HD + HD / 2 + c * 8) = hi;
@@ -1493,17 +1499,92 @@ int vt_kv_tiles_launch(bf16_t* qkv, int ldqkv, int q_col0, int k_col0, int v_col
                        const float* rope_cos, const float* rope_sin, const int* positions, hipStream_t s) {
   VT_REQUIRE(qkv && Kt && Vt && tile_table && seqs, "vt_kv_tiles: null pointer");
   VT_REQUIRE(HD == 64 || HD == 128, "vt_kv_tiles: head_dim %d unsupported", HD);
-  VT_REQUIRE(ldqkv % 8 == 0 && q_col0 % 8 == 0 && k_col0 % 8 == 0 && v_col0 % 8 == 0, "vt_kv_tiles: misaligned columns");
+  const bool qrot = q_col0 >= 0;   // q_col0 < 0: K and V only, the q columns are not touched
+  VT_REQUIRE(ldqkv % 8 == 0 && (!qrot || q_col0 % 8 == 0) && k_col0 % 8 == 0 && v_col0 % 8 == 0, "vt_kv_tiles: misaligned columns");
   dim3 grid(max_new_tiles, heads, nseq), block(256);
   const bool rope = rope_cos != nullptr;
   if (rope) VT_REQUIRE(rope_sin && positions, "vt_kv_tiles: rope needs sin table and positions");
+#define VT_KVT(HDV, RV, QV) \
+  hipLaunchKernelGGL((kv_tiles_kernel<HDV, RV, QV>), grid, block, 0, s, qkv, ldqkv, q_col0, k_col0, v_col0, Kt, Vt, tile_table, seqs, heads, rope_cos, rope_sin, positions)
   if (HD == 64) {
-    if (rope) hipLaunchKernelGGL((kv_tiles_kernel<64, true>), grid, block, 0, s, qkv, ldqkv, q_col0, k_col0, v_col0, Kt, Vt, tile_table, seqs, heads, rope_cos, rope_sin, positions);
-    else hipLaunchKernelGGL((kv_tiles_kernel<64, false>), grid, block, 0, s, qkv, ldqkv, q_col0, k_col0, v_col0, Kt, Vt, tile_table, seqs, heads, rope_cos, rope_sin, positions);
+    if (rope && qrot) VT_KVT(64, true, true);
+    else if (rope) VT_KVT(64, true, false);
+    else VT_KVT(64, false, true);
   } else {
-    if (rope) hipLaunchKernelGGL((kv_tiles_kernel<128, true>), grid, block, 0, s, qkv, ldqkv, q_col0, k_col0, v_col0, Kt, Vt, tile_table, seqs, heads, rope_cos, rope_sin, positions);
-    else hipLaunchKernelGGL((kv_tiles_kernel<128, false>), grid, block, 0, s, qkv, ldqkv, q_col0, k_col0, v_col0, Kt, Vt, tile_table, seqs, heads, rope_cos, rope_sin, positions);
+    if (rope && qrot) VT_KVT(128, true, true);
+    else if (rope) VT_KVT(128, true, false);
+    else VT_KVT(128, false, true);
   }
+#undef VT_KVT
+  VT_LAUNCH_CHECK();
+  return VT_OK;
+}
+
+// ---- the pruned last decoder layer of a prefill (vt_api.hip): the logit rows as single-query attention problems ------------------
+// One descriptor per logit row, built on the device from the pass's seq_desc: row r of sequence s sees the keys row r sees in the
+// causal prefill, kv_len_s - (last row of s - r), through s's own tiles; q_row0 = i addresses the compact [n][.] buffers (the
+// decode kernel uses it for the Q row and the O row). Rows may repeat and come in any order. A row that belongs to no sequence
+// gets kv_len 0 (the attention output of such a row is 0).
+__global__ void attn_tail_desc_kernel(const VtAttnSeq* __restrict__ seqs, int nseq, const int* __restrict__ logit_rows, int n,
+                                      VtAttnSeq* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int r = logit_rows[i];
+  VtAttnSeq d = {i, 1, 0, 0};
+  for (int sidx = 0; sidx < nseq; ++sidx) {
+    const VtAttnSeq sq = seqs[sidx];
+    if (r >= sq.q_row0 && r < sq.q_row0 + sq.q_len) {
+      d.kv_len = sq.kv_len - (sq.q_row0 + sq.q_len - 1 - r);
+      d.table_off = sq.table_off;
+      break;
+    }
+  }
+  out[i] = d;
+}
+
+// rotary embedding of the compact q rows [n][heads * HD] in place: row i takes the position of row rows_idx[i] of the pass. Same tables,
+// same expression and the same rounding as the q half of kv_tiles_kernel. One block per row; thread -> (head, chunk pair).
+template <int HD>
+__global__ __launch_bounds__(256) void rope_rows_kernel(bf16_t* __restrict__ q, int ldq, const int* __restrict__ rows_idx,
+                                                        const int* __restrict__ positions, const float* __restrict__ rope_cos,
+                                                        const float* __restrict__ rope_sin, int heads) {
+  constexpr int CH = HD / 8;
+  const int rp = positions[rows_idx[blockIdx.x]];
+  for (int it = threadIdx.x; it < heads * (CH / 2); it += 256) {
+    const int head = it / (CH / 2), c = it % (CH / 2);
+    const float* cs = rope_cos + (size_t)rp * (HD / 2) + c * 8;
+    const float* sn = rope_sin + (size_t)rp * (HD / 2) + c * 8;
+    bf16_t* qp = q + (size_t)blockIdx.x * ldq + head * HD;
+    const u32x4 qlo = *(const u32x4*)(qp + c * 8);
+    const u32x4 qhi = *(const u32x4*)(qp + HD / 2 + c * 8);
+    u32x4 qlo_o, qhi_o;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const float c0 = cs[2 * w], c1 = cs[2 * w + 1], s0 = sn[2 * w], s1 = sn[2 * w + 1];
+      const float a0 = oplo_to_f32(qlo[w]), a1 = ophi_to_f32(qlo[w]);
+      const float b0 = oplo_to_f32(qhi[w]), b1 = ophi_to_f32(qhi[w]);
+      qlo_o[w] = pack_op2(rope_lo(a0, b0, c0, s0), rope_lo(a1, b1, c1, s1));
+      qhi_o[w] = pack_op2(rope_hi(a0, b0, c0, s0), rope_hi(a1, b1, c1, s1));
+    }
+    *(u32x4*)(qp + c * 8) = qlo_o;
+    *(u32x4*)(qp + HD / 2 + c * 8) = qhi_o;
+  }
+}
+
+int vt_attn_tail_desc_launch(const VtAttnSeq* seqs, int nseq, const int* logit_rows, int n, VtAttnSeq* out, hipStream_t s) {
+  VT_REQUIRE(seqs && logit_rows && out && nseq > 0 && n > 0, "vt_attn_tail_desc: bad arguments");
+  hipLaunchKernelGGL(attn_tail_desc_kernel, dim3(cdiv(n, 64)), dim3(64), 0, s, seqs, nseq, logit_rows, n, out);
+  VT_LAUNCH_CHECK();
+  return VT_OK;
+}
+
+int vt_rope_rows_launch(bf16_t* q, int ldq, const int* rows_idx, int n, const int* positions, const float* rope_cos, const float* rope_sin,
+                        int heads, int HD, hipStream_t s) {
+  VT_REQUIRE(q && rows_idx && positions && rope_cos && rope_sin && n > 0 && heads > 0, "vt_rope_rows: bad arguments");
+  VT_REQUIRE(HD == 64 || HD == 128, "vt_rope_rows: head_dim %d unsupported", HD);
+  VT_REQUIRE(ldq % 8 == 0 && ((uintptr_t)q % 16) == 0, "vt_rope_rows: misaligned rows");
+  if (HD == 64) hipLaunchKernelGGL((rope_rows_kernel<64>), dim3(n), dim3(256), 0, s, q, ldq, rows_idx, positions, rope_cos, rope_sin, heads);
+  else hipLaunchKernelGGL((rope_rows_kernel<128>), dim3(n), dim3(256), 0, s, q, ldq, rows_idx, positions, rope_cos, rope_sin, heads);
   VT_LAUNCH_CHECK();
   return VT_OK;
 }

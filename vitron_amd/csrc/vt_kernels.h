@@ -132,6 +132,8 @@ int vt_f32_to_pair_launch(const float* x, bf16_t* hi, bf16_t* lo, size_t out_row
 int vt_add_op_to_f32_launch(float* dst, const bf16_t* a, size_t n, hipStream_t s);
 int vt_rowscale_finalize_launch(const float* partials, int np, int ldp, int rows, float inv_dim, float eps, float* out, hipStream_t s);
 int vt_gather_f32_to_bf16_launch(const float* in, const int* idx, bf16_t* out, int rows, int D, hipStream_t s);
+// out row r = in row idx[r], rows of row_bytes bytes (a multiple of 16, both sides 16-byte aligned): a plain copy of any element type
+int vt_gather_rows_launch(const void* in, const int* idx, void* out, int rows, size_t row_bytes, hipStream_t s);
 int vt_bf16_to_f32_launch(const bf16_t* in, float* out, size_t n, hipStream_t s);
 int vt_add_f32_launch(float* dst, const float* a, size_t n, hipStream_t s);
 // drop the CLS row of every frame: out_bf16[f*G2+p] = bf16(x[f*(G2+1)+1+p])
@@ -164,6 +166,12 @@ extern int g_vt_flash_attn_wgs;   // persistent form: workgroup cap (0 = one per
 int vt_kv_tiles_launch(bf16_t* qkv, int ldqkv, int q_col0, int k_col0, int v_col0, bf16_t* Kt, bf16_t* Vt,
                        const int* tile_table, const VtAttnSeq* seqs, int nseq, int max_new_tiles, int heads, int HD,
                        const float* rope_cos, const float* rope_sin, const int* positions, hipStream_t s);
+// (q_col0 < 0: K and V^T pages only, the q columns are neither read nor rotated -- same page bits)
+// the pruned last layer of a prefill: one single-query descriptor per logit row {q_row0 = i, q_len = 1, kv_len = the keys row
+// logit_rows[i] sees, table_off of its sequence}, built on the device; rotary on the compact q rows [n][heads * HD] in place
+int vt_attn_tail_desc_launch(const VtAttnSeq* seqs, int nseq, const int* logit_rows, int n, VtAttnSeq* out, hipStream_t s);
+int vt_rope_rows_launch(bf16_t* q, int ldq, const int* rows_idx, int n, const int* positions, const float* rope_cos, const float* rope_sin,
+                        int heads, int HD, hipStream_t s);
 // precise_qk (vt_llama_model.precise_qk): fp32 q / k in, rotary in fp32, q and k written as operand pairs (hi + lo); the matching
 // attention kernel computes K_hi.(Q_hi + Q_lo)^T + K_lo.Q_hi^T
 int vt_kv_tiles_precise_launch(const float* qk32, int ld32, int v_f32, bf16_t* qkv, int ldqkv, int q_col0, int v_col0, bf16_t* qlo, bf16_t* Kt, bf16_t* Vt,

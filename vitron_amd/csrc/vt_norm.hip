@@ -368,6 +368,13 @@ __global__ void gather_f32_to_bf16_kernel(const float* __restrict__ in, const in
   *(u32x2*)(out + (size_t)r * D + c) = o;
 }
 
+__global__ void gather_rows_kernel(const u32x4* __restrict__ in, const int* __restrict__ idx, u32x4* __restrict__ out, int rows, int per_row) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)rows * per_row) return;
+  const int r = (int)(i / per_row), c = (int)(i % per_row);
+  out[(size_t)r * per_row + c] = in[(size_t)idx[r] * per_row + c];
+}
+
 __global__ void drop_cls_kernel(const float* __restrict__ x, bf16_t* __restrict__ out, int F, int G2, int D) {
   const int per_row = D >> 2;
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -501,6 +508,16 @@ int vt_gather_f32_to_bf16_launch(const float* in, const int* idx, bf16_t* out, i
   VT_REQUIRE(in && out && rows > 0 && D % 4 == 0, "vt_gather_f32_to_bf16: bad arguments");
   const size_t n = (size_t)rows * (D / 4);
   hipLaunchKernelGGL(gather_f32_to_bf16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, idx, out, rows, D);
+  VT_LAUNCH_CHECK();
+  return VT_OK;
+}
+
+int vt_gather_rows_launch(const void* in, const int* idx, void* out, int rows, size_t row_bytes, hipStream_t s) {
+  VT_REQUIRE(in && idx && out && rows > 0 && row_bytes > 0 && row_bytes % 16 == 0, "vt_gather_rows: bad arguments");
+  VT_REQUIRE(((uintptr_t)in % 16) == 0 && ((uintptr_t)out % 16) == 0, "vt_gather_rows: rows must be 16-byte aligned");
+  const int per_row = (int)(row_bytes / 16);
+  const size_t n = (size_t)rows * per_row;
+  hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const u32x4*)in, idx, (u32x4*)out, rows, per_row);
   VT_LAUNCH_CHECK();
   return VT_OK;
 }

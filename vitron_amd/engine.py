@@ -587,6 +587,11 @@ class PackedLlama:
         """RMSNorm folded into the prefill tile GEMMs (vt_llama_model.prefill_norm_fold; measured neutral, default off)."""
         self.model.prefill_norm_fold = int(bool(on))
 
+    def set_last_layer_full(self, on: bool) -> None:
+        """True: a prefill runs its last layer on all rows like the others, instead of only on the <= 16 rows whose logits are read
+        (vt_llama_model.last_layer_full; same KV pool either way; for A/B runs and tests, default off)."""
+        self.model.last_layer_full = int(bool(on))
+
 
 def parse_kv_cache_dtype(x) -> str:
     """config.kv_cache_dtype -> '16bit' | 'fp8'. None / 'auto' / '16bit': the 16-bit pool; 'fp8' / 'fp8_e4m3': the e4m3 pool; anything else

@@ -147,6 +147,15 @@ def kv_tiles(qkv: torch.Tensor, q_col0: int, k_col0: int, v_col0: int, k_tiles: 
                                _p(positions), _stream()), "vt_kv_tiles", lib)
 
 
+def attn_tail_desc(seq_desc: torch.Tensor, logit_rows: torch.Tensor) -> torch.Tensor:
+    """int32 [n,4]: the single-query descriptor of every logit row (vt_attn_tail_desc, include/vitron_hip.h), built on the device."""
+    lib = _lib.load()
+    n = logit_rows.numel()
+    out = torch.empty((n, 4), dtype=torch.int32, device=seq_desc.device)
+    _lib.check(lib.vt_attn_tail_desc(_p(seq_desc), seq_desc.shape[0], _p(logit_rows), n, _p(out), _stream()), "vt_attn_tail_desc", lib)
+    return out
+
+
 def flash_attn(q: torch.Tensor, k_tiles: torch.Tensor, vt_tiles: torch.Tensor, tile_table: torch.Tensor,
                seq_desc: torch.Tensor, max_q_len: int, heads: int, head_dim: int, causal: bool, scale: float,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
