@@ -46,6 +46,7 @@ CFGS = [2, 3, 4, 5, 6, 8, 10]  # 128x128, 256x128, 256x256, 64x128, 256x256 8-ph
 @pytest.mark.parametrize("cfg", CFGS)
 @pytest.mark.parametrize("M,N,K", [(300, 384, 256), (128, 128, 64), (577, 1024, 640), (1000, 512, 1024), (700, 1056, 1408)])
 def test_gemm_tile_configs(dev, cfg, M, N, K):
+    """(exact probes, per-element bounds, strided views: tests/test_gpu_gemm.py)"""
     from vitron_amd import ops
     if cfg in (6, 10) and (K % 128 or K < 256):
         pytest.skip("8-phase kernel needs an even number (>= 4) of 64-wide K steps")
@@ -60,7 +61,8 @@ def test_gemm_tile_configs(dev, cfg, M, N, K):
 @pytest.mark.parametrize("cfg", [5, 10, 2])
 @pytest.mark.parametrize("M,N,K", [(300, 384, 256), (577, 1024, 640 + 128), (1000, 544, 1024)])
 def test_gemm_resid_and_relu_tile_configs(dev, cfg, M, N, K):
-    """residual-accumulate (fp32 C += A W^T + bias), ReLU and quick-GELU epilogues per explicit tile configuration, ragged M / N."""
+    """residual-accumulate (fp32 C += A W^T + bias), ReLU and quick-GELU epilogues per explicit tile configuration, ragged M / N.
+    (exact probes, per-element bounds, strided views: tests/test_gpu_gemm.py)"""
     from vitron_amd import ops
     a, w, b = randn((M, K), 21), randn((N, K), 22, 0.05), randn((N,), 23)
     resid = randn((M, N), 24)
@@ -76,6 +78,7 @@ def test_gemm_resid_and_relu_tile_configs(dev, cfg, M, N, K):
 @pytest.mark.parametrize("epi_name", ["BF16", "BF16_GELU", "BF16_QGELU", "BF16_RELU", "F32_RESID", "F32", "SWIGLU_BF16"])
 @pytest.mark.parametrize("M", [1, 4, 7, 16, 17, 40, 64, 200])
 def test_gemm_epilogues_auto(dev, epi_name, M):
+    """(exact probes, per-element bounds, strided views: tests/test_gpu_gemm.py)"""
     from vitron_amd import ops
     epi = getattr(ops, "EPI_" + epi_name)
     N, K = 320, 192
@@ -91,7 +94,8 @@ def test_gemm_epilogues_auto(dev, epi_name, M):
 @pytest.mark.parametrize("cfg", [1, 9])
 @pytest.mark.parametrize("M,N,K", [(1, 64, 64), (4, 4096, 4096), (3, 96, 1376), (16, 320, 200), (9, 320, 448), (7, 4096 + 32, 11008), (4, 2048, 8)])
 def test_gemm_skinny_kernels(dev, cfg, M, N, K):
-    """M <= 16 weight-streaming kernels: LDS-DMA ring (cfg 1, default when K % 64 == 0) and register-operand MFMA (cfg 9, also the ragged-K fallback); ragged N/K tails, all epilogues."""
+    """M <= 16 weight-streaming kernels: LDS-DMA ring (cfg 1, default when K % 64 == 0) and register-operand MFMA (cfg 9, also the ragged-K fallback); ragged N/K tails, all epilogues.
+    (exact probes, per-element bounds, strided views: tests/test_gpu_gemm.py)"""
     from vitron_amd import ops
     a, w, b = randn((M, K), 21), randn((N, K), 22, 0.05), randn((N,), 23)
     resid = randn((M, N), 24)
@@ -108,7 +112,8 @@ def test_gemm_skinny_kernels(dev, cfg, M, N, K):
                                       (700, 512, 1024, 2), (1088, 4096, 4096, 0), (5120, 4096, 11008, 0)])
 def test_gemm_resid_two_pass_split_k(dev, M, N, K, ks):
     """vt_gemm_bf16_resid_splitk: partial products per K range + ordered reduce == the plain residual GEMM up to fp32
-    summation order, bit-identical from run to run; ks = 0 lets the dispatcher decide (incl. the M-split remainder at M = 5120)."""
+    summation order, bit-identical from run to run; ks = 0 lets the dispatcher decide (incl. the M-split remainder at M = 5120).
+    (exact probes, per-element bounds, strided views: tests/test_gpu_gemm.py)"""
     from vitron_amd import ops
     a, w, b = randn((M, K), 31), randn((N, K), 32, 0.05), randn((N,), 33)
     resid = randn((M, N), 34)
@@ -127,7 +132,8 @@ def test_gemm_resid_two_pass_split_k(dev, M, N, K, ks):
 @pytest.mark.parametrize("M,N,K", [(17, 96, 64), (24, 12288, 4096), (32, 4096 + 32, 11008), (20, 8192 + 32, 256), (32, 320, 1408), (40, 4096, 4096), (64, 8192, 1024)])
 def test_gemm_skinny_32_row_kernel(dev, M, N, K):
     """17..32 rows: the weight-streaming kernel with two MFMA column groups and register-loaded activations (narrow and wide
-    variant, ragged N, all epilogues); 33..64 rows: the same kernel in groups of 32."""
+    variant, ragged N, all epilogues); 33..64 rows: the same kernel in groups of 32.
+    (exact probes, per-element bounds, strided views: tests/test_gpu_gemm.py)"""
     from vitron_amd import ops
     a, w, b = randn((M, K), 41), randn((N, K), 42, 0.05), randn((N,), 43)
     resid = randn((M, N), 44)
@@ -141,7 +147,8 @@ def test_gemm_skinny_32_row_kernel(dev, M, N, K):
 
 
 def test_gemm_transpose_detecting(dev):
-    """A = I-like selector with an ASYMMETRIC W catches row/col swaps of the MFMA C layout."""
+    """A = I-like selector with an ASYMMETRIC W catches row/col swaps of the MFMA C layout.
+    (exact probes, per-element bounds, strided views: tests/test_gpu_gemm.py)"""
     from vitron_amd import ops
     M = N = 128
     K = 128
@@ -492,7 +499,8 @@ def test_sample_top_p_keep_set_and_distribution(dev):
                                                  (1100, 2048, 1024, "SWIGLU_BF16", 10), (260, 512, 256, "BF16", 6)])
 def test_gemm_row_scale(dev, M, N, K, epi_name, cfg):
     """vt_gemm_bf16's optional per-row factor (the consumer side of the folded RMSNorm): epi(rs[m] * (a w^T) + bias) on every
-    MFMA tile path, ragged M included, against fp32 torch."""
+    MFMA tile path, ragged M included, against fp32 torch.
+    (exact probes, per-element bounds, strided views: tests/test_gpu_gemm.py)"""
     from vitron_amd import ops
     g = torch.Generator().manual_seed(M + N + K)
     a = torch.randn((M, K), generator=g).bfloat16()
@@ -561,7 +569,8 @@ def test_sample_top_k_keep_set(dev, V):
 @pytest.mark.parametrize("M,N,K", [(300, 384, 256), (577, 1024, 640 + 128), (1000, 544, 1024), (512, 512, 384), (2048, 1024, 2048), (650, 256, 512)])
 def test_gemm_four_wave_kernel(dev, M, N, K):
     """cfg 13 / 14 / 16: 256x256 (320x256, 224x256) tile, four waves of 128x128 (160x128, 112x128), accumulators pinned to the accumulator
-    file, hand-placed K step (ragged M / N, short and long K loops, every epilogue, repeated launches bit-identical)."""
+    file, hand-placed K step (ragged M / N, short and long K loops, every epilogue, repeated launches bit-identical).
+    (exact probes, per-element bounds, strided views: tests/test_gpu_gemm.py)"""
     from vitron_amd import _lib, ops
     a, w, b = randn((M, K), 41), randn((N, K), 42, 0.05), randn((N,), 43)
     resid = randn((M, N), 44)
@@ -583,7 +592,8 @@ def test_gemm_four_wave_kernel(dev, M, N, K):
 @pytest.mark.parametrize("M,N,K", [(300, 384, 256), (577, 1024, 1024), (1000, 544, 512), (4616, 1024, 1024), (161, 128, 768)])
 def test_gemm_four_wave_ring_kernel(dev, M, N, K):
     """cfg 15: 160x128 tile, four waves of 80x64, four-deep LDS ring with one barrier per K step (ragged M / N, the shortest legal K
-    loop, every epilogue, repeated launches bit-identical, and bit-identical to the ping-pong kernel)."""
+    loop, every epilogue, repeated launches bit-identical, and bit-identical to the ping-pong kernel).
+    (exact probes, per-element bounds, strided views: tests/test_gpu_gemm.py)"""
     from vitron_amd import _lib, ops
     a, w, b = randn((M, K), 71), randn((N, K), 72, 0.05), randn((N,), 73)
     resid = randn((M, N), 74)
@@ -720,7 +730,8 @@ def test_gemm_column_split_plan_is_bit_identical(epi_name):
     """Round 5's column split (a few row blocks x many column tiles that spill just over whole rounds: 768 x 22016 = 258 tiles of 256 rows):
     the AUTO plan runs 85 column tiles on whole rounds of big tiles and plans the 256-column tail again -- weights, bias and output of the
     tail are offset views of the same GEMM, so the result must equal the single-grid launch bit for bit (also for the SwiGLU epilogue,
-    whose output has one column per gate / up pair)."""
+    whose output has one column per gate / up pair).
+    (exact probes, per-element bounds, strided views: tests/test_gpu_gemm.py)"""
     from vitron_amd import _lib, ops
     _lib.load()
     dev = torch.device("cuda:0")

@@ -207,7 +207,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(GemmP8 p) {
   // behind the prologue's vmcnt(0) -- fetched at the top of the epilogue they cost every tile an exposed L2/HBM round trip
   // (+1.3 us per tile measured), and inside the row loop one per row
   float rsv[2][4];
-  if constexpr (EPI != VT_EPI_F32_RESID && EPI != VT_EPI_F32) {
+  if constexpr (EPI != VT_EPI_F32_RESID) {
 #pragma unroll
     for (int qm = 0; qm < 2; ++qm)
 #pragma unroll
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(GemmP8 p) {
   STAGE(1, SLOT_B0);
   if (P4) STAGE(1, SLOT_B1);
   VT_VMCNT(0);
-  if constexpr (EPI != VT_EPI_F32_RESID && EPI != VT_EPI_F32) {
+  if constexpr (EPI != VT_EPI_F32_RESID) {
 #pragma unroll
     for (int qm = 0; qm < 2; ++qm)
 #pragma unroll
@@ -573,7 +573,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(GemmP8 p) {
       for (int mi = 0; mi < 4; ++mi) {
         const int m = bm0 + qm * 128 + wr * 64 + mi * 16 + (lane & 15);
         if (m >= p.M) continue;
-        const float rs = (EPI == VT_EPI_F32) ? 1.f : rsv[qm][mi];
+        const float rs = rsv[qm][mi];
 #pragma unroll
         for (int qn = 0; qn < 2; ++qn) {
           const int nbase = bn0 + qn * 128 + wc * 32;     // multiple of 32

@@ -41,6 +41,20 @@ def _chk(t: torch.Tensor, dtype, name: str):
         raise _lib.VitronHipError(f"{name}: tensor must be contiguous")
 
 
+def _chk_view(t: torch.Tensor, dtype, name: str):
+    """contiguous tensor, or row-strided 2-D view (stride(1) == 1, rows that do not overlap): its row stride travels as the leading dimension.
+    Alignment (lda / ldw % 8, ldc % 4, 16-byte base pointers) is the C ABI's own check."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise _lib.VitronHipError(f"{name}: expected a CUDA/HIP tensor (vitron_amd has no CPU path)")
+    if t.dtype != dtype:
+        raise _lib.VitronHipError(f"{name}: expected dtype {dtype}, got {t.dtype}")
+    if t.is_contiguous():
+        return
+    if t.dim() != 2 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+        raise _lib.VitronHipError(f"{name}: expected a 2-D tensor with contiguous rows (a row-strided view at most), got shape "
+                                  f"{tuple(t.shape)} strides {tuple(t.stride())}")
+
+
 def gemm_plan(M: int, N: int, K: int, epi: int = EPI_BF16):
     """(cfg, rows_first) the dispatcher picks for an AUTO vt_gemm_bf16 of this shape (host logic, no launch; include/vitron_hip.h)."""
     import ctypes
@@ -63,8 +77,8 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
          out: Optional[torch.Tensor] = None, cfg: int = CFG_AUTO, row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = epi(row_scale[:, None] * (a[M,K] @ w[N,K]^T) + bias). EPI_F32_RESID accumulates into `out` (fp32, required)."""
     lib, dt = _op16(a, "gemm.a")
-    _chk(a, dt, "gemm.a")
-    _chk(w, dt, "gemm.w")
+    _chk_view(a, dt, "gemm.a")
+    _chk_view(w, dt, "gemm.w")
     M, K = a.shape
     N, K2 = w.shape
     if K != K2:
@@ -77,7 +91,9 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
         if epi == EPI_F32_RESID:
             raise _lib.VitronHipError("gemm: EPI_F32_RESID needs `out` (the fp32 residual stream)")
         out = torch.empty((M, n_out), device=a.device, dtype=odt)
-    _chk(out, odt, "gemm.out")
+    _chk_view(out, odt, "gemm.out")
+    if not out.is_contiguous() and tuple(out.shape) != (M, n_out):
+        raise _lib.VitronHipError(f"gemm: out is a view of {tuple(out.shape)}, expected {(M, n_out)}")
     if row_scale is not None:
         _chk(row_scale, torch.float32, "gemm.row_scale")
         if row_scale.numel() != M:
@@ -91,11 +107,13 @@ def gemm_resid_splitk(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, bias:
                       partials: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out (fp32) += a @ w^T + bias, optionally as a two-pass split-K through the fp32 workspace `partials`."""
     lib, dt = _op16(a, "gemm_resid_splitk.a")
-    _chk(a, dt, "gemm_resid_splitk.a")
-    _chk(w, dt, "gemm_resid_splitk.w")
-    _chk(out, torch.float32, "gemm_resid_splitk.out")
+    _chk_view(a, dt, "gemm_resid_splitk.a")
+    _chk_view(w, dt, "gemm_resid_splitk.w")
+    _chk_view(out, torch.float32, "gemm_resid_splitk.out")
     M, K = a.shape
     N = w.shape[0]
+    if not out.is_contiguous() and tuple(out.shape) != (M, N):
+        raise _lib.VitronHipError(f"gemm_resid_splitk: out is a view of {tuple(out.shape)}, expected {(M, N)}")
     nbytes = 0 if partials is None else partials.numel() * partials.element_size()
     _lib.check(lib.vt_gemm_bf16_resid_splitk(_p(a), a.stride(0), _p(w), w.stride(0), _p(out), out.stride(0), _p(bias), M, N, K,
                                              int(ksplit), _p(partials), nbytes, _stream()), "vt_gemm_bf16_resid_splitk", lib)
