@@ -84,6 +84,8 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
  * of the field select a correct pass (0 prunes the last layer of a prefill, anything else runs it on all rows as before), so a caller
  * built against the earlier 114 header keeps working whatever its padding holds. The rule: bump when an existing field moves, the size of
  * a struct changes or a function gains a parameter. */
+/* 114 also carries the folded-norm unit entry points vt_gemm_bf16_norm, vt_gemm_bf16_resid_norm and vt_rowscale_finalize WITHOUT a bump:
+ * three new symbols that forward to launches vt_llama_forward already makes; no struct and no existing signature changes. */
 #define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
@@ -123,6 +125,28 @@ int vt_layernorm(float* x, const float* temb, int T, int tokens_per_frame, const
 
 /* y_bf16[r] = w * x[idx ? idx[r] : r] * rsqrt(mean(x^2) + eps) : transformers-4.31 LlamaRMSNorm. */
 int vt_rmsnorm(const float* x, const int* idx, const float* w, uint16_t* y, int rows, int D, float eps, void* stream);
+
+/* ---- the RMSNorm folded into the decoder's 16-bit GEMMs, as vt_llama_forward runs it (no reference counterpart: the reference calls
+ * LlamaRMSNorm and nn.Linear separately; W (w .* x) * rstd == W (x * rstd .* w)). Exported for unit parity tests.
+ * Decode flavour (1 <= M <= 16, N % 32 == 0, K % 64 == 0; epi = VT_EPI_BF16 / F32 / F32_RESID / SWIGLU_BF16; no bias), the tail as vt_gemm_nf4:
+ *   consumer (in_partials != NULL, fp32 [M][in_n], in_n % 64 == 0, in_n <= 512): row m is scaled by
+ *   rsqrt(sum(in_partials[m][0..in_n)) * inv_dim + eps) before the activation;
+ *   producer (out_partials != NULL, VT_EPI_F32_RESID only): also out_xw[m][n] = op16(x_new * out_w[n]) and out_partials[m][n / 16] = the sum
+ *   of x_new^2 over each 16 columns. NULL pointers = no fold. */
+int vt_gemm_bf16_norm(const uint16_t* A, int lda, const uint16_t* W, int ldw, void* C, int ldc, int M, int N, int K, int epi,
+                      const float* in_partials, int in_n, float inv_dim, float eps, const float* out_w, uint16_t* out_xw, int ld_xw,
+                      float* out_partials, void* stream);
+/* Tile flavour, producer: C[M,N] (fp32) += A W^T + bias on the MFMA tile kernels (N % 32 == 0, K % 64 == 0), which also store
+ * out_xw[m][n] = op16(x_new * out_w[n]) (ld_xw % 4 == 0) and out_partials[n / 32][m] = the sum of x_new^2 over each 32 columns (group-major:
+ * out_np >= N / 32 groups of out_ldp >= M floats). ksplit < 0: vt_gemm_bf16's dispatcher with the configuration `cfg` (AUTO or one of the
+ * 128x128 / 256x128 / 256x256 / 64x128 / 256x256_P8 / 256x256_P4 tiles); ksplit >= 0: the residual GEMM's route with its split-K workspace, as
+ * vt_gemm_bf16_resid_splitk (cfg ignored; when K is split the reduce pass writes out_xw and out_partials). */
+int vt_gemm_bf16_resid_norm(const uint16_t* A, int lda, const uint16_t* W, int ldw, float* C, int ldc, const float* bias, int M, int N, int K,
+                            int cfg, int ksplit, float* workspace, size_t workspace_bytes, const float* out_w, uint16_t* out_xw, int ld_xw,
+                            float* out_partials, int out_np, int out_ldp, void* stream);
+/* Tile flavour, between producer and consumer: out[m] = rsqrt(sum_g partials[g][m] * inv_dim + eps), g < np, m < rows (partials fp32
+ * [np][ldp], ldp >= rows) -- the row_scale of the consuming vt_gemm_bf16. */
+int vt_rowscale_finalize(const float* partials, int np, int ldp, int rows, float inv_dim, float eps, float* out, void* stream);
 
 /* ---- NF4 weight-only Linears: load_pretrained_model(..., load_4bit=True) (reference vitron/model/builder.py:36-45: bitsandbytes
  * BitsAndBytesConfig(load_in_4bit=True, bnb_4bit_quant_type="nf4", bnb_4bit_compute_dtype=float16)), restated from bitsandbytes' algorithm:

@@ -159,6 +159,7 @@ def test_gemm_transpose_detecting(dev):
 
 
 def test_layernorm_rmsnorm(dev):
+    """aggregate rel-L2 against fp32 torch; tests/test_gpu_norm.py holds every kernel behind these two operators per element to fp64"""
     from vitron_amd import ops
     for D in (128, 1024, 4096, 320):
         x = randn((37, D), 5, 3.0) + 0.5

@@ -93,6 +93,9 @@ SIGNATURES = {
     "vt_gemm_plan_query": (_i, [_i, _i, _i, _i, vp, vp]),
     "vt_gemm_plan_query2": (_i, [_i, _i, _i, _i, vp, vp, vp]),
     "vt_gemm_bf16_resid_splitk": (_i, [vp, _i, vp, _i, vp, _i, vp, _i, _i, _i, _i, vp, _sz, vp]),
+    "vt_gemm_bf16_norm": (_i, [vp, _i, vp, _i, vp, _i, _i, _i, _i, _i, vp, _i, _f, _f, vp, vp, _i, vp, vp]),
+    "vt_gemm_bf16_resid_norm": (_i, [vp, _i, vp, _i, vp, _i, vp, _i, _i, _i, _i, _i, vp, _sz, vp, vp, _i, vp, _i, _i, vp]),
+    "vt_rowscale_finalize": (_i, [vp, _i, _i, _i, _f, _f, vp, vp]),
     "vt_attn_decode_fused": (_i, [vp, _i, _i, _i, _i, vp, vp, vp, vp, _i, vp, _i, _i, _i, _f, vp, vp, vp, vp]),
     "vt_kv_tiles": (_i, [vp, _i, _i, _i, _i, vp, vp, vp, vp, _i, _i, _i, _i, vp, vp, vp, vp]),
     "vt_attn_tail_desc": (_i, [vp, _i, vp, _i, vp, vp]),

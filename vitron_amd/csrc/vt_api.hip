@@ -330,6 +330,41 @@ int vt_gemm_bf16_resid_splitk(const uint16_t* A, int lda, const uint16_t* W, int
   return vt_gemm_resid_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, ksplit, partials, partial_bytes, S(stream));
 }
 
+// ---- the folded RMSNorm of the 16-bit GEMMs, one launch at a time (unit parity tests) ----
+int vt_gemm_bf16_norm(const uint16_t* A, int lda, const uint16_t* W, int ldw, void* C, int ldc, int M, int N, int K, int epi,
+                      const float* in_partials, int in_n, float inv_dim, float eps, const float* out_w, uint16_t* out_xw, int ld_xw,
+                      float* out_partials, void* stream) {
+  VtGemmNormFuse nf;
+  nf.in_partials = in_partials;
+  nf.in_n = in_n;
+  nf.inv_dim = inv_dim;
+  nf.eps = eps;
+  nf.out_w = out_w;
+  nf.out_xw = out_xw;
+  nf.ld_xw = ld_xw;
+  nf.out_partials = out_partials;
+  return vt_gemm_skinny_norm_launch(A, lda, W, ldw, C, ldc, M, N, K, epi, nf, S(stream));
+}
+
+int vt_gemm_bf16_resid_norm(const uint16_t* A, int lda, const uint16_t* W, int ldw, float* C, int ldc, const float* bias, int M, int N, int K,
+                            int cfg, int ksplit, float* workspace, size_t workspace_bytes, const float* out_w, uint16_t* out_xw, int ld_xw,
+                            float* out_partials, int out_np, int out_ldp, void* stream) {
+  VT_REQUIRE(out_w && out_xw && out_partials, "vt_gemm_bf16_resid_norm: the producer needs out_w, out_xw and out_partials");
+  VtGemmNormFuse nf;
+  nf.out_w = out_w;
+  nf.out_xw = out_xw;
+  nf.ld_xw = ld_xw;
+  nf.out_partials = out_partials;
+  nf.out_np = out_np;
+  nf.out_ldp = out_ldp;
+  if (ksplit < 0) return vt_gemm_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, VT_EPI_F32_RESID, cfg, S(stream), &nf);
+  return vt_gemm_resid_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, ksplit, workspace, workspace_bytes, S(stream), &nf);
+}
+
+int vt_rowscale_finalize(const float* partials, int np, int ldp, int rows, float inv_dim, float eps, float* out, void* stream) {
+  return vt_rowscale_finalize_launch(partials, np, ldp, rows, inv_dim, eps, out, S(stream));
+}
+
 int vt_attn_decode_fused(const uint16_t* qkv, int ldqkv, int q_col0, int k_col0, int v_col0, uint16_t* k_tiles,
                          uint16_t* vt_tiles, const int* tile_table, const int* seq_desc, int nseq, uint16_t* O, int ldo,
                          int heads, int head_dim, float scale, const float* rope_cos, const float* rope_sin,

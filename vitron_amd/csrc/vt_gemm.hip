@@ -235,7 +235,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_bt_kernel(GemmP p
             ss += __shfl_xor(ss, 16, 64);
             ss += __shfl_xor(ss, 32, 64);
             const int grp = (bn0 + wn * WTN + (ni - 1) * 16) >> 5;
-            if ((lane >> 4) == 0 && grp < p.nf.out_np) out_partials[(size_t)grp * p.nf.out_ldp + m] = ss;
+            // (a group past N -- the ragged last column tile -- is absent: out_np may be larger than N / 32)
+            if ((lane >> 4) == 0 && (grp << 5) < p.N) out_partials[(size_t)grp * p.nf.out_ldp + m] = ss;
             ss = 0.f;
           }
         }

@@ -120,28 +120,139 @@ def gemm_resid_splitk(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, bias:
     return out
 
 
+def _chk_norm_out(norm_out, dt, M: int, N: int, name: str):
+    """(w fp32 [N], xw op16 [M][N] -- a row-strided view at most --, partials fp32) of a folded-norm producer"""
+    ow, oxw, opart = norm_out
+    _chk(ow, torch.float32, name + ".norm_out.w")
+    _chk_view(oxw, dt, name + ".norm_out.xw")
+    _chk(opart, torch.float32, name + ".norm_out.partials")
+    if ow.numel() != N or tuple(oxw.shape) != (M, N):
+        raise _lib.VitronHipError(f"{name}: norm_out shapes must be w [N], xw [M][N]")
+    return ow, oxw, opart
+
+
+def gemm_norm(a: torch.Tensor, w: torch.Tensor, epi: int = EPI_BF16, out: Optional[torch.Tensor] = None,
+              norm_in: Optional[tuple] = None, norm_out: Optional[tuple] = None) -> torch.Tensor:
+    """out = epi(a[M,K] @ w[N,K]^T) on the M <= 16 weight-streaming kernel with the decode step's folded RMSNorm (include/vitron_hip.h
+    vt_gemm_bf16_norm; EPI_BF16 / EPI_F32 / EPI_F32_RESID into `out` / EPI_SWIGLU_BF16), the conventions of gemm_nf4:
+      norm_in  = (partials fp32 [M][in_n], inv_dim, eps): row m scaled by rsqrt(sum(partials[m]) * inv_dim + eps);
+      norm_out = (w_next fp32 [N], xw op16 [M][N], partials fp32 [M][N/16]) with EPI_F32_RESID: xw = op16(x_new * w_next), partials = sums
+      of x_new^2 over each 16 columns."""
+    lib, dt = _op16(a, "gemm_norm.a")
+    _chk_view(a, dt, "gemm_norm.a")
+    _chk_view(w, dt, "gemm_norm.w")
+    M, K = a.shape
+    N, K2 = w.shape
+    if K != K2:
+        raise _lib.VitronHipError(f"gemm_norm: K mismatch {K} vs {K2}")
+    n_out = N // 2 if epi == EPI_SWIGLU_BF16 else N
+    odt = torch.float32 if epi in (EPI_F32, EPI_F32_RESID) else dt
+    if out is None:
+        if epi == EPI_F32_RESID:
+            raise _lib.VitronHipError("gemm_norm: EPI_F32_RESID needs `out` (the fp32 residual stream)")
+        out = torch.empty((M, n_out), device=a.device, dtype=odt)
+    _chk_view(out, odt, "gemm_norm.out")
+    if tuple(out.shape) != (M, n_out):
+        raise _lib.VitronHipError(f"gemm_norm: out is {tuple(out.shape)}, expected {(M, n_out)}")
+    pin, in_n, inv_dim, eps = None, 0, 0.0, 0.0
+    if norm_in is not None:
+        pin, inv_dim, eps = norm_in
+        _chk(pin, torch.float32, "gemm_norm.norm_in")
+        if pin.dim() != 2 or pin.shape[0] < M:
+            raise _lib.VitronHipError("gemm_norm: norm_in partials must be [M][in_n]")
+        in_n = pin.shape[1]
+    ow = oxw = opart = None
+    ld_xw = 0
+    if norm_out is not None:
+        ow, oxw, opart = _chk_norm_out(norm_out, dt, M, N, "gemm_norm")
+        if opart.numel() < M * (N // 16):
+            raise _lib.VitronHipError("gemm_norm: norm_out partials must be [M][N/16]")
+        ld_xw = oxw.stride(0)
+    _lib.check(lib.vt_gemm_bf16_norm(_p(a), a.stride(0), _p(w), w.stride(0), _p(out), out.stride(0), M, N, K, epi, _p(pin), in_n,
+                                     float(inv_dim), float(eps), _p(ow), _p(oxw), ld_xw, _p(opart), _stream()), "vt_gemm_bf16_norm", lib)
+    return out
+
+
+def gemm_resid_norm(a: torch.Tensor, w: torch.Tensor, out: torch.Tensor, norm_out: tuple, bias: Optional[torch.Tensor] = None,
+                    cfg: int = CFG_AUTO, ksplit: int = -1, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out (fp32) += a @ w^T + bias on the MFMA tile kernels with the folded RMSNorm's producer (include/vitron_hip.h vt_gemm_bf16_resid_norm):
+    norm_out = (w_next fp32 [N], xw op16 [M][N], partials fp32 [np][ldp], np >= N/32 groups of ldp >= M rows): xw = op16(x_new * w_next),
+    partials[g][m] = the sum of x_new^2 over columns [32 g, 32 g + 32). ksplit < 0: gemm's dispatcher with `cfg`; ksplit >= 0: the route of
+    gemm_resid_splitk (0 = decide, >= 2 = force) through the fp32 `workspace`."""
+    lib, dt = _op16(a, "gemm_resid_norm.a")
+    _chk_view(a, dt, "gemm_resid_norm.a")
+    _chk_view(w, dt, "gemm_resid_norm.w")
+    _chk_view(out, torch.float32, "gemm_resid_norm.out")
+    M, K = a.shape
+    N, K2 = w.shape
+    if K != K2:
+        raise _lib.VitronHipError(f"gemm_resid_norm: K mismatch {K} vs {K2}")
+    if tuple(out.shape) != (M, N):
+        raise _lib.VitronHipError(f"gemm_resid_norm: out is {tuple(out.shape)}, expected {(M, N)}")
+    if bias is not None:
+        _chk(bias, torch.float32, "gemm_resid_norm.bias")
+    ow, oxw, opart = _chk_norm_out(norm_out, dt, M, N, "gemm_resid_norm")
+    if opart.dim() != 2 or opart.shape[0] < N // 32 or opart.shape[1] < M:
+        raise _lib.VitronHipError(f"gemm_resid_norm: norm_out partials must be [np >= N/32][ldp >= M], got {tuple(opart.shape)}")
+    nbytes = 0 if workspace is None else workspace.numel() * workspace.element_size()
+    _lib.check(lib.vt_gemm_bf16_resid_norm(_p(a), a.stride(0), _p(w), w.stride(0), _p(out), out.stride(0), _p(bias), M, N, K, int(cfg),
+                                           int(ksplit), _p(workspace), nbytes, _p(ow), _p(oxw), oxw.stride(0), _p(opart), opart.shape[0],
+                                           opart.shape[1], _stream()), "vt_gemm_bf16_resid_norm", lib)
+    return out
+
+
+def rowscale_finalize(partials: torch.Tensor, rows: int, inv_dim: float, eps: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[m] = rsqrt(sum_g partials[g][m] * inv_dim + eps), m < rows, for partials fp32 [np][ldp >= rows]: the row_scale of the GEMM that
+    consumes a gemm_resid_norm producer's xw."""
+    _chk(partials, torch.float32, "rowscale_finalize.partials")
+    if partials.dim() != 2 or partials.shape[1] < rows:
+        raise _lib.VitronHipError(f"rowscale_finalize: partials must be [np][ldp >= rows], got {tuple(partials.shape)} for rows={rows}")
+    if out is None:
+        out = torch.empty((rows,), device=partials.device, dtype=torch.float32)
+    _chk(out, torch.float32, "rowscale_finalize.out")
+    if out.numel() < rows:
+        raise _lib.VitronHipError(f"rowscale_finalize: out has {out.numel()} elements for rows={rows}")
+    lib = _lib.load_any()
+    _lib.check(lib.vt_rowscale_finalize(_p(partials), partials.shape[0], partials.shape[1], rows, float(inv_dim), float(eps), _p(out),
+                                        _stream()), "vt_rowscale_finalize", lib)
+    return out
+
+
+def _norm_out(out: Optional[torch.Tensor], rows: int, D: int, device, dtype, name: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty((rows, D), device=device, dtype=dtype)
+    _chk(out, dtype, name + ".out")
+    if tuple(out.shape) != (rows, D):
+        raise _lib.VitronHipError(f"{name}: out is {tuple(out.shape)}, expected {(rows, D)}")
+    return out
+
+
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, temb: Optional[torch.Tensor] = None,
-              tokens_per_frame: int = 0, dtype=None) -> torch.Tensor:
+              tokens_per_frame: int = 0, dtype=None, out: Optional[torch.Tensor] = None, rows: Optional[int] = None) -> torch.Tensor:
     """16-bit (`dtype`: bf16 default / fp16) LayerNorm of the fp32 rows of x; with temb ([T,D] fp32)
-    x[row] += temb[(row//tokens_per_frame)%T] in place."""
+    x[row] += temb[(row//tokens_per_frame)%T] in place. `rows`: only the first `rows` rows of x; `out`: a contiguous [rows][D] tensor."""
     dtype = dtype or _lib.torch_dtype()
     lib = _lib.lib_for(dtype)
     _chk(x, torch.float32, "layernorm.x")
-    rows, D = x.shape
-    y = torch.empty((rows, D), device=x.device, dtype=dtype)
+    D = x.shape[1]
+    rows = x.shape[0] if rows is None else rows
+    if not 0 < rows <= x.shape[0]:
+        raise _lib.VitronHipError(f"layernorm: rows={rows} of an x of {x.shape[0]} rows")
+    y = _norm_out(out, rows, D, x.device, dtype, "layernorm")
     T = 0 if temb is None else temb.shape[0]
     _lib.check(lib.vt_layernorm(_p(x), _p(temb), T, tokens_per_frame, _p(gamma), _p(beta), _p(y), rows, D, eps, _stream()),
                "vt_layernorm", lib)
     return y
 
 
-def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float, idx: Optional[torch.Tensor] = None, dtype=None) -> torch.Tensor:
+def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float, idx: Optional[torch.Tensor] = None, dtype=None,
+            out: Optional[torch.Tensor] = None) -> torch.Tensor:
     dtype = dtype or _lib.torch_dtype()
     lib = _lib.lib_for(dtype)
     _chk(x, torch.float32, "rmsnorm.x")
     rows = x.shape[0] if idx is None else idx.shape[0]
     D = x.shape[1]
-    y = torch.empty((rows, D), device=x.device, dtype=dtype)
+    y = _norm_out(out, rows, D, x.device, dtype, "rmsnorm")
     _lib.check(lib.vt_rmsnorm(_p(x), _p(idx), _p(w), _p(y), rows, D, eps, _stream()), "vt_rmsnorm", lib)
     return y
 
