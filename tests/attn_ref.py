@@ -1,5 +1,6 @@
 """Host restatement of the decode attention kernels (vitron_amd/csrc/vt_attn.hip attn_decode_fused_kernel, attn_decode_kernel +
-attn_decode_combine_kernel; include/vitron_hip.h vt_attn_decode_fused / vt_attn_decode): the paged K / V^T layout (pack_pages /
+attn_decode_combine_kernel, whose arithmetic is the shared bodies of vitron_amd/csrc/vt_attn_decode.h with the 16-bit page format;
+include/vitron_hip.h vt_attn_decode_fused / vt_attn_decode): the paged K / V^T layout (pack_pages /
 unpack_pages, written here without vt_kv_tiles so that a layout slip in that kernel cannot hide a matching one in the decode kernels),
 the kernels' half-split rotary embedding rounded exactly as they round it (rope_ref), and fp64 single-query attention with a per-element
 error limit for the kernels' fp32 arithmetic (decode_ref / decode_bound). The prefill kernels (flash_attn_kernel, vt_attn_w4.hip

@@ -1,4 +1,5 @@
-"""Host restatement of the FP8 (OCP e4m3fn) paged KV cache (vitron_amd/csrc/vt_kv8.hip; include/vitron_hip.h "FP8 KV CACHE"): the
+"""Host restatement of the FP8 (OCP e4m3fn) paged KV cache (vitron_amd/csrc/vt_kv8.hip, its decode kernels being the shared bodies of
+vitron_amd/csrc/vt_attn_decode.h with the e4m3 page format; include/vitron_hip.h "FP8 KV CACHE"): the
 element format from its definition (E4M3 table), the canonical byte quant(x) = e4m3_rne(clamp(x, -448, +448)) and its exact inverse,
 the page layout (pack_pages8 / unpack_pages8 = the 16-bit layouts of tests/attn_ref.py with 1-byte elements), and the fp64 reference +
 per-element error limit of the fp8 decode kernels (decode_ref / decode_bound over the DEQUANTISED pages: the quantisation itself is
@@ -88,7 +89,7 @@ def decode_ref(q, k8, v8, scale: float) -> torch.Tensor:
 
 def decode_bound(q, k8, v8, scale: float, store: str, exact_scores: bool = False) -> torch.Tensor:
     """Per-element limit of |got - decode_ref| for attn_decode_kv8_kernel / attn_decode_fused_kv8_kernel: attn_ref.decode_bound's terms with
-    the operation counts of the fp8 kernels (vt_kv8.hip header comments), every constant as there:
+    the operation counts of the fp8 kernels (vt_attn_decode.h header comments with EPC = 16), every constant as there:
     * scores: the product of an e4m3 value (4 significant bits) and a 16-bit operand value is exact in fp32; a lane chains 16 fmaf (one
       16-byte chunk = 16 elements of a key) and the hd / 16 <= 8 lanes of a key meet in <= 3 adds -- <= 19 roundings on any path, inside the
       (hd + 16) u sum |q k| of the 16-bit bound, which holds for any summation order. Unchanged.

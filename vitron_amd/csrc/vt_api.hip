@@ -256,7 +256,6 @@ int vt_flash_attn_block_order(int heads, int q_blocks, int nseq, int multiproces
   return (int)o.size();
 }
 
-size_t vt_attn_decode_scratch_bytes(int nseq, int heads, int head_dim, int max_kv_len);  // defined in vt_attn.hip (C++ linkage there)
 int vt_attn_decode(const uint16_t* Q, int ldq, const uint16_t* k_tiles, const uint16_t* vt_tiles, const int* tile_table,
                    const int* seq_desc, int nseq, uint16_t* O, int ldo, int heads, int head_dim, float scale,
                    int max_kv_len, void* scratch, size_t scratch_bytes, void* stream) {

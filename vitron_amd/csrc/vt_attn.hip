@@ -17,13 +17,15 @@
 //  * kv_tiles_kernel<HD, ROPE>: fused-QKV rows -> (rotary embedding on q,k) -> K tiles / V^T tiles.
 //  * attn_decode_fused_kernel<HD, ROPE>: one decode step's attention in one launch (rotary on the new q / k, k / v append to
 //    the pages, single-query attention, in-block combine); attn_decode_kernel + _combine: the same on an existing cache as a
-//    standalone op (split over the KV tiles). HBM-bound.
+//    standalone op (split over the KV tiles). HBM-bound. The bodies are vt_attn_decode.h's (shared with the e4m3 pages of
+//    vt_kv8.hip); this file holds the 16-bit page format and the combine kernel.
 //  * attn_temporal8_kernel / attn_temporal_kernel<T>: the video tower's attention over T frames at one token position
 //    (reference modeling_video.py:105-127) -- one wavefront per (clip, position, head).
 #include <stdlib.h>
 
 #include <atomic>
 
+#include "vt_attn_decode.h"
 #include "vt_common.h"
 #include "vt_kernels.h"
 #include "vt_mx4.h"
@@ -837,55 +839,40 @@ __global__ __launch_bounds__(256) void kv_tiles_precise_kernel(const float* __re
   }
 }
 
-// lane ^ MASK exchange inside groups of 16 lanes without an LDS address: DPP quad_perm (1, 2), row_ror:8 (8), ds_swizzle (4)
-template <int MASK>
-__device__ __forceinline__ float lane_xor16(float v) {
-  int x = __builtin_bit_cast(int, v);
-  if constexpr (MASK == 1) x = __builtin_amdgcn_update_dpp(0, x, 0xB1, 0xF, 0xF, true);
-  else if constexpr (MASK == 2) x = __builtin_amdgcn_update_dpp(0, x, 0x4E, 0xF, 0xF, true);
-  else if constexpr (MASK == 8) x = __builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, true);
-  else x = __builtin_amdgcn_ds_swizzle(x, (MASK << 10) | 0x1F);
-  return __builtin_bit_cast(float, x);
-}
-// CH lanes (c = lane % CH) each hold CH partial sums part[i]; on return part[0] is the FULL sum of value i == c.
-// Recursive halving: CH - 1 exchanges instead of CH * log2(CH) for one butterfly per value.
-template <int CH>
-__device__ __forceinline__ float reduce_scatter_lanes(float (&part)[CH], int c) {
-#define VT_RS_STEP(N)                                                   \
-  if constexpr (CH >= 2 * (N)) {                                        \
-    const bool up = (c & (N)) != 0;                                     \
-    _Pragma("unroll") for (int j = 0; j < (N); ++j) {                   \
-      const float send = up ? part[j] : part[j + (N)];                  \
-      const float mine = up ? part[j + (N)] : part[j];                  \
-      part[j] = mine + lane_xor16<(N)>(send);                           \
-    }                                                                   \
+// ------------------------------------------------------------------------------------------------------------------
+// Decode attention on 16-bit pages: the bodies are vt_attn_decode.h's, this is the page format. EPC = 8: 16 (HD = 128) lanes
+// cooperate on one 256-B K row, 4 rows per wave-instruction, 15 exchanges per tile; 8 lanes cooperate on one 128-B V^T row,
+// 8 rows per wave-instruction = 8 full cache lines. K pages hold the operand format of the build, V^T pages fp16 in both builds.
+// ------------------------------------------------------------------------------------------------------------------
+struct DecodePages16 {
+  typedef bf16_t elem_t;
+  static constexpr int EPC = 8;
+  static __device__ __forceinline__ float dot(const u32x4 kv, const float (&qf)[8]) {
+    float s = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      s = fmaf(oplo_to_f32(kv[w]), qf[2 * w], s);
+      s = fmaf(ophi_to_f32(kv[w]), qf[2 * w + 1], s);
+    }
+    return s;
   }
-  VT_RS_STEP(8)
-  VT_RS_STEP(4)
-  VT_RS_STEP(2)
-  VT_RS_STEP(1)
-#undef VT_RS_STEP
-  return part[0];
-}
-template <int CH>
-__device__ __forceinline__ float allreduce_lanes(float v) {
-  if constexpr (CH >= 16) v += lane_xor16<8>(v);
-  if constexpr (CH >= 8) v += lane_xor16<4>(v);
-  v += lane_xor16<2>(v);
-  v += lane_xor16<1>(v);
-  return v;
-}
+  static __device__ __forceinline__ float pv(float acc, float alpha, const u32x4 vv, const float (&p)[8]) {
+    float a = acc * alpha;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      a = fmaf(f16lo_to_f32(vv[w]), p[2 * w], a);
+      a = fmaf(f16hi_to_f32(vv[w]), p[2 * w + 1], a);
+    }
+    return a;
+  }
+  // the stored K chunk is the rounded operand row itself
+  static __device__ __forceinline__ u32x4 pack_k(const uint32_t (&w)[4]) { return (u32x4){w[0], w[1], w[2], w[3]}; }
+  static __device__ __forceinline__ u32x4 pack_v(const uint32_t (&w)[4]) {
+    return (u32x4){op2_to_f16x2(w[0]), op2_to_f16x2(w[1]), op2_to_f16x2(w[2]), op2_to_f16x2(w[3])};
+  }
+  static __device__ __forceinline__ float v_to_f32(elem_t h) { return f16_bits_to_f32(h); }
+};
 
-// ------------------------------------------------------------------------------------------------------------------
-// attn_decode_kernel: single-query attention over the paged tiles, flash-decoding style. HBM-bound: the whole job is
-// to stream K and V^T tiles once, fully coalesced, with enough waves in flight.
-//   grid (head, sequence, split); 4 waves per block; wave w of split s owns tiles t = 4*s + w, 4*s + w + 4*nsplit, ...
-//   scores : 16 (HD=128) lanes cooperate on one 256-B K row, 4 rows per wave-instruction; the 16 partial sums per lane are
-//            reduce-scattered over the 16 lanes (15 DPP/swizzle exchanges per tile), lane ends up owning key (lane%16)*4 + lane/16
-//   PV     : 8 lanes cooperate on one 128-B V^T row (8 rows per wave-instruction = 8 full cache lines); every lane
-//            keeps HD/8 partial accumulators and the cross-lane reduction happens ONCE after the last tile
-//   each block writes an online-softmax partial (m, l, o[HD]) to scratch; attn_decode_combine_kernel merges the splits.
-// ------------------------------------------------------------------------------------------------------------------
 template <int HD>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restrict__ Q, int ldq,
                                                           const bf16_t* __restrict__ Kt,
@@ -893,119 +880,10 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const bf16_t* __restri
                                                           const int* __restrict__ tile_table,
                                                           const VtAttnSeq* __restrict__ seqs, int heads,
                                                           float scale_log2e, float* __restrict__ part, int nsplit) {
-  constexpr int CH = HD / 8;        // 16-B chunks per K row; CH lanes cooperate on one key
-  constexpr int KPI = 64 / CH;      // keys per wave-instruction
-  constexpr int NACC = HD / 8;      // V^T rows handled per lane (one per PV instruction)
-  __shared__ float sm_m[4], sm_l[4];
-  __shared__ float sm_o[4][HD];
-  __shared__ __attribute__((aligned(16))) float sm_p[4][64];
-  const VtAttnSeq sq = seqs[blockIdx.y];
-  const int head = blockIdx.x, split = blockIdx.z;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int ntiles = (sq.kv_len + 63) >> 6;
-  const bf16_t* qp = Q + (size_t)sq.q_row0 * ldq + head * HD;
-  const int c = lane % CH;
-  const u32x4 qv = *(const u32x4*)(qp + c * 8);
-  float qf[8];
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    qf[2 * w] = oplo_to_f32(qv[w]);
-    qf[2 * w + 1] = ophi_to_f32(qv[w]);
-  }
-  float m_run = -INFINITY, l_run = 0.f, acc[NACC];
-#pragma unroll
-  for (int i = 0; i < NACC; ++i) acc[i] = 0.f;
-  const int vrow = lane >> 3, vchk = lane & 7;
-  const int key_of_lane = c * KPI + lane / CH;   // the key (inside a tile) whose score this lane ends up owning
-
-  for (int t = split * 4 + wave; t < ntiles; t += 4 * nsplit) {
-    const size_t toff = ((size_t)tile_table[sq.table_off + t] * heads + head) * 64 * HD;
-    const bf16_t* kt = Kt + toff;
-    const bf16_t* vt = Vt + toff;
-    // the whole tile (16 KiB of K + 16 KiB of V^T) is requested before anything is consumed
-    u32x4 kk[CH], vv[NACC];
-#pragma unroll
-    for (int i = 0; i < CH; ++i) kk[i] = __builtin_nontemporal_load((const u32x4*)(kt + (i * KPI + lane / CH) * HD + c * 8));
-#pragma unroll
-    for (int i = 0; i < NACC; ++i) vv[i] = __builtin_nontemporal_load((const u32x4*)(vt + (i * 8 + vrow) * 64 + vchk * 8));
-    __builtin_amdgcn_sched_barrier(0);
-    float part[CH];
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      const u32x4 kv = kk[i];
-      float part_s = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        part_s = fmaf(oplo_to_f32(kv[w]), qf[2 * w], part_s);
-        part_s = fmaf(ophi_to_f32(kv[w]), qf[2 * w + 1], part_s);
-      }
-      part[i] = part_s;
-    }
-    const float s_mine = reduce_scatter_lanes<CH>(part, c);   // full score of key c*KPI + lane/CH
-    const int mykey = t * 64 + key_of_lane;
-    const float s2 = (mykey < sq.kv_len) ? s_mine * scale_log2e : -INFINITY;
-    const float m_new = fmaxf(m_run, wave_max(s2));
-    const float alpha = fast_exp2(m_run - m_new);
-    const float p = fast_exp2(s2 - m_new);
-    l_run = l_run * alpha + wave_sum(p);
-    m_run = m_new;
-    sm_p[wave][key_of_lane] = p;
-    __builtin_amdgcn_wave_barrier();  // DS ops of one wave are in order; only stop compiler reordering
-    const f32x4 pa = *(const f32x4*)(&sm_p[wave][vchk * 8]);
-    const f32x4 pb = *(const f32x4*)(&sm_p[wave][vchk * 8 + 4]);
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int i = 0; i < NACC; ++i) {
-      float a = acc[i] * alpha;
-      a = fmaf(f16lo_to_f32(vv[i][0]), pa[0], a);
-      a = fmaf(f16hi_to_f32(vv[i][0]), pa[1], a);
-      a = fmaf(f16lo_to_f32(vv[i][1]), pa[2], a);
-      a = fmaf(f16hi_to_f32(vv[i][1]), pa[3], a);
-      a = fmaf(f16lo_to_f32(vv[i][2]), pb[0], a);
-      a = fmaf(f16hi_to_f32(vv[i][2]), pb[1], a);
-      a = fmaf(f16lo_to_f32(vv[i][3]), pb[2], a);
-      a = fmaf(f16hi_to_f32(vv[i][3]), pb[3], a);
-      acc[i] = a;
-    }
-  }
-  // reduce the 8 lanes of every V^T row, then combine the 4 waves through LDS
-#pragma unroll
-  for (int i = 0; i < NACC; ++i) {
-    float a = acc[i];
-    a += __shfl_xor(a, 1, 64);
-    a += __shfl_xor(a, 2, 64);
-    a += __shfl_xor(a, 4, 64);
-    if (vchk == 0) sm_o[wave][i * 8 + vrow] = a;
-  }
-  if (lane == 0) {
-    sm_m[wave] = m_run;
-    sm_l[wave] = l_run;
-  }
-  __syncthreads();
-  if (wave == 0) {
-    const float m = fmaxf(fmaxf(sm_m[0], sm_m[1]), fmaxf(sm_m[2], sm_m[3]));
-    float l = 0.f, w4[4];
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      w4[w] = (sm_m[w] == -INFINITY) ? 0.f : fast_exp2(sm_m[w] - m);
-      l += sm_l[w] * w4[w];
-    }
-    float* dst = part + (((size_t)blockIdx.y * heads + head) * nsplit + split) * (HD + 2);
-    if (lane == 0) {
-      dst[0] = m;
-      dst[1] = l;
-    }
-#pragma unroll
-    for (int i = 0; i < HD / 64; ++i) {
-      const int d = lane + 64 * i;
-      float o = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) o += sm_o[w][d] * w4[w];
-      dst[2 + d] = o;
-    }
-  }
+  attn_decode_split_body<DecodePages16, HD>(Q, ldq, Kt, Vt, tile_table, seqs, heads, scale_log2e, part, nsplit);
 }
 
+// merges the splits' partials (fp32, [sequence][head][split][2 + HD]); nothing in it depends on the page format
 template <int HD>
 __global__ __launch_bounds__(64) void attn_decode_combine_kernel(const float* __restrict__ part,
                                                                  const VtAttnSeq* __restrict__ seqs,
@@ -1030,231 +908,14 @@ __global__ __launch_bounds__(64) void attn_decode_combine_kernel(const float* __
   for (int i = 0; i < HD / 64; ++i) op[lane + 64 * i] = f32_to_op(o[i] * inv);
 }
 
-// ------------------------------------------------------------------------------------------------------------------
-// attn_decode_fused_kernel: the whole attention part of one decode step of one layer in ONE launch (q_len == 1):
-//   rotary embedding of the new q and k rows, append of the new k row / v column to the paged tiles, single-query
-//   attention over the cache, combine. Replaces kv_tiles + attn_decode + attn_decode_combine (3 launches, 2 boundaries).
-//   grid (head, sequence), 8 waves per block: wave w owns tiles w, w + 8, ... of its (sequence, head) and streams them
-//   exactly like attn_decode_kernel (K rows by 16-lane groups, V^T rows by 8-lane groups, everything of a tile in
-//   flight at once); the 8 online-softmax partials meet in LDS -- no scratch, no cross-block traffic. One head of one
-//   sequence is <= 1 MiB of K/V^T at 2048 tokens, which one CU streams in a few microseconds.
-//   The wave that owns the LAST tile also owns the new token: it rotates k, scores it from registers, stores the k row
-//   and the v column, and adds p_new * v_new to its accumulators. A tile that STARTS with the new token is zero-filled
-//   around it (same invariant as kv_tiles_kernel: padding rows/columns of a tile are zero, never garbage).
-// ------------------------------------------------------------------------------------------------------------------
 template <int HD, bool ROPE>
 __global__ __launch_bounds__(512) void attn_decode_fused_kernel(
     const bf16_t* __restrict__ qkv, int ldqkv, int q_col0, int k_col0, int v_col0, bf16_t* __restrict__ Kt,
     bf16_t* __restrict__ Vt, const int* __restrict__ tile_table, const VtAttnSeq* __restrict__ seqs, int heads,
     const float* __restrict__ rope_cos, const float* __restrict__ rope_sin, const int* __restrict__ positions,
     float scale_log2e, bf16_t* __restrict__ O, int ldo) {
-  constexpr int NW = 8;
-  constexpr int CH = HD / 8;        // 16-B chunks per K row; CH lanes cooperate on one key
-  constexpr int KPI = 64 / CH;      // keys per wave-instruction
-  constexpr int NACC = HD / 8;      // V^T rows handled per lane
-  __shared__ float sm_m[NW], sm_l[NW];
-  __shared__ float sm_o[NW][HD];
-  __shared__ __attribute__((aligned(16))) float sm_p[NW][64];
-  __shared__ __attribute__((aligned(16))) bf16_t sm_v[HD];
-  const VtAttnSeq sq = seqs[blockIdx.y];
-  const int head = blockIdx.x;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int past = sq.kv_len - 1;
-  const int t_last = past >> 6, r_new = past & 63, ntiles = t_last + 1;
-  const bf16_t* qrow = qkv + (size_t)sq.q_row0 * ldqkv;
-  const int c = lane % CH, ch = c % (CH / 2);
-  const bool upper = c >= CH / 2;
-  constexpr bool rope = ROPE;
-  const int vrow = lane >> 3, vchk = lane & 7;
-  const int key_of_lane = c * KPI + lane / CH;   // the key (inside a tile) whose score this lane ends up owning
-  float m_run = -INFINITY, l_run = 0.f, acc[NACC];
-#pragma unroll
-  for (int i = 0; i < NACC; ++i) acc[i] = 0.f;
-
-  // the whole tile (16 KiB of K + 16 KiB of V^T) is requested before anything is consumed; the first tile's requests go
-  // out before the rotary prologue so that its three dependent look-ups (positions -> tables, q row) overlap the K/V latency
-  u32x4 kk[CH], vv[NACC];
-  auto issue = [&](int t) {
-    const size_t toff = ((size_t)tile_table[sq.table_off + t] * heads + head) * 64 * HD;
-    if (t == t_last && r_new == 0) {   // tile starts with the new token: nothing to read (it is zero-filled below)
-#pragma unroll
-      for (int i = 0; i < CH; ++i) kk[i] = (u32x4){0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int i = 0; i < NACC; ++i) vv[i] = (u32x4){0u, 0u, 0u, 0u};
-    } else {
-#pragma unroll
-      for (int i = 0; i < CH; ++i)
-        kk[i] = __builtin_nontemporal_load((const u32x4*)(Kt + toff + (i * KPI + lane / CH) * HD + c * 8));
-#pragma unroll
-      for (int i = 0; i < NACC; ++i)
-        vv[i] = __builtin_nontemporal_load((const u32x4*)(Vt + toff + (i * 8 + vrow) * 64 + vchk * 8));
-    }
-    return toff;
-  };
-  float cs[8], sn[8];
-  if (rope) {
-    const int rp = positions[sq.q_row0];
-    const float* cp = rope_cos + (size_t)rp * (HD / 2) + ch * 8;
-    const float* sp = rope_sin + (size_t)rp * (HD / 2) + ch * 8;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      cs[j] = cp[j];
-      sn[j] = sp[j];
-    }
-  }
-  // this lane's 16-B chunk c of a head row, rotated (half-split rotary, same arithmetic and bf16 rounding as kv_tiles_kernel)
-  auto rotate = [&](const u32x4 lo, const u32x4 hi) -> u32x4 {
-    u32x4 o;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const float a0 = oplo_to_f32(lo[w]), a1 = ophi_to_f32(lo[w]);
-      const float b0 = oplo_to_f32(hi[w]), b1 = ophi_to_f32(hi[w]);
-      const float c0 = cs[2 * w], c1 = cs[2 * w + 1], s0 = sn[2 * w], s1 = sn[2 * w + 1];
-      o[w] = upper ? pack_op2(rope_hi(a0, b0, c0, s0), rope_hi(a1, b1, c1, s1)) : pack_op2(rope_lo(a0, b0, c0, s0), rope_lo(a1, b1, c1, s1));
-    }
-    return o;
-  };
-  auto head_chunk = [&](const bf16_t* base) -> u32x4 {
-    if (!rope) return *(const u32x4*)(base + c * 8);
-    return rotate(*(const u32x4*)(base + ch * 8), *(const u32x4*)(base + HD / 2 + ch * 8));
-  };
-  // raw q chunk(s) first, then the first tile's 32 requests, then the rotary arithmetic: loads complete in issue order, so
-  // the prologue only ever waits for its own small look-ups while the tile is in flight
-  const bf16_t* qbase = qrow + q_col0 + head * HD;
-  const u32x4 q_lo = *(const u32x4*)(qbase + (rope ? ch : c) * 8);
-  const u32x4 q_hi = *(const u32x4*)(qbase + (rope ? HD / 2 + ch * 8 : c * 8));
-  __builtin_amdgcn_sched_barrier(0);
-  int t = wave;
-  size_t toff = 0;
-  if (t < ntiles) toff = issue(t);
-  __builtin_amdgcn_sched_barrier(0);
-  const u32x4 qv = rope ? rotate(q_lo, q_hi) : q_lo;
-  float qf[8];
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    qf[2 * w] = oplo_to_f32(qv[w]);
-    qf[2 * w + 1] = ophi_to_f32(qv[w]);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-
-  while (t < ntiles) {
-    const bool is_last = t == t_last;
-    const bool fresh = is_last && r_new == 0;
-    bf16_t* kt = Kt + toff;
-    bf16_t* vt = Vt + toff;
-    float part[CH];
-#pragma unroll
-    for (int i = 0; i < CH; ++i) {
-      const u32x4 kv = kk[i];
-      float part_s = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        part_s = fmaf(oplo_to_f32(kv[w]), qf[2 * w], part_s);
-        part_s = fmaf(ophi_to_f32(kv[w]), qf[2 * w + 1], part_s);
-      }
-      part[i] = part_s;
-    }
-    float s_mine = reduce_scatter_lanes<CH>(part, c);   // full score of key_of_lane = c*KPI + lane/CH
-    if (is_last) {
-      // ---- the new token: key r_new of this tile ----
-      const u32x4 kr = head_chunk(qrow + k_col0 + head * HD);
-      float part_s = 0.f;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        part_s = fmaf(oplo_to_f32(kr[w]), qf[2 * w], part_s);
-        part_s = fmaf(ophi_to_f32(kr[w]), qf[2 * w + 1], part_s);
-      }
-      part_s = allreduce_lanes<CH>(part_s);
-      if (key_of_lane == r_new) s_mine = part_s;
-      if (lane < CH) {
-        *(u32x4*)(kt + r_new * HD + lane * 8) = kr;                                       // lane < CH: c == lane
-        const u32x4 vn = *(const u32x4*)(qrow + v_col0 + head * HD + lane * 8);       // bf16 from the projection -> fp16 page format
-        *(u32x4*)(&sm_v[lane * 8]) = (u32x4){op2_to_f16x2(vn.x), op2_to_f16x2(vn.y), op2_to_f16x2(vn.z), op2_to_f16x2(vn.w)};
-      }
-      __builtin_amdgcn_wave_barrier();
-      if (!fresh) {
-#pragma unroll
-        for (int i = 0; i < HD / 64; ++i) vt[(lane + 64 * i) * 64 + r_new] = sm_v[lane + 64 * i];
-      } else {
-        const u32x4 z = {0u, 0u, 0u, 0u};
-        for (int it = lane; it < 63 * CH; it += 64) *(u32x4*)(kt + HD + it * 8) = z;      // K rows 1..63
-        for (int it = lane; it < HD * 8; it += 64) {                                       // V^T: (d, 8-key chunk)
-          const int d = it >> 3, kc = it & 7;
-          u32x4 w = z;
-          if (kc == 0) w.x = sm_v[d];
-          *(u32x4*)(vt + d * 64 + kc * 8) = w;
-        }
-      }
-    }
-    const int mykey = t * 64 + key_of_lane;
-    const float s2 = (mykey < sq.kv_len) ? s_mine * scale_log2e : -INFINITY;
-    const float m_new = fmaxf(m_run, wave_max(s2));
-    const float alpha = fast_exp2(m_run - m_new);
-    const float p = fast_exp2(s2 - m_new);
-    l_run = l_run * alpha + wave_sum(p);
-    m_run = m_new;
-    sm_p[wave][key_of_lane] = p;
-    __builtin_amdgcn_wave_barrier();  // DS ops of one wave are in order; only stop compiler reordering
-    float p_new = 0.f;
-    if (is_last) {
-      // the new token's value comes from sm_v below, never from the loaded tile: its weight is taken out of the tile's row of
-      // probabilities, so a column r_new that already holds a value (a step that was rolled back and is run again) is not
-      // counted twice and the kernel is idempotent
-      p_new = sm_p[wave][r_new];
-      __builtin_amdgcn_wave_barrier();
-      if (key_of_lane == r_new) sm_p[wave][r_new] = 0.f;
-      __builtin_amdgcn_wave_barrier();
-    }
-    const f32x4 pa = *(const f32x4*)(&sm_p[wave][vchk * 8]);
-    const f32x4 pb = *(const f32x4*)(&sm_p[wave][vchk * 8 + 4]);
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int i = 0; i < NACC; ++i) {
-      float a = acc[i] * alpha;
-      a = fmaf(f16lo_to_f32(vv[i][0]), pa[0], a);
-      a = fmaf(f16hi_to_f32(vv[i][0]), pa[1], a);
-      a = fmaf(f16lo_to_f32(vv[i][1]), pa[2], a);
-      a = fmaf(f16hi_to_f32(vv[i][1]), pa[3], a);
-      a = fmaf(f16lo_to_f32(vv[i][2]), pb[0], a);
-      a = fmaf(f16hi_to_f32(vv[i][2]), pb[1], a);
-      a = fmaf(f16lo_to_f32(vv[i][3]), pb[2], a);
-      a = fmaf(f16hi_to_f32(vv[i][3]), pb[3], a);
-      acc[i] = a;
-    }
-    if (is_last && vchk == 0) {   // column r_new of the loaded tile carries no weight (see above): add the new value here
-#pragma unroll
-      for (int i = 0; i < NACC; ++i) acc[i] = fmaf(f16_bits_to_f32(sm_v[i * 8 + vrow]), p_new, acc[i]);
-    }
-    t += NW;
-    if (t < ntiles) toff = issue(t);
-  }
-  // reduce the 8 lanes of every V^T row, then combine the waves through LDS
-#pragma unroll
-  for (int i = 0; i < NACC; ++i) {
-    float a = acc[i];
-    a += __shfl_xor(a, 1, 64);
-    a += __shfl_xor(a, 2, 64);
-    a += __shfl_xor(a, 4, 64);
-    if (vchk == 0) sm_o[wave][i * 8 + vrow] = a;
-  }
-  if (lane == 0) {
-    sm_m[wave] = m_run;
-    sm_l[wave] = l_run;
-  }
-  __syncthreads();
-  if (threadIdx.x < HD) {
-    float m = sm_m[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) m = fmaxf(m, sm_m[w]);
-    float l = 0.f, o = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      const float wt = (sm_m[w] == -INFINITY) ? 0.f : fast_exp2(sm_m[w] - m);
-      l += sm_l[w] * wt;
-      o += sm_o[w][threadIdx.x] * wt;
-    }
-    O[(size_t)sq.q_row0 * ldo + head * HD + threadIdx.x] = f32_to_op(l > 0.f ? o / l : 0.f);
-  }
+  attn_decode_fused_body<DecodePages16, HD, ROPE>(qkv, ldqkv, q_col0, k_col0, v_col0, Kt, Vt, tile_table, seqs, heads, rope_cos,
+                                                  rope_sin, positions, scale_log2e, O, ldo);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1642,11 +1303,20 @@ int vt_flash_attn_precise_launch(const bf16_t* Q, int ldq, const bf16_t* Qlo, in
   return VT_OK;
 }
 
+// splits of the split-KV decode kernels: one per 4 tiles (a block's 4 waves take one tile each per round), at most 32
+int vt_attn_decode_nsplit(int max_kv_len) {
+  const int nsplit = ((max_kv_len + 63) / 64 + 3) / 4;
+  return nsplit < 1 ? 1 : (nsplit > 32 ? 32 : nsplit);
+}
+
 size_t vt_attn_decode_scratch_bytes(int nseq, int heads, int HD, int max_kv_len) {
-  const int ntiles = (max_kv_len + 63) / 64;
-  int nsplit = (ntiles + 3) / 4;
-  nsplit = nsplit < 1 ? 1 : (nsplit > 32 ? 32 : nsplit);
-  return (size_t)nseq * heads * nsplit * (HD + 2) * sizeof(float);
+  return (size_t)nseq * heads * vt_attn_decode_nsplit(max_kv_len) * (HD + 2) * sizeof(float);
+}
+
+void vt_attn_decode_combine_launch(const float* scratch, const VtAttnSeq* seqs, int nseq, bf16_t* O, int ldo, int heads, int HD,
+                                   int nsplit, hipStream_t s) {
+  if (HD == 64) hipLaunchKernelGGL((attn_decode_combine_kernel<64>), dim3(heads, nseq), dim3(64), 0, s, scratch, seqs, O, ldo, heads, nsplit);
+  else hipLaunchKernelGGL((attn_decode_combine_kernel<128>), dim3(heads, nseq), dim3(64), 0, s, scratch, seqs, O, ldo, heads, nsplit);
 }
 
 int vt_attn_decode_launch(const bf16_t* Q, int ldq, const bf16_t* Kt, const bf16_t* Vt, const int* tile_table,
@@ -1655,10 +1325,8 @@ int vt_attn_decode_launch(const bf16_t* Q, int ldq, const bf16_t* Kt, const bf16
   VT_REQUIRE(Q && Kt && Vt && tile_table && seqs && O && scratch, "vt_attn_decode: null pointer");
   VT_REQUIRE(HD == 64 || HD == 128, "vt_attn_decode: head_dim %d unsupported", HD);
   VT_REQUIRE(max_kv_len > 0, "vt_attn_decode: max_kv_len must be > 0");
-  const int ntiles = (max_kv_len + 63) / 64;
-  int nsplit = (ntiles + 3) / 4;
-  nsplit = nsplit < 1 ? 1 : (nsplit > 32 ? 32 : nsplit);
-  const size_t need = (size_t)nseq * heads * nsplit * (HD + 2) * sizeof(float);
+  const int nsplit = vt_attn_decode_nsplit(max_kv_len);
+  const size_t need = vt_attn_decode_scratch_bytes(nseq, heads, HD, max_kv_len);
   if (scratch_bytes < need) {
     vt_set_error("vt_attn_decode: scratch too small (%zu < %zu)", scratch_bytes, need);
     return VT_ERR_WORKSPACE;
@@ -1666,13 +1334,9 @@ int vt_attn_decode_launch(const bf16_t* Q, int ldq, const bf16_t* Kt, const bf16
   const float sl2 = scale * 1.4426950408889634f;
   VtProfScope prof(VT_PROF_ATTN_DECODE, 0.0, s);
   dim3 grid(heads, nseq, nsplit), block(256);
-  if (HD == 64) {
-    hipLaunchKernelGGL((attn_decode_kernel<64>), grid, block, 0, s, Q, ldq, Kt, Vt, tile_table, seqs, heads, sl2, scratch, nsplit);
-    hipLaunchKernelGGL((attn_decode_combine_kernel<64>), dim3(heads, nseq), dim3(64), 0, s, scratch, seqs, O, ldo, heads, nsplit);
-  } else {
-    hipLaunchKernelGGL((attn_decode_kernel<128>), grid, block, 0, s, Q, ldq, Kt, Vt, tile_table, seqs, heads, sl2, scratch, nsplit);
-    hipLaunchKernelGGL((attn_decode_combine_kernel<128>), dim3(heads, nseq), dim3(64), 0, s, scratch, seqs, O, ldo, heads, nsplit);
-  }
+  if (HD == 64) hipLaunchKernelGGL((attn_decode_kernel<64>), grid, block, 0, s, Q, ldq, Kt, Vt, tile_table, seqs, heads, sl2, scratch, nsplit);
+  else hipLaunchKernelGGL((attn_decode_kernel<128>), grid, block, 0, s, Q, ldq, Kt, Vt, tile_table, seqs, heads, sl2, scratch, nsplit);
+  vt_attn_decode_combine_launch(scratch, seqs, nseq, O, ldo, heads, HD, nsplit, s);
   VT_LAUNCH_CHECK();
   return VT_OK;
 }

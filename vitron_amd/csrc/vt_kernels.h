@@ -180,7 +180,12 @@ int vt_kv_tiles_precise_launch(const float* qk32, int ld32, int v_f32, bf16_t* q
 int vt_flash_attn_precise_launch(const bf16_t* Q, int ldq, const bf16_t* Qlo, int ldqlo, const bf16_t* Kt, const bf16_t* Klo,
                                  int klo_tiles_per_seq, const bf16_t* Vt, const int* tile_table, const VtAttnSeq* seqs, int nseq,
                                  int max_q_len, bf16_t* O, int ldo, bf16_t* Olo, int heads, int HD, int causal, float scale, hipStream_t s);
+// the split-KV decode kernels of both page formats: split count for a longest context, the scratch it needs ([sequence][head][split]
+// [2 + HD] fp32 partials), and the format-free merge of the splits into O (launched after attn_decode_kernel / attn_decode_kv8_kernel)
+int vt_attn_decode_nsplit(int max_kv_len);
 size_t vt_attn_decode_scratch_bytes(int nseq, int heads, int HD, int max_kv_len);
+void vt_attn_decode_combine_launch(const float* scratch, const VtAttnSeq* seqs, int nseq, bf16_t* O, int ldo, int heads, int HD,
+                                   int nsplit, hipStream_t s);
 int vt_attn_decode_fused_launch(const bf16_t* qkv, int ldqkv, int q_col0, int k_col0, int v_col0, bf16_t* Kt, bf16_t* Vt,
                                 const int* tile_table, const VtAttnSeq* seqs, int nseq, bf16_t* O, int ldo, int heads, int HD,
                                 float scale, const float* rope_cos, const float* rope_sin, const int* positions, hipStream_t s);
