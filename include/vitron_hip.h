@@ -86,6 +86,8 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
  * a struct changes or a function gains a parameter. */
 /* 114 also carries the folded-norm unit entry points vt_gemm_bf16_norm, vt_gemm_bf16_resid_norm and vt_rowscale_finalize WITHOUT a bump:
  * three new symbols that forward to launches vt_llama_forward already makes; no struct and no existing signature changes. */
+/* 114 also carries vt_sample_rows and struct vt_sample_row WITHOUT a bump: one new symbol and one new struct; vt_sample_top_p and
+ * vt_argmax keep their signatures and return what they returned, bit for bit. */
 #define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
@@ -331,6 +333,44 @@ int vt_cross_entropy(const float* logits, int rows, int V, int ldl, const int* l
  * Replaces GenerationMixin.sample's temperature / top-k / top-p / multinomial step (reference app.py:562-571, do_sample=True). */
 int vt_sample_top_p(const float* logits, int rows, int V, int ldl, float temperature, int top_k, float top_p, uint64_t seed,
                     uint64_t step, int* out_ids, int* kept_count, void* stream);
+
+/* One token per row with PER-ROW parameters, one launch: greedy and sampled rows, rows of different requests, in one batch.
+ * params: DEVICE array of `rows` vt_sample_row (48 bytes each, 8-byte aligned; the offsets are part of the ABI):
+ *    0 float    temperature         > 0 samples (TemperatureLogitsWarper); 0 -- anything not > 0 -- is a greedy row
+ *    4 float    top_p               TopPLogitsWarper; >= 1 keeps all
+ *    8 int32    top_k               TopKLogitsWarper; <= 0 is off
+ *   12 float    repetition_penalty  RepetitionPenaltyLogitsProcessor; 1 is off
+ *   16 uint64   seed                \
+ *   24 uint64   counter              > the uniform is splitmix64(seed ^ splitmix64(counter * 0x632be59bd9b4e019 + stream)): the roles of
+ *   44 uint32   stream              /  vt_sample_top_p's (seed, step, row index), so its draw can be reproduced from any batch position
+ *   32 const int* history           DEVICE token ids the penalty applies to (may be NULL)
+ *   40 int32    history_len         <= 0: no history
+ * Per row, in transformers' order (LogitsProcessorList, then the warpers of GenerationMixin.sample, 4.31):
+ *   1. penalty: every DISTINCT id of history with 0 <= id < V:  x = x < 0 ? x * penalty : x / penalty  (fp32, correctly rounded divide:
+ *      torch's fp32 result bit for bit). Ids outside [0, V) -- the negative image / region sentinels of a multimodal prompt, ids of a
+ *      larger vocabulary -- are skipped and index nothing.
+ *   2. greedy row: out_ids = first index of the maximum of the penalised row (vt_argmax's answer on that row), kept_count = 1.
+ *      sampled row: exactly vt_sample_top_p's arithmetic on the penalised row with the row's temperature, top_k, top_p and uniform.
+ *   3. logprob (optional) = raw[id] - (max(raw) + logf(sum expf(raw - max))) over the RAW row (before penalty and temperature): the
+ *      chosen token's log_softmax, without a [rows][V] copy to the host.
+ * The kernel is total: no field value leads to an out-of-bounds access (history must be readable for history_len ints when both are set).
+ * kept_count, logprob: optional [rows]. V <= 32768 with 16-byte aligned rows runs with the row in registers; anything else streams the row
+ * and needs V <= VT_SAMPLE_ROWS_MAX_V (its V-bit history mask lives in LDS); a larger V is refused with a message.
+ * 114 carries this entry point WITHOUT a bump: one new symbol and one new struct, nothing existing changes (see the note at VT_ABI_VERSION). */
+#define VT_SAMPLE_ROWS_MAX_V 262144
+typedef struct vt_sample_row {
+  float temperature;
+  float top_p;
+  int32_t top_k;
+  float repetition_penalty;
+  uint64_t seed;
+  uint64_t counter;
+  const int* history;
+  int32_t history_len;
+  uint32_t stream;
+} vt_sample_row;
+int vt_sample_rows(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, int* out_ids, int* kept_count,
+                   float* logprob, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * mm_projector: Linear(Din,Dh) -> GELU(erf) -> Linear(Dh,Dout)   ('mlp2x_gelu';  w2 == NULL -> 'linear')

@@ -1,25 +1,97 @@
-"""Times vt_argmax and vt_sample_top_p on decode-sized logits ([4, 32000] fp32)."""
+"""Times vt_argmax, vt_sample_top_p and vt_sample_rows on decode-sized logits ([rows, 32000] fp32).
+
+vt_sample_rows runs all-sampled, all-greedy and mixed batches (even rows greedy), each without a history and with a 2048-id history under
+a repetition penalty of 1.3, and all-sampled with the log-probability output. The arms are alternated inside one process over `--rounds`
+rounds of `--iters` launches between two device events; per arm the output gives every round, the median and the spread
+(max - min) / median -- two arms are apart only when they differ by more than the spreads. `--baseline-lib PATH` adds vt_argmax and
+vt_sample_top_p of ANOTHER build of libvitron_hip.so (for instance the parent commit's) to the same alternation. `--json FILE` writes the
+table (profiles/sampler_rows_bench.json).
+
+  python tools/sampler_bench.py [--rows 4,16] [--iters 200] [--rounds 3] [--baseline-lib path/libvitron_hip.so] [--json out.json]
+"""
+import argparse
+import ctypes as C
+import json
 import os
+import statistics
 import sys
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vitron_amd import _lib, ops  # noqa: E402
+from vitron_amd.sampling import pack_sample_rows  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--rows", default="1,4,16")
+ap.add_argument("--iters", type=int, default=200)
+ap.add_argument("--rounds", type=int, default=3)
+ap.add_argument("--baseline-lib", default=None)
+ap.add_argument("--json", default=None)
+args = ap.parse_args()
 
 _lib.load()
 dev = torch.device("cuda:0")
-for rows in (1, 4, 16):
-    lg = torch.randn((rows, 32000), device=dev) * 3
-    for name, fn in (("argmax", lambda: ops.argmax(lg)), ("top_p 0.7", lambda: ops.sample_top_p(lg, 0.2, 0.7, 1, 2)),
-                     ("top_p 1.0", lambda: ops.sample_top_p(lg, 1.0, 1.0, 1, 2))):
-        for _ in range(3):
-            fn()
-        torch.cuda.synchronize()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(50):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        print(f"rows={rows:2d} {name:10s} {a.elapsed_time(b) / 50 * 1e3:8.1f} us")
+V, T, P, SEED, STEP, HIST = 32000, 0.2, 0.7, 1, 2, 2048
+base = None
+if args.baseline_lib:
+    base = C.CDLL(os.path.abspath(args.baseline_lib))
+    base.vt_argmax.argtypes = _lib.SIGNATURES["vt_argmax"][1]
+    base.vt_sample_top_p.argtypes = _lib.SIGNATURES["vt_sample_top_p"][1]
+
+
+def time_us(fn):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(args.iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / args.iters * 1e3
+
+
+result = {"V": V, "iters": args.iters, "rounds": args.rounds, "temperature": T, "top_p": P, "history_ids": HIST, "penalty": 1.3,
+          "baseline_lib": bool(base), "device": torch.cuda.get_device_name(0), "shapes": {}}
+for rows in [int(r) for r in args.rows.split(",")]:
+    lg = torch.randn((rows, V), device=dev) * 3
+    out = torch.empty((rows,), dtype=torch.int32, device=dev)
+    hist = torch.randint(0, V, (rows, HIST), dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def params(kind, with_hist):
+        rs = []
+        for r in range(rows):
+            greedy = kind == "greedy" or (kind == "mixed" and r % 2 == 0)
+            rs.append((0.0 if greedy else T, 0, P, 1.3 if with_hist else 1.0, SEED, STEP, r,
+                       hist[r].data_ptr() if with_hist else 0, HIST if with_hist else 0))
+        return pack_sample_rows(rs, dev)
+
+    arms = {"argmax": lambda: ops.argmax(lg), "top_p 0.7": lambda: ops.sample_top_p(lg, T, P, SEED, STEP),
+            "top_p 1.0": lambda: ops.sample_top_p(lg, 1.0, 1.0, SEED, STEP)}
+    if base is not None:
+        arms["baseline argmax"] = lambda: base.vt_argmax(lg.data_ptr(), rows, V, V, out.data_ptr(), stream)
+        arms["baseline top_p 0.7"] = lambda: base.vt_sample_top_p(lg.data_ptr(), rows, V, V, T, 0, P, SEED, STEP, out.data_ptr(), None, stream)
+    for kind in ("sampled", "greedy", "mixed"):
+        for with_hist in (False, True):
+            pr = params(kind, with_hist)
+            arms[f"rows {kind}" + (" +hist" if with_hist else "")] = lambda pr=pr: ops.sample_rows(lg, pr)
+    pr_lp = params("sampled", False)
+    arms["rows sampled +logprob"] = lambda: ops.sample_rows(lg, pr_lp, return_logprob=True)
+    assert torch.equal(ops.sample_rows(lg, params("sampled", False)), ops.sample_top_p(lg, T, P, SEED, STEP))      # the same draw
+    times = {name: [] for name in arms}
+    for _ in range(args.rounds):
+        for name, fn in arms.items():
+            times[name].append(time_us(fn))
+    shape = {}
+    for name, ts in times.items():
+        med = statistics.median(ts)
+        shape[name] = {"us": [round(t, 2) for t in ts], "median_us": round(med, 2), "spread": round((max(ts) - min(ts)) / med, 4)}
+        print(f"rows={rows:2d} {name:22s} {med:8.1f} us   rounds {[f'{t:.1f}' for t in ts]}  spread {shape[name]['spread']:.3f}")
+    result["shapes"][f"{rows}x{V}"] = shape
+if args.json:
+    with open(args.json, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")

@@ -447,6 +447,11 @@ int vt_sample_top_p(const float* logits, int rows, int V, int ldl, float tempera
   return vt_sample_top_p_launch(logits, rows, V, ldl, temperature, top_k, top_p, seed, step, out_ids, kept_count, S(stream));
 }
 
+int vt_sample_rows(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, int* out_ids, int* kept_count,
+                   float* logprob, void* stream) {
+  return vt_sample_rows_launch(logits, rows, V, ldl, params, out_ids, kept_count, logprob, S(stream));
+}
+
 // ---- mm_projector ---------------------------------------------------------------------------------------------------
 size_t vt_projector_workspace_bytes(int M, int Dh) { return align_up((size_t)M * Dh * 2, 256) + 256; }
 

@@ -1,4 +1,5 @@
-// vt_llama.hip -- small kernels around the decoder: embedding gather + multimodal splice, greedy argmax.
+// vt_llama.hip -- small kernels around the decoder: embedding gather + multimodal splice, greedy argmax, the samplers
+// (vt_sample_top_p with launch-uniform parameters, vt_sample_rows with per-row ones: two bodies written once), cross entropy.
 //
 // embed_splice replaces the tensor surgery of prepare_inputs_labels_for_multimodal in the reference
 // (vitron/model/llava_arch.py:306-398 region branch, :479-558 plain branch): embed_tokens gather for text
@@ -60,6 +61,32 @@ __global__ __launch_bounds__(256) void decode_feed_kernel(const bf16_t* __restri
   for (int c = threadIdx.x; c < (H >> 3); c += 256) *(u32x4*)(dst + c * 8) = *(const u32x4*)(src + c * 8);
 }
 
+// first-index arg-max bookkeeping of the greedy rows of vt_sample_rows, argmax_kernel's rule: (value, index) pairs ordered by larger
+// value, then lower index; a NaN is never taken.
+__device__ __forceinline__ void argmax_take(float& best, int& bi, float v, int i) {
+  if (v > best || (v == best && i < bi)) {
+    best = v;
+    bi = i;
+  }
+}
+// block-wide result in thread 0 (1024 threads); sv / si: 16 LDS slots each
+__device__ __forceinline__ void block_argmax_1024(float& best, int& bi, float* sv, int* si) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    argmax_take(best, bi, ov, oi);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    sv[wave] = best;
+    si[wave] = bi;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int w = 1; w < 16; ++w) argmax_take(best, bi, sv[w], si[w]);
+}
+
 // first index of the maximum of each row (torch.argmax tie rule on CPU: lowest index). 1024 threads per row, 16-B loads,
 // every request of the row in flight at once (a 32000-float row is 8 loads per thread).
 __global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ logits, int V, int ldl,
@@ -109,6 +136,10 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ 
 //   found by bisection on the probability threshold instead of a sort; then inverse-CDF sampling over the kept tokens in
 //   index order with a counter-based uniform (splitmix64 of seed, step, row). One 1024-thread block per row.
 // Replaces GenerationMixin.sample's warper + torch.multinomial (app.py:562-571 passes do_sample=True, temperature, top_p).
+// The rule is written ONCE, as two __device__ bodies that read one row's parameters from a SampleArgs (sample_reg_body: the row in
+// registers; sample_stream_body: any V). The vt_sample_top_p kernels fill SampleArgs from their launch-uniform scalars, the
+// vt_sample_rows kernels from the row's vt_sample_row; their kRows instantiation adds the repetition penalty
+// (RepetitionPenaltyLogitsProcessor), greedy rows and the chosen token's log-probability.
 // ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float block_sum_1024(float v, float* sh) {
   v = wave_sum(v);
@@ -141,17 +172,95 @@ __device__ __forceinline__ uint32_t order_key(float x) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// One row's sampling parameters as the two sampler bodies read them. vt_sample_top_p fills it from its launch-uniform scalars
+// (stream = blockIdx.x: today's draw), vt_sample_rows from the row's vt_sample_row.
+struct SampleArgs {
+  float inv_temp;
+  int top_k;
+  float top_p;
+  uint64_t seed, counter;
+  uint32_t stream;
+  bool greedy;            // first index of the maximum instead of a draw (kRows bodies only)
+  float penalty;          // RepetitionPenaltyLogitsProcessor factor; applied to the ids of history[0..history_len) (kRows only)
+  const int* history;
+  int history_len;
+};
+__device__ __forceinline__ float sample_uniform24(const SampleArgs& a) {   // (0, 1): 24 bits of splitmix64(seed, counter, stream), centred
+  const uint64_t r = splitmix64(a.seed ^ splitmix64(a.counter * 0x632be59bd9b4e019ull + a.stream));
+  return (float)((r >> 40) + 0.5) * (1.0f / 16777216.0f);
+}
+// RepetitionPenaltyLogitsProcessor on one logit (transformers 4.31: torch.where(score < 0, score * penalty, score / penalty)), fp32 with
+// the correctly rounded divide: torch's fp32 result bit for bit
+__device__ __forceinline__ float penalise(float x, float penalty) { return x < 0.f ? x * penalty : __fdiv_rn(x, penalty); }
+
+// V-bit "seen" mask of the row's history in LDS: bit id is set for every history id in [0, V). Ids outside that range (the negative
+// image / region sentinels of a multimodal prompt, anything >= V) are skipped and index nothing. Returns whether a penalty applies.
+__device__ __forceinline__ bool fill_seen_mask(uint32_t* seen, int V, const SampleArgs& a) {
+  if (!(a.history && a.history_len > 0) || a.penalty == 1.0f) return false;     // (block-uniform: the barriers below are safe)
+  const int words = (V + 31) >> 5;
+  for (int w = threadIdx.x; w < words; w += 1024) seen[w] = 0u;
+  __syncthreads();
+  for (int h = threadIdx.x; h < a.history_len; h += 1024) {
+    const int id = a.history[h];
+    if (id >= 0 && id < V) atomicOr(&seen[id >> 5], 1u << (id & 31));
+  }
+  __syncthreads();
+  return true;
+}
+
 // TopKLogitsWarper (transformers 4.31: scores < topk(scores, k)[..., -1] are removed, ties with the k-th value stay): the
 // k-th largest scaled logit is found exactly by bisection on the ordered bit pattern (32 counting passes), no sort.
-__global__ __launch_bounds__(1024) void sample_top_p_kernel(const float* __restrict__ logits, int V, int ldl,
-                                                            float inv_temp, int top_k, float top_p, uint64_t seed, uint64_t step,
-                                                            int* __restrict__ out_ids, int* __restrict__ kept_count) {
+//
+// Streaming form of the sampler, any V: the row is re-read from memory (L2) in every pass. kRows adds what vt_sample_rows needs on
+// top of vt_sample_top_p's arithmetic -- the repetition penalty (through `seen`, ceil(V/32) words of LDS), greedy rows and the
+// log-probability of the chosen token -- and compiles to nothing in the launch-uniform kernel.
+template <bool kRows>
+__device__ __forceinline__ void sample_stream_body(const float* __restrict__ row, int V, const SampleArgs& a, uint32_t* seen,
+                                                   int* __restrict__ out_id, int* __restrict__ kept_out, float* __restrict__ logprob) {
   __shared__ float sh[16];
   __shared__ float sh_scan[16];
-  const float* row = logits + (size_t)blockIdx.x * ldl;
+  __shared__ int chosen;
   const int tid = threadIdx.x;
+  const float inv_temp = a.inv_temp, top_p = a.top_p;
+  const int top_k = a.top_k;
+  float lse = 0.f;
+  bool pen = false;
+  if constexpr (kRows) {
+    if (logprob) {       // log-sum-exp of the RAW row (before penalty and temperature), expf / logf as cross_entropy_rows_kernel
+      float rmx = -INFINITY;
+      for (int i = tid; i < V; i += 1024) rmx = fmaxf(rmx, row[i]);
+      rmx = block_max_1024(rmx, sh);
+      float rz = 0.f;
+      for (int i = tid; i < V; i += 1024) rz += expf(row[i] - rmx);
+      rz = block_sum_1024(rz, sh);
+      lse = rmx + logf(rz);
+    }
+    pen = fill_seen_mask(seen, V, a);
+  }
+  auto val = [&](int i) -> float {     // the (penalised) logit i
+    float x = row[i];
+    if constexpr (kRows)
+      if (pen && ((seen[i >> 5] >> (i & 31)) & 1u)) x = penalise(x, a.penalty);
+    return x;
+  };
+  if constexpr (kRows) {
+    if (a.greedy) {      // block-uniform
+      __shared__ int si[16];
+      float best = -INFINITY;
+      int bi = 0x7fffffff;
+      for (int i = tid; i < V; i += 1024) argmax_take(best, bi, val(i), i);
+      __syncthreads();
+      block_argmax_1024(best, bi, sh, si);
+      if (tid == 0) {
+        *out_id = bi;
+        if (kept_out) *kept_out = 1;
+        if (logprob) *logprob = (unsigned)bi < (unsigned)V ? row[bi] - lse : NAN;
+      }
+      return;
+    }
+  }
   float mx = -INFINITY;
-  for (int i = tid; i < V; i += 1024) mx = fmaxf(mx, row[i] * inv_temp);
+  for (int i = tid; i < V; i += 1024) mx = fmaxf(mx, val(i) * inv_temp);
   mx = block_max_1024(mx, sh);
   float floor_logit = -INFINITY;   // scaled logits below this are outside the top-k set
   if (top_k > 0 && top_k < V) {
@@ -159,14 +268,14 @@ __global__ __launch_bounds__(1024) void sample_top_p_kernel(const float* __restr
     for (int it = 0; it < 32; ++it) {
       const uint64_t mid = lo + ((hi - lo) >> 1);
       float c = 0.f;
-      for (int i = tid; i < V; i += 1024) c += ((uint64_t)order_key(row[i] * inv_temp) >= mid) ? 1.f : 0.f;
+      for (int i = tid; i < V; i += 1024) c += ((uint64_t)order_key(val(i) * inv_temp) >= mid) ? 1.f : 0.f;
       c = block_sum_1024(c, sh);
       if (c >= (float)top_k) lo = mid; else hi = mid;
     }
     const uint32_t k32 = (uint32_t)lo;
     floor_logit = __uint_as_float((k32 & 0x80000000u) ? (k32 & 0x7fffffffu) : ~k32);
   }
-#define VT_P_OF(i) ((row[i] * inv_temp >= floor_logit) ? __expf(row[i] * inv_temp - mx) : 0.f)
+#define VT_P_OF(i) ((val(i) * inv_temp >= floor_logit) ? __expf(val(i) * inv_temp - mx) : 0.f)
   float z = 0.f;
   for (int i = tid; i < V; i += 1024) z += VT_P_OF(i);
   z = block_sum_1024(z, sh);
@@ -188,23 +297,22 @@ __global__ __launch_bounds__(1024) void sample_top_p_kernel(const float* __restr
   float kept = 0.f, cnt = 0.f;
   for (int i = tid; i < V; i += 1024) {
     const float p = VT_P_OF(i) * inv_z;
-    if (p >= thr && row[i] * inv_temp >= floor_logit) {      // (thr == 0 at top_p >= 1: the top-k filter still applies)
+    if (p >= thr && val(i) * inv_temp >= floor_logit) {      // (thr == 0 at top_p >= 1: the top-k filter still applies)
       kept += p;
       cnt += 1.f;
     }
   }
   kept = block_sum_1024(kept, sh);
   cnt = block_sum_1024(cnt, sh);
-  if (tid == 0 && kept_count) kept_count[blockIdx.x] = (int)cnt;
+  if (tid == 0 && kept_out) *kept_out = (int)cnt;
   // inverse CDF over the kept tokens in index order: thread t owns the contiguous index range [t*chunk, (t+1)*chunk)
-  const uint64_t r = splitmix64(seed ^ splitmix64(step * 0x632be59bd9b4e019ull + blockIdx.x));
-  const float u = (float)((r >> 40) + 0.5) * (1.0f / 16777216.0f) * kept;
+  const float u = sample_uniform24(a) * kept;
   const int chunk = (V + 1023) / 1024;
   const int i0 = tid * chunk, i1 = min(V, i0 + chunk);
   float mine = 0.f;
   for (int i = i0; i < i1; ++i) {
     const float p = VT_P_OF(i) * inv_z;
-    if (p >= thr && row[i] * inv_temp >= floor_logit) mine += p;
+    if (p >= thr && val(i) * inv_temp >= floor_logit) mine += p;
   }
   // exclusive prefix over threads: wave scan + scan of the 16 wave totals
   float incl = mine;
@@ -220,7 +328,6 @@ __global__ __launch_bounds__(1024) void sample_top_p_kernel(const float* __restr
   for (int w = 0; w < (tid >> 6); ++w) base += sh_scan[w];
   const float excl = base + incl - mine;
   // the owner of u is the thread with excl <= u < excl + mine; fall back to the last kept token against rounding
-  __shared__ int chosen;
   if (tid == 0) chosen = -1;
   __syncthreads();
   if (mine > 0.f && u >= excl && u < excl + mine) {
@@ -228,7 +335,7 @@ __global__ __launch_bounds__(1024) void sample_top_p_kernel(const float* __restr
     int pick = -1;
     for (int i = i0; i < i1; ++i) {
       const float p = VT_P_OF(i) * inv_z;
-      if (p >= thr && row[i] * inv_temp >= floor_logit) {
+      if (p >= thr && val(i) * inv_temp >= floor_logit) {
         pick = i;
         c += p;
         if (u < c) break;
@@ -240,29 +347,36 @@ __global__ __launch_bounds__(1024) void sample_top_p_kernel(const float* __restr
   if (chosen < 0 && mine > 0.f) {  // u landed on a rounding seam: take the last kept token of the highest owning range
     int last = -1;
     for (int i = i0; i < i1; ++i)
-      if (VT_P_OF(i) * inv_z >= thr && row[i] * inv_temp >= floor_logit) last = i;
+      if (VT_P_OF(i) * inv_z >= thr && val(i) * inv_temp >= floor_logit) last = i;
     atomicMax(&chosen, last);
   }
   __syncthreads();
-  if (tid == 0) out_ids[blockIdx.x] = chosen;
+  if (tid == 0) {
+    const int id = chosen;
+    *out_id = id;
+    if constexpr (kRows)
+      if (logprob) *logprob = (unsigned)id < (unsigned)V ? row[id] - lse : NAN;
+  }
 }
 #undef VT_P_OF
 
 // Same rule with the row held in registers (V <= 32 * 1024): every thread owns 32 consecutive logits, computes their
 // exponentials ONCE, and the 30 bisection passes, the kept-mass pass and the inverse-CDF walk never touch memory again.
 // 165 us -> ~20 us per call at V = 32000 (tools/sampler_bench.py).
-__global__ __launch_bounds__(1024) void sample_top_p_reg_kernel(const float* __restrict__ logits, int V, int ldl,
-                                                                float inv_temp, int top_k, float top_p, uint64_t seed, uint64_t step,
-                                                                int* __restrict__ out_ids, int* __restrict__ kept_count) {
+// kRows: thread t's 32 logits are exactly word t of the seen mask, so the penalty is one LDS word per thread and a static unroll
+// (no dynamic register index, no scratch).
+template <bool kRows>
+__device__ __forceinline__ void sample_reg_body(const float* __restrict__ row, int V, const SampleArgs& a, uint32_t* seen,
+                                                int* __restrict__ out_id, int* __restrict__ kept_out, float* __restrict__ logprob) {
   constexpr int NPT = 32;
   __shared__ float sh[2][16];
   __shared__ float sh_scan[16];
   __shared__ int chosen;
-  const float* row = logits + (size_t)blockIdx.x * ldl;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i0 = tid * NPT;
+  const float inv_temp = a.inv_temp, top_p = a.top_p;
+  const int top_k = a.top_k;
   float p[NPT];
-  float mx = -INFINITY;
 #pragma unroll
   for (int j = 0; j < NPT; j += 4) {
     f32x4 v = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
@@ -274,10 +388,7 @@ __global__ __launch_bounds__(1024) void sample_top_p_reg_kernel(const float* __r
         if (i0 + j + k < V) v[k] = row[i0 + j + k];
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      p[j + k] = v[k] * inv_temp;
-      mx = fmaxf(mx, p[j + k]);
-    }
+    for (int k = 0; k < 4; ++k) p[j + k] = v[k];
   }
   int buf = 0;
   auto block_sum = [&](float v) -> float {   // one barrier per call: two alternating LDS rows
@@ -290,33 +401,83 @@ __global__ __launch_bounds__(1024) void sample_top_p_reg_kernel(const float* __r
     buf ^= 1;
     return t;
   };
-  {
-    mx = wave_max(mx);
-    if (lane == 0) sh[buf][wave] = mx;
+  auto block_max = [&](float v) -> float {
+    v = wave_max(v);
+    if (lane == 0) sh[buf][wave] = v;
     __syncthreads();
     float t = sh[buf][0];
 #pragma unroll
     for (int i = 1; i < 16; ++i) t = fmaxf(t, sh[buf][i]);
-    mx = t;
     buf ^= 1;
+    return t;
+  };
+  __shared__ float lse;    // (kRows; in LDS, not in a register that would live across the whole body: only thread 0 reads it back)
+  if constexpr (kRows) {
+    if (logprob) {       // log-sum-exp of the RAW row (before penalty and temperature), expf / logf as cross_entropy_rows_kernel
+      float rmx = -INFINITY;
+#pragma unroll
+      for (int j = 0; j < NPT; ++j) rmx = fmaxf(rmx, p[j]);
+      rmx = block_max(rmx);
+      float rz = 0.f;
+#pragma unroll
+      for (int j = 0; j < NPT; ++j) rz += expf(p[j] - rmx);     // exp(-inf) = 0 for the slots past V
+      rz = block_sum(rz);
+      if (tid == 0) lse = rmx + logf(rz);
+    }
+    if (fill_seen_mask(seen, V, a)) {
+      const uint32_t word = seen[tid];
+#pragma unroll
+      for (int j = 0; j < NPT; ++j)
+        if ((word >> j) & 1u) p[j] = penalise(p[j], a.penalty);
+    }
+    if (a.greedy) {      // block-uniform
+      __shared__ int si[16];
+      float best = -INFINITY;
+      int bi = 0x7fffffff;
+#pragma unroll
+      for (int j = 0; j < NPT; ++j)
+        if (i0 + j < V) argmax_take(best, bi, p[j], i0 + j);
+      __syncthreads();
+      block_argmax_1024(best, bi, sh[0], si);
+      if (tid == 0) {
+        *out_id = bi;
+        if (kept_out) *kept_out = 1;
+        if (logprob) *logprob = (unsigned)bi < (unsigned)V ? row[bi] - lse : NAN;
+      }
+      return;
+    }
   }
+  float mx = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < NPT; ++j) {
+    p[j] = p[j] * inv_temp;
+    mx = fmaxf(mx, p[j]);
+  }
+  mx = block_max(mx);
   uint32_t valid = 0xffffffffu;   // bit j: slot j is inside the top-k set (all slots when the filter is off)
   if (top_k > 0 && top_k < V) {   // TopKLogitsWarper: everything below the k-th largest scaled logit leaves the distribution
+    // the slots hold their ordered keys (as bits) for the 32 passes and get their values back after: a second set of 32 registers for
+    // the keys is what used to push this kernel into scratch
+#pragma unroll
+    for (int j = 0; j < NPT; ++j) p[j] = __uint_as_float(order_key(p[j]));
     uint64_t lo = 0, hi = 0x100000000ull;
     for (int it = 0; it < 32; ++it) {
-      const uint64_t mid = lo + ((hi - lo) >> 1);
+      const uint64_t mid = lo + ((hi - lo) >> 1);     // < 2^32: mid < hi
+      const uint32_t mid32 = (uint32_t)mid;
       float c = 0.f;
 #pragma unroll
-      for (int j = 0; j < NPT; ++j) c += ((uint64_t)order_key(p[j]) >= mid) ? 1.f : 0.f;
+      for (int j = 0; j < NPT; ++j) c += (__float_as_uint(p[j]) >= mid32) ? 1.f : 0.f;
       c = block_sum(c);
       if (c >= (float)top_k) lo = mid; else hi = mid;
     }
     valid = 0u;
+    const uint32_t lo32 = (uint32_t)lo;
 #pragma unroll
     for (int j = 0; j < NPT; ++j) {
-      const bool in = (uint64_t)order_key(p[j]) >= lo;
+      const uint32_t key = __float_as_uint(p[j]);
+      const bool in = key >= lo32;
       valid |= in ? (1u << j) : 0u;
-      p[j] = in ? p[j] : -INFINITY;
+      p[j] = in ? __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key) : -INFINITY;
     }
   }
   float zl = 0.f;
@@ -350,11 +511,10 @@ __global__ __launch_bounds__(1024) void sample_top_p_reg_kernel(const float* __r
   const float kept = block_sum(mine);
   cnt = block_sum(cnt);
   if (tid == 0) {
-    if (kept_count) kept_count[blockIdx.x] = (int)cnt;
+    if (kept_out) *kept_out = (int)cnt;
     chosen = -1;
   }
-  const uint64_t r = splitmix64(seed ^ splitmix64(step * 0x632be59bd9b4e019ull + blockIdx.x));
-  const float u = (float)((r >> 40) + 0.5) * (1.0f / 16777216.0f) * kept;
+  const float u = sample_uniform24(a) * kept;
   // exclusive prefix over threads: wave scan + scan of the 16 wave totals
   float incl = mine;
 #pragma unroll
@@ -390,7 +550,52 @@ __global__ __launch_bounds__(1024) void sample_top_p_reg_kernel(const float* __r
     atomicMax(&chosen, last);
   }
   __syncthreads();
-  if (tid == 0) out_ids[blockIdx.x] = chosen;
+  if (tid == 0) {
+    const int id = chosen;
+    *out_id = id;
+    if constexpr (kRows)
+      if (logprob) *logprob = (unsigned)id < (unsigned)V ? row[id] - lse : NAN;
+  }
+}
+
+// vt_sample_top_p: launch-uniform parameters, the row index as the stream of the uniform
+__device__ __forceinline__ SampleArgs uniform_args(float inv_temp, int top_k, float top_p, uint64_t seed, uint64_t step) {
+  return SampleArgs{inv_temp, top_k, top_p, seed, step, blockIdx.x, false, 1.0f, nullptr, 0};
+}
+__global__ __launch_bounds__(1024) void sample_top_p_kernel(const float* __restrict__ logits, int V, int ldl,
+                                                            float inv_temp, int top_k, float top_p, uint64_t seed, uint64_t step,
+                                                            int* __restrict__ out_ids, int* __restrict__ kept_count) {
+  sample_stream_body<false>(logits + (size_t)blockIdx.x * ldl, V, uniform_args(inv_temp, top_k, top_p, seed, step), nullptr,
+                            out_ids + blockIdx.x, kept_count ? kept_count + blockIdx.x : nullptr, nullptr);
+}
+__global__ __launch_bounds__(1024) void sample_top_p_reg_kernel(const float* __restrict__ logits, int V, int ldl,
+                                                                float inv_temp, int top_k, float top_p, uint64_t seed, uint64_t step,
+                                                                int* __restrict__ out_ids, int* __restrict__ kept_count) {
+  sample_reg_body<false>(logits + (size_t)blockIdx.x * ldl, V, uniform_args(inv_temp, top_k, top_p, seed, step), nullptr,
+                         out_ids + blockIdx.x, kept_count ? kept_count + blockIdx.x : nullptr, nullptr);
+}
+
+// vt_sample_rows: the same two bodies, every row with its own vt_sample_row. Nothing a field can hold indexes out of bounds: a
+// temperature that is not > 0 (0, negative, NaN) is a greedy row, top_k <= 0 is off, a top_p the bisection cannot reach keeps the whole
+// row, history ids are range-checked, a NULL history or a length <= 0 is an empty one.
+constexpr int kSampleRowsMaxV = VT_SAMPLE_ROWS_MAX_V;
+__device__ __forceinline__ SampleArgs row_args(const vt_sample_row& r) {
+  const bool greedy = !(r.temperature > 0.f);
+  return SampleArgs{greedy ? 1.0f : __fdiv_rn(1.0f, r.temperature), r.top_k, r.top_p, r.seed, r.counter, r.stream, greedy,
+                    r.repetition_penalty, r.history, r.history_len};
+}
+template <bool kReg>
+__global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restrict__ logits, int V, int ldl,
+                                                           const vt_sample_row* __restrict__ params, int* __restrict__ out_ids,
+                                                           int* __restrict__ kept_count, float* __restrict__ logprob) {
+  __shared__ uint32_t seen[(kReg ? 32 * 1024 : kSampleRowsMaxV) / 32];
+  const int r = blockIdx.x;
+  const SampleArgs a = row_args(params[r]);
+  const float* row = logits + (size_t)r * ldl;
+  if constexpr (kReg)
+    sample_reg_body<true>(row, V, a, seen, out_ids + r, kept_count ? kept_count + r : nullptr, logprob ? logprob + r : nullptr);
+  else
+    sample_stream_body<true>(row, V, a, seen, out_ids + r, kept_count ? kept_count + r : nullptr, logprob ? logprob + r : nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -452,6 +657,22 @@ int vt_sample_top_p_launch(const float* logits, int rows, int V, int ldl, float 
   else
     hipLaunchKernelGGL(sample_top_p_kernel, dim3(rows), dim3(1024), 0, s, logits, V, ldl, 1.0f / temperature, top_k, top_p, seed,
                        step, out_ids, kept_count);
+  VT_LAUNCH_CHECK();
+  return VT_OK;
+}
+
+int vt_sample_rows_launch(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, int* out_ids, int* kept_count,
+                          float* logprob, hipStream_t s) {
+  VT_REQUIRE(logits && params && out_ids, "vt_sample_rows: null pointer (logits, params and out_ids are required)");
+  VT_REQUIRE(rows > 0 && V > 0 && ldl >= V, "vt_sample_rows: rows=%d V=%d ldl=%d (rows, V > 0 and ldl >= V)", rows, V, ldl);
+  VT_REQUIRE(((uintptr_t)params % 8) == 0, "vt_sample_rows: params must be 8-byte aligned");
+  if (V <= 32 * 1024 && (ldl % 4) == 0 && ((uintptr_t)logits % 16) == 0) {
+    hipLaunchKernelGGL(sample_rows_kernel<true>, dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, out_ids, kept_count, logprob);
+  } else {
+    VT_REQUIRE(V <= VT_SAMPLE_ROWS_MAX_V, "vt_sample_rows: V=%d is beyond the history mask of the streaming form (V <= %d)", V,
+               VT_SAMPLE_ROWS_MAX_V);
+    hipLaunchKernelGGL(sample_rows_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, out_ids, kept_count, logprob);
+  }
   VT_LAUNCH_CHECK();
   return VT_OK;
 }

@@ -457,8 +457,14 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
     def generate(self, input_ids=None, images=None, regions=None, attention_mask=None, do_sample=False,
                  temperature=1.0, top_p=1.0, top_k=None, max_new_tokens=None, max_length=None, use_cache=True,
                  stopping_criteria=None, eos_token_id=None, pad_token_id=None, num_beams=1, seed=None,
-                 return_logits=False, padded_batch=False, **kwargs):
-        """padded_batch=True (B > 1, right padding): reproduce what the REFERENCE's batched generate() returns -- transformers 4.31 reads the
+                 return_logits=False, padded_batch=False, repetition_penalty=1.0, return_logprobs=False, **kwargs):
+        """repetition_penalty (RepetitionPenaltyLogitsProcessor; 1.0 is off) and return_logprobs: with both at their defaults a step
+        launches what it always did (vt_argmax / vt_sample_top_p). Otherwise every step is ONE vt_sample_rows launch (row b: stream = b,
+        counter = step -- today's draws) whose penalty history -- the sample's non-negative prompt ids plus what it has generated -- lives
+        and grows on the device. return_logprobs=True additionally returns a [B, n_new] fp32 tensor: log_softmax of the raw logits at every
+        emitted id (for a row that has finished, of the id it would have emitted instead of the pad). Returns ids; (ids, all_logits) with
+        return_logits; the log-probabilities come last: (ids, logprobs) or (ids, all_logits, logprobs).
+        padded_batch=True (B > 1, right padding): reproduce what the REFERENCE's batched generate() returns -- transformers 4.31 reads the
         first token of every sample from the last COLUMN of the padded logits (a pad row for the shorter samples) and the decode-step
         fix-up (llava_arch.py:196-205) attends the pad rows of the spliced batch while masking the rows that share an index with the
         ids-length mask's zeros (engine.padded_batch_fixup; pinned by tests/golden/greedy_batch.npz). Default False: sequences are packed
@@ -483,6 +489,10 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         sample_seed = 0
         if do_sample:
             sample_seed = int(seed) if seed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        from ...sampling import ROW_BYTES, check_sampling_values, pack_sample_rows
+        check_sampling_values(temperature if do_sample else 0.0, top_p if (do_sample and top_p) else 1.0, int(top_k or 0), repetition_penalty,
+                              "generate")
+        use_rows = float(repetition_penalty) != 1.0 or bool(return_logprobs)
 
         reuse = B == 1 and bool(getattr(self.config, "kv_prefix_reuse", True))
         cache = None
@@ -593,7 +603,24 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         out_host[:, :L0] = input_ids.cpu()
         n_out = L0
         all_logits = []
+        all_lp = []
         state = None
+        if use_rows:
+            # every step's vt_sample_row array in ONE upload (counter = step, history_len = prompt ids + step): no per-step copy
+            hist = hist_pos = None
+            base = [0] * B
+            if float(repetition_penalty) != 1.0:
+                keep = [input_ids[b][input_ids[b] >= 0].to(torch.int32) for b in range(B)]        # (image / region sentinels are negative)
+                base = [int(k.numel()) for k in keep]
+                hist = torch.zeros((B, max(base) + max_new_tokens), dtype=torch.int32, device=dev)
+                for b in range(B):
+                    hist[b, :base[b]] = keep[b]
+                hist_pos = torch.tensor(base, dtype=torch.long, device=dev).unsqueeze(1)
+            row_T, row_p, row_k = (float(temperature), float(top_p if top_p else 1.0), int(top_k or 0)) if do_sample else (0.0, 1.0, 0)
+            row_params = pack_sample_rows(
+                [(row_T, row_k, row_p, float(repetition_penalty), sample_seed, st, b,
+                  0 if hist is None else hist.data_ptr() + 4 * b * hist.stride(0), base[b] + st if hist is not None else 0)
+                 for st in range(max_new_tokens) for b in range(B)], dev).view(max_new_tokens, B, ROW_BYTES)
         try:   # (the prefill is inside: pages it took before a failure go back to the pool / the kept prefix below)
             logits = llama_forward(llama, self.kv, seqs, flat, lens, embeds_lo=flat_lo)     # [B, V]: last position of every sequence
             if pad_mode:
@@ -606,7 +633,15 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
             for step in range(max_new_tokens):
                 if return_logits:
                     all_logits.append(logits.clone())
-                if do_sample:   # device-side temperature / top-k / top-p sampler (no host sync, counter-based RNG)
+                if use_rows:    # per-row sampler: penalty over the device history, greedy or sampled, the chosen token's log-probability
+                    nxt = ops.sample_rows(logits, row_params[step], return_logprob=bool(return_logprobs))
+                    if return_logprobs:
+                        nxt, lp = nxt
+                        all_lp.append(lp)
+                    if hist is not None:                # the history grows on the device: no host sync
+                        hist.scatter_(1, hist_pos, nxt.unsqueeze(1))
+                        hist_pos += 1
+                elif do_sample:   # device-side temperature / top-k / top-p sampler (no host sync, counter-based RNG)
                     nxt = ops.sample_top_p(logits, temperature, top_p if top_p else 1.0, sample_seed, step, top_k=int(top_k or 0))
                 else:
                     nxt = ops.argmax(logits)
@@ -643,6 +678,9 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                 for s in seqs:
                     self.kv.release(s.pages)
         out = out_host[:, :n_out].to(dev)
+        if return_logprobs:
+            lps = torch.stack(all_lp, 1)[:, :n_out - L0] if all_lp else torch.empty((B, 0), dtype=torch.float32, device=dev)
+            return (out, all_logits, lps) if return_logits else (out, lps)
         if return_logits:
             return out, all_logits
         return out

@@ -508,6 +508,27 @@ def sample_top_p(logits: torch.Tensor, temperature: float, top_p: float, seed: i
     return (out, kept) if return_kept else out
 
 
+def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = False, return_logprob: bool = False):
+    """One token id per row (int32, on device) with PER-ROW parameters: greedy and sampled rows, penalties and the chosen token's
+    log-probability in one launch; see vt_sample_rows in include/vitron_hip.h. `params`: the device array of vt_sample_row that
+    sampling.pack_sample_rows builds (uint8 [rows, 48]). Returns ids, or (ids[, kept_count][, logprob]) when either is asked for."""
+    from .sampling import ROW_BYTES
+    lib = _lib.load_any()
+    _chk_rows(logits, torch.float32, "sample_rows.logits")
+    rows, V = logits.shape
+    if not isinstance(params, torch.Tensor) or params.device != logits.device or params.dtype != torch.uint8 \
+            or not params.is_contiguous() or params.numel() != rows * ROW_BYTES:
+        raise _lib.VitronHipError(f"sample_rows.params: expected a contiguous uint8 tensor of {rows} x {ROW_BYTES} bytes on the logits' device "
+                                  "(sampling.pack_sample_rows)")
+    out = torch.empty((rows,), device=logits.device, dtype=torch.int32)
+    kept = torch.empty((rows,), device=logits.device, dtype=torch.int32) if return_kept else None
+    lp = torch.empty((rows,), device=logits.device, dtype=torch.float32) if return_logprob else None
+    _lib.check(lib.vt_sample_rows(_p(logits), rows, V, logits.stride(0), _p(params), _p(out), _p(kept), _p(lp), _stream()),
+               "vt_sample_rows", lib)
+    res = (out,) + ((kept,) if return_kept else ()) + ((lp,) if return_logprob else ())
+    return res if len(res) > 1 else out
+
+
 def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, ignore_index: int = -100) -> torch.Tensor:
     """Mean cross entropy of fp32 logits [rows, V] against int labels [rows] (rows with `ignore_index` skipped); 0-dim tensor."""
     lib = _lib.load_any()

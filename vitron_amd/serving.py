@@ -11,7 +11,9 @@ GEMMs + the fused decode attention), and requests join / leave between steps.
   for rid, token in eng.step(): ...                  # or: outputs = eng.run()   -> {rid: LongTensor of new tokens}
 
 Admission runs the request's multimodal prefill on its own (towers -> splice -> decoder prefill, exactly what `generate` does,
-including the visual-feature cache), so a request's tokens are bit-identical to running it alone with greedy decoding as long
+including the visual-feature cache), so a request's tokens are bit-identical to running it alone -- with greedy decoding, and with
+sampling for a request submitted with its own `SamplingParams` (submit(..., sampling=): its draws depend on its seed and on how many
+tokens it has generated, never on its neighbours; DESIGN.md 8, the `_pick` contract) -- as long
 as the decode batch stays on one kernel path (<= 16 rows: the folded-norm path; the engine never mixes a sequence between the
 <= 16 and > 16 row paths within one request unless max_batch > 16).
 
@@ -33,6 +35,7 @@ import torch
 
 from . import ops
 from .engine import PagedKVCache, SequenceState, llama_forward, pair_lo, parse_kv_cache_dtype
+from .sampling import SamplingParams, pack_sample_rows
 
 
 @dataclass
@@ -51,6 +54,11 @@ class _Request:
     flat_lo: Optional[torch.Tensor] = None   # their low halves in the precise levels 2 / 3 (the embeddings travel as an operand pair)
     need: int = 0                            # KV pages for prompt + max_new_tokens
     error: Optional[BaseException] = None    # set when the request failed on its own (it is in ServingEngine.failed then)
+    sampling: Optional[SamplingParams] = None  # per-request sampling; None: the engine-wide setting (the legacy draw)
+    hist: Optional[torch.Tensor] = None      # device int32: non-negative prompt ids + generated tokens (only with a repetition penalty)
+    hist_len: int = 0
+    last_lp: Optional[torch.Tensor] = None   # device fp32 [1]: log-probability of `last` (sampling.logprobs)
+    logprobs: List[float] = field(default_factory=list)
 
 
 class ServingEngine:
@@ -82,13 +90,21 @@ class ServingEngine:
 
     # ---- queue ----------------------------------------------------------------------------------------------------------
     def submit(self, input_ids: torch.Tensor, images=None, regions=None, max_new_tokens: int = 256,
-               eos_token_id=None) -> int:
+               eos_token_id=None, sampling: Optional[SamplingParams] = None) -> int:
+        """sampling: this request's own SamplingParams. It then draws with (seed = sampling.seed, counter = tokens it has generated so
+        far, stream = 0) -- what generate() uses for a batch of one -- so its tokens equal
+        generate(do_sample=temperature > 0, temperature, top_p, top_k, seed, repetition_penalty) for the request alone, whatever else is in
+        the batch. Without it the request follows the engine-wide setting exactly as before."""
         ids = input_ids if input_ids.dim() == 2 else input_ids.unsqueeze(0)
         if ids.shape[0] != 1:
             raise ValueError("submit() takes one sequence per request")
+        if sampling is not None:                 # rejected here, before anything is queued
+            if not isinstance(sampling, SamplingParams):
+                raise TypeError(f"submit(sampling=...) takes a SamplingParams, got {type(sampling).__name__}")
+            sampling.validate()
         eos = self.model.config.eos_token_id if eos_token_id is None else eos_token_id
         eos_set = frozenset(eos) if isinstance(eos, (list, tuple, set, frozenset)) else (frozenset([eos]) if eos is not None else frozenset())
-        r = _Request(self._next_id, ids.to(self.model.device), images, regions, int(max_new_tokens), eos_set)
+        r = _Request(self._next_id, ids.to(self.model.device), images, regions, int(max_new_tokens), eos_set, sampling=sampling)
         self._next_id += 1
         self.waiting.append(r)
         return r.rid
@@ -109,7 +125,7 @@ class ServingEngine:
         """The request failed on its own: it leaves the engine with its exception; nothing else is disturbed."""
         if r.seq.pages:
             self.model.kv.release(r.seq.pages)
-        r.seq.pages, r.seq.length, r.last, r.flat = [], 0, None, None
+        r.seq.pages, r.seq.length, r.last, r.flat, r.hist, r.last_lp = [], 0, None, None, None, None
         r.error, r.done = exc, True
         self.failed[r.rid] = r
 
@@ -119,10 +135,36 @@ class ServingEngine:
         return isinstance(exc, torch.cuda.OutOfMemoryError) or "status -2" in str(exc) or "HIP error" in str(exc)
 
     # ---- one scheduling step ---------------------------------------------------------------------------------------------
-    def _pick(self, logits: torch.Tensor) -> torch.Tensor:
-        if self.do_sample:
-            return ops.sample_top_p(logits, self.temperature, self.top_p, self.seed, self._step)
-        return ops.argmax(logits)
+    def _pick(self, logits: torch.Tensor, reqs: Optional[List[_Request]] = None) -> torch.Tensor:
+        """One token per logits row (row i belongs to reqs[i]). While no row's request carries `sampling` this is the launch it always
+        was: ops.argmax, or ops.sample_top_p with the engine's scalars. Otherwise ONE ops.sample_rows launch serves every row: a request
+        with `sampling` draws from (its seed, the number of tokens it has generated, stream 0); a request without gets the parameters
+        that reproduce its legacy draw (the engine's temperature / top_p, top_k 0, the engine's seed, counter = the engine's step,
+        stream = its batch row; greedy when the engine does not sample). Log-probabilities land in r.last_lp."""
+        if reqs is None or all(r.sampling is None for r in reqs):
+            if self.do_sample:
+                return ops.sample_top_p(logits, self.temperature, self.top_p, self.seed, self._step)
+            return ops.argmax(logits)
+        rows = []
+        for i, r in enumerate(reqs):
+            sp = r.sampling
+            if sp is None:
+                rows.append((self.temperature if self.do_sample else 0.0, 0, self.top_p, 1.0, self.seed, self._step, i, 0, 0))
+                continue
+            if sp.repetition_penalty != 1.0 and r.hist is None:
+                keep = r.input_ids[0][r.input_ids[0] >= 0].to(torch.int32)          # (the image / region sentinels are negative)
+                r.hist = torch.empty((keep.numel() + r.max_new_tokens,), dtype=torch.int32, device=keep.device)
+                r.hist[:keep.numel()] = keep
+                r.hist_len = int(keep.numel())
+            rows.append((sp.temperature, sp.resolved_top_k(self.model.config), sp.top_p, sp.repetition_penalty, sp.seed, len(r.tokens), 0,
+                         r.hist.data_ptr() if r.hist is not None else 0, r.hist_len if r.hist is not None else 0))
+        want_lp = any(r.sampling is not None and r.sampling.logprobs for r in reqs)
+        res = ops.sample_rows(logits, pack_sample_rows(rows, logits.device), return_logprob=want_lp)
+        ids, lp = res if want_lp else (res, None)
+        for i, r in enumerate(reqs):
+            if r.sampling is not None and r.sampling.logprobs:
+                r.last_lp = lp[i:i + 1]
+        return ids
 
     def _embed(self, r: _Request) -> torch.Tensor:
         m = self.model
@@ -202,7 +244,7 @@ class ServingEngine:
 
         def prefill_one(r):
             try:
-                r.last = self._pick(llama_forward(llama, m.kv, [r.seq], r.flat, [r.flat.shape[0]], embeds_lo=getattr(r, "flat_lo", None)))
+                r.last = self._pick(llama_forward(llama, m.kv, [r.seq], r.flat, [r.flat.shape[0]], embeds_lo=getattr(r, "flat_lo", None)), [r])
                 ok.append(r)
             except Exception as e:  # noqa: BLE001
                 if self._is_device_error(e):
@@ -218,7 +260,7 @@ class ServingEngine:
                     if any(l is not None for l in los):      # (requests without visual rows have an exact 16-bit embedding: low half zero)
                         lo_cat = torch.cat([l if l is not None else torch.zeros_like(f) for l, f in zip(los, flats)], 0)
                     logits = llama_forward(llama, m.kv, [r.seq for r in admitted], torch.cat(flats, 0), [f.shape[0] for f in flats], embeds_lo=lo_cat)
-                    nxt = self._pick(logits)
+                    nxt = self._pick(logits, admitted)
                     for i, r in enumerate(admitted):
                         r.last = nxt[i:i + 1]
                     ok = list(admitted)
@@ -249,6 +291,7 @@ class ServingEngine:
         r.done = True
         self.model.kv.release(r.seq.pages)
         r.seq.pages = []
+        r.hist = r.last_lp = None
         self.finished[r.rid] = r
 
     def step(self) -> List[Tuple[int, int]]:
@@ -263,6 +306,10 @@ class ServingEngine:
             return []
         # tokens chosen at the end of the previous step (or by the prefill) become visible now: ONE read-back per step
         toks = torch.cat([r.last for r in self.active]).tolist()
+        with_lp = [r for r in self.active if r.last_lp is not None]
+        if with_lp:
+            for r, v in zip(with_lp, torch.cat([r.last_lp for r in with_lp]).tolist()):
+                r.logprobs.append(float(v))
         out: List[Tuple[int, int]] = []
         still: List[_Request] = []
         for r, t in zip(self.active, toks):
@@ -280,7 +327,11 @@ class ServingEngine:
             plan = torch.stack([torch.zeros_like(ids), ids], dim=1).contiguous()
             x = ops.embed_splice(llama.embed, None, None, plan)
             logits = llama_forward(llama, m.kv, [r.seq for r in self.active], x, [1] * len(self.active))
-            nxt = self._pick(logits)
+            for r in self.active:                       # the token just fed joins the request's penalty history, on the device
+                if r.hist is not None:
+                    r.hist[r.hist_len:r.hist_len + 1].copy_(r.last)
+                    r.hist_len += 1
+            nxt = self._pick(logits, self.active)
             for i, r in enumerate(self.active):
                 r.last = nxt[i:i + 1]
         self._step += 1
@@ -301,6 +352,16 @@ class ServingEngine:
                 raise RuntimeError(f"ServingEngine.run: no progress -- {len(self.waiting)} request(s) waiting, none active, {free} KV pages free "
                                    f"(the head request needs {self.waiting[0].need}); pages are held outside the engine")
         return {rid: torch.tensor(r.tokens, dtype=torch.long) for rid, r in sorted(self.finished.items())}
+
+    def logprobs(self, rid: int) -> torch.Tensor:
+        """fp32 log-probabilities (log_softmax of the raw logits at the chosen id) of the tokens request `rid` has emitted so far, in
+        order; the request must have been submitted with SamplingParams(logprobs=True)."""
+        for r in list(self.finished.values()) + self.active:
+            if r.rid == rid:
+                if r.sampling is None or not r.sampling.logprobs:
+                    raise ValueError(f"request {rid} was not submitted with SamplingParams(logprobs=True)")
+                return torch.tensor(r.logprobs, dtype=torch.float32)
+        raise KeyError(f"request {rid} has emitted nothing (waiting, failed or unknown)")
 
     def errors(self) -> Dict[int, BaseException]:
         """{request id: exception} of the requests that failed on their own."""
