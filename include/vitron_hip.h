@@ -88,6 +88,7 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
  * three new symbols that forward to launches vt_llama_forward already makes; no struct and no existing signature changes. */
 /* 114 also carries vt_sample_rows and struct vt_sample_row WITHOUT a bump: one new symbol and one new struct; vt_sample_top_p and
  * vt_argmax keep their signatures and return what they returned, bit for bit. */
+/* 114 also carries vt_sample_rows_allow WITHOUT a bump: one new symbol; struct vt_sample_row and vt_sample_rows do not change. */
 #define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
@@ -371,6 +372,25 @@ typedef struct vt_sample_row {
 } vt_sample_row;
 int vt_sample_rows(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, int* out_ids, int* kept_count,
                    float* logprob, void* stream);
+
+/* vt_sample_rows with a PER-ROW ALLOW MASK: which token ids a row may emit at all (constrained decoding; the role of transformers'
+ * SuppressTokens / BeginSuppressTokens / MinNewTokensLength / single-token NoBadWords / PrefixConstrained logits processors, which all
+ * write -inf at the ids they forbid).
+ * allow: DEVICE array of `rows` device pointers (8-byte aligned); allow[r] points to ceil(V / 32) uint32 words, or is NULL.
+ *   Word / bit layout: token i may be chosen iff bit (i & 31) of word (i >> 5) is set. Bits at positions >= V in the last word are
+ *   ignored. A NULL entry means every token of that row is allowed. A mask must be readable for ceil(V / 32) words; no word outside
+ *   [0, ceil(V / 32)) and no logit outside the row is read.
+ * A token whose bit is clear is treated as if its logit were -inf in steps 1 and 2 of the vt_sample_rows contract (-inf is unchanged by
+ * the penalty and by the temperature; the mask is applied before the row maximum and the top-k threshold are computed). out_ids and
+ * kept_count are bit-equal to what vt_sample_rows returns on a copy of the logits with -inf written at the banned positions; that also
+ * defines a row with nothing allowed (what an all -inf row returns). Step 3 is unchanged: logprob stays raw[id] - logsumexp(raw) over
+ * the RAW row, banned positions included.
+ * allow == NULL behaves exactly like vt_sample_rows (the same launch). The argument checks, the two forms and VT_SAMPLE_ROWS_MAX_V are
+ * vt_sample_rows's; the mask stays in global memory in both forms.
+ * 114 carries this entry point WITHOUT a bump: one new symbol, nothing existing changes (see the note at VT_ABI_VERSION). */
+int vt_sample_rows_allow(const float* logits, int rows, int V, int ldl, const vt_sample_row* params,
+                         const uint32_t* const* allow /* DEVICE array of `rows` device pointers, entries may be NULL */,
+                         int* out_ids, int* kept_count, float* logprob, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * mm_projector: Linear(Din,Dh) -> GELU(erf) -> Linear(Dh,Dout)   ('mlp2x_gelu';  w2 == NULL -> 'linear')

@@ -1,11 +1,19 @@
-"""Times vt_argmax, vt_sample_top_p and vt_sample_rows on decode-sized logits ([rows, 32000] fp32).
+"""Times vt_argmax, vt_sample_top_p, vt_sample_rows and vt_sample_rows_allow on decode-sized logits ([rows, 32000] fp32).
 
 vt_sample_rows runs all-sampled, all-greedy and mixed batches (even rows greedy), each without a history and with a 2048-id history under
-a repetition penalty of 1.3, and all-sampled with the log-probability output. The arms are alternated inside one process over `--rounds`
-rounds of `--iters` launches between two device events; per arm the output gives every round, the median and the spread
-(max - min) / median -- two arms are apart only when they differ by more than the spreads. `--baseline-lib PATH` adds vt_argmax and
-vt_sample_top_p of ANOTHER build of libvitron_hip.so (for instance the parent commit's) to the same alternation. `--json FILE` writes the
-table (profiles/sampler_rows_bench.json).
+a repetition penalty of 1.3, and all-sampled with the log-probability output.
+
+The constrained arms (vt_sample_rows_allow) run the all-sampled batch only, with an allow mask of about half the vocabulary
+on every row ("allow all rows") and on the odd rows only ("allow half rows", the others NULL). Each runs with the pointer array built
+beforehand (the kernel's cost) and built per call from the list of masks ("+ptrs": what ServingEngine._pick pays). "step mask upload" is
+the host build and the ceil(V / 32) * 4-byte upload of ONE step-dependent mask, of 16000 ids and of 8: the engine's extra cost per
+constrained row and step.
+
+The arms are alternated inside one process over `--rounds` rounds of `--iters` launches between two device events; per arm the output
+gives every round, the median and the spread (max - min) / median -- two arms are apart only when they differ by more than the spreads.
+`--baseline-lib PATH` adds vt_argmax, vt_sample_top_p and vt_sample_rows of ANOTHER build of libvitron_hip.so (for instance the parent
+commit's) to the same alternation. `--json FILE` writes the table (profiles/sampler_rows_bench.json: the run of DESIGN.md 9.3;
+profiles/sampler_allow_bench.json: the run of 9.4, with the constrained arms).
 
   python tools/sampler_bench.py [--rows 4,16] [--iters 200] [--rounds 3] [--baseline-lib path/libvitron_hip.so] [--json out.json]
 """
@@ -16,11 +24,12 @@ import os
 import statistics
 import sys
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vitron_amd import _lib, ops  # noqa: E402
-from vitron_amd.sampling import pack_sample_rows  # noqa: E402
+from vitron_amd.sampling import allow_mask, pack_sample_rows  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--rows", default="1,4,16")
@@ -38,6 +47,7 @@ if args.baseline_lib:
     base = C.CDLL(os.path.abspath(args.baseline_lib))
     base.vt_argmax.argtypes = _lib.SIGNATURES["vt_argmax"][1]
     base.vt_sample_top_p.argtypes = _lib.SIGNATURES["vt_sample_top_p"][1]
+    base.vt_sample_rows.argtypes = _lib.SIGNATURES["vt_sample_rows"][1]
 
 
 def time_us(fn):
@@ -78,6 +88,19 @@ for rows in [int(r) for r in args.rows.split(",")]:
         for with_hist in (False, True):
             pr = params(kind, with_hist)
             arms[f"rows {kind}" + (" +hist" if with_hist else "")] = lambda pr=pr: ops.sample_rows(lg, pr)
+    pr_s = params("sampled", False)
+    if base is not None:
+        arms["baseline rows sampled"] = lambda: base.vt_sample_rows(lg.data_ptr(), rows, V, V, pr_s.data_ptr(), out.data_ptr(), None, None, stream)
+    g = np.random.default_rng(rows)
+    host_masks = [allow_mask(V, np.flatnonzero(g.random(V) < 0.5)) for _ in range(rows)]
+    masks = [torch.from_numpy(m.view(np.int32)).to(dev) for m in host_masks]
+    for label, lst in (("allow all rows", masks), ("allow half rows", [m if r % 2 else None for r, m in enumerate(masks)])):
+        ptrs = ops.allow_pointers(lst, rows, V, dev)
+        arms[f"rows sampled {label}"] = lambda ptrs=ptrs: ops.sample_rows(lg, pr_s, _allow_ptrs=ptrs)
+        arms[f"rows sampled {label} +ptrs"] = lambda lst=lst: ops.sample_rows(lg, pr_s, allow=lst)
+    half_ids = np.flatnonzero(g.random(V) < 0.5)
+    arms["step mask upload (16000 ids)"] = lambda: torch.from_numpy(allow_mask(V, half_ids).view(np.int32)).to(dev)
+    arms["step mask upload (8 ids)"] = lambda: torch.from_numpy(allow_mask(V, [5, 31, 32, 1023, 1024, 7777, 20000, V - 1]).view(np.int32)).to(dev)
     pr_lp = params("sampled", False)
     arms["rows sampled +logprob"] = lambda: ops.sample_rows(lg, pr_lp, return_logprob=True)
     assert torch.equal(ops.sample_rows(lg, params("sampled", False)), ops.sample_top_p(lg, T, P, SEED, STEP))      # the same draw
@@ -89,7 +112,7 @@ for rows in [int(r) for r in args.rows.split(",")]:
     for name, ts in times.items():
         med = statistics.median(ts)
         shape[name] = {"us": [round(t, 2) for t in ts], "median_us": round(med, 2), "spread": round((max(ts) - min(ts)) / med, 4)}
-        print(f"rows={rows:2d} {name:22s} {med:8.1f} us   rounds {[f'{t:.1f}' for t in ts]}  spread {shape[name]['spread']:.3f}")
+        print(f"rows={rows:2d} {name:36s} {med:8.1f} us   rounds {[f'{t:.1f}' for t in ts]}  spread {shape[name]['spread']:.3f}")
     result["shapes"][f"{rows}x{V}"] = shape
 if args.json:
     with open(args.json, "w") as f:

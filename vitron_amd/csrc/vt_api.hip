@@ -449,7 +449,12 @@ int vt_sample_top_p(const float* logits, int rows, int V, int ldl, float tempera
 
 int vt_sample_rows(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, int* out_ids, int* kept_count,
                    float* logprob, void* stream) {
-  return vt_sample_rows_launch(logits, rows, V, ldl, params, out_ids, kept_count, logprob, S(stream));
+  return vt_sample_rows_launch(logits, rows, V, ldl, params, nullptr, out_ids, kept_count, logprob, S(stream));
+}
+
+int vt_sample_rows_allow(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, const uint32_t* const* allow,
+                         int* out_ids, int* kept_count, float* logprob, void* stream) {
+  return vt_sample_rows_launch(logits, rows, V, ldl, params, allow, out_ids, kept_count, logprob, S(stream));
 }
 
 // ---- mm_projector ---------------------------------------------------------------------------------------------------

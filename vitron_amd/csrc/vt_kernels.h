@@ -234,8 +234,8 @@ int vt_cross_entropy_launch(const float* logits, int rows, int V, int ldl, const
                             float* loss, hipStream_t s);
 int vt_sample_top_p_launch(const float* logits, int rows, int V, int ldl, float temperature, int top_k, float top_p, uint64_t seed,
                            uint64_t step, int* out_ids, int* kept_count, hipStream_t s);
-int vt_sample_rows_launch(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, int* out_ids, int* kept_count,
-                          float* logprob, hipStream_t s);
+int vt_sample_rows_launch(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, const uint32_t* const* allow,
+                          int* out_ids, int* kept_count, float* logprob, hipStream_t s);   // allow == NULL: vt_sample_rows
 
 // ---- vt_preproc.hip -------------------------------------------------------------------------------
 int vt_preprocess_launch(const void* src, int src_u8, int hwc, int F, int H, int W, int bicubic, int S, const float* mean,

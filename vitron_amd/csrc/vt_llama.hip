@@ -214,9 +214,13 @@ __device__ __forceinline__ bool fill_seen_mask(uint32_t* seen, int V, const Samp
 // Streaming form of the sampler, any V: the row is re-read from memory (L2) in every pass. kRows adds what vt_sample_rows needs on
 // top of vt_sample_top_p's arithmetic -- the repetition penalty (through `seen`, ceil(V/32) words of LDS), greedy rows and the
 // log-probability of the chosen token -- and compiles to nothing in the launch-uniform kernel.
-template <bool kRows>
+// kAllow (vt_sample_rows_allow): `allow` is the row's V-bit allow mask in GLOBAL memory (ceil(V/32) words, NULL = all
+// allowed). val(i) reads word i >> 5 for i < V only -- always inside the mask -- and a token whose bit is clear is -inf BEFORE the penalty,
+// i.e. exactly a row with -inf written there. The raw log-sum-exp does not go through val(): logprob stays over the RAW row.
+template <bool kRows, bool kAllow = false>
 __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row, int V, const SampleArgs& a, uint32_t* seen,
-                                                   int* __restrict__ out_id, int* __restrict__ kept_out, float* __restrict__ logprob) {
+                                                   int* __restrict__ out_id, int* __restrict__ kept_out, float* __restrict__ logprob,
+                                                   const uint32_t* __restrict__ allow = nullptr) {
   __shared__ float sh[16];
   __shared__ float sh_scan[16];
   __shared__ int chosen;
@@ -239,6 +243,8 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
   }
   auto val = [&](int i) -> float {     // the (penalised) logit i
     float x = row[i];
+    if constexpr (kAllow)
+      if (allow && !((allow[i >> 5] >> (i & 31)) & 1u)) x = -INFINITY;
     if constexpr (kRows)
       if (pen && ((seen[i >> 5] >> (i & 31)) & 1u)) x = penalise(x, a.penalty);
     return x;
@@ -365,9 +371,13 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
 // 165 us -> ~20 us per call at V = 32000 (tools/sampler_bench.py).
 // kRows: thread t's 32 logits are exactly word t of the seen mask, so the penalty is one LDS word per thread and a static unroll
 // (no dynamic register index, no scratch).
-template <bool kRows>
+// kAllow: word t of the row's allow mask is read straight from global memory (threads past ceil(V/32) read nothing: their slots are
+// -inf already) and applied under the same static unroll, after the raw log-sum-exp and before the penalty. Bits >= V of the last
+// word meet slots that are -inf whatever the bit says.
+template <bool kRows, bool kAllow = false>
 __device__ __forceinline__ void sample_reg_body(const float* __restrict__ row, int V, const SampleArgs& a, uint32_t* seen,
-                                                int* __restrict__ out_id, int* __restrict__ kept_out, float* __restrict__ logprob) {
+                                                int* __restrict__ out_id, int* __restrict__ kept_out, float* __restrict__ logprob,
+                                                const uint32_t* __restrict__ allow = nullptr) {
   constexpr int NPT = 32;
   __shared__ float sh[2][16];
   __shared__ float sh_scan[16];
@@ -423,6 +433,14 @@ __device__ __forceinline__ void sample_reg_body(const float* __restrict__ row, i
       for (int j = 0; j < NPT; ++j) rz += expf(p[j] - rmx);     // exp(-inf) = 0 for the slots past V
       rz = block_sum(rz);
       if (tid == 0) lse = rmx + logf(rz);
+    }
+    if constexpr (kAllow) {
+      if (allow) {       // block-uniform
+        const uint32_t ok = tid < ((V + 31) >> 5) ? allow[tid] : 0u;
+#pragma unroll
+        for (int j = 0; j < NPT; ++j)
+          if (!((ok >> j) & 1u)) p[j] = -INFINITY;
+      }
     }
     if (fill_seen_mask(seen, V, a)) {
       const uint32_t word = seen[tid];
@@ -597,6 +615,25 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
   else
     sample_stream_body<true>(row, V, a, seen, out_ids + r, kept_count ? kept_count + r : nullptr, logprob ? logprob + r : nullptr);
 }
+// vt_sample_rows_allow: the same launch with row r's allow mask allow[r] (a device pointer to ceil(V/32) words, or NULL: everything
+// allowed). A kernel of its own, so that sample_rows_kernel above stays the code it was, instruction for instruction. The seen mask keeps
+// its LDS; the allow mask stays in global memory in both forms, so the LDS figures are those of sample_rows_kernel.
+template <bool kReg>
+__global__ __launch_bounds__(1024) void sample_rows_allow_kernel(const float* __restrict__ logits, int V, int ldl,
+                                                                 const vt_sample_row* __restrict__ params,
+                                                                 const uint32_t* const* __restrict__ allow, int* __restrict__ out_ids,
+                                                                 int* __restrict__ kept_count, float* __restrict__ logprob) {
+  __shared__ uint32_t seen[(kReg ? 32 * 1024 : kSampleRowsMaxV) / 32];
+  const int r = blockIdx.x;
+  const SampleArgs a = row_args(params[r]);
+  const float* row = logits + (size_t)r * ldl;
+  const uint32_t* mask = allow[r];
+  if constexpr (kReg)
+    sample_reg_body<true, true>(row, V, a, seen, out_ids + r, kept_count ? kept_count + r : nullptr, logprob ? logprob + r : nullptr, mask);
+  else
+    sample_stream_body<true, true>(row, V, a, seen, out_ids + r, kept_count ? kept_count + r : nullptr, logprob ? logprob + r : nullptr,
+                                   mask);
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Shifted-token cross entropy of LlamaForCausalLM.forward(labels=...) (ignore_index rows skipped, mean over the rest):
@@ -661,17 +698,26 @@ int vt_sample_top_p_launch(const float* logits, int rows, int V, int ldl, float 
   return VT_OK;
 }
 
-int vt_sample_rows_launch(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, int* out_ids, int* kept_count,
-                          float* logprob, hipStream_t s) {
+int vt_sample_rows_launch(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, const uint32_t* const* allow,
+                          int* out_ids, int* kept_count, float* logprob, hipStream_t s) {
   VT_REQUIRE(logits && params && out_ids, "vt_sample_rows: null pointer (logits, params and out_ids are required)");
   VT_REQUIRE(rows > 0 && V > 0 && ldl >= V, "vt_sample_rows: rows=%d V=%d ldl=%d (rows, V > 0 and ldl >= V)", rows, V, ldl);
   VT_REQUIRE(((uintptr_t)params % 8) == 0, "vt_sample_rows: params must be 8-byte aligned");
+  VT_REQUIRE(((uintptr_t)allow % 8) == 0, "vt_sample_rows_allow: the allow pointer array must be 8-byte aligned");
   if (V <= 32 * 1024 && (ldl % 4) == 0 && ((uintptr_t)logits % 16) == 0) {
-    hipLaunchKernelGGL(sample_rows_kernel<true>, dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, out_ids, kept_count, logprob);
+    if (allow)
+      hipLaunchKernelGGL(sample_rows_allow_kernel<true>, dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, allow, out_ids,
+                         kept_count, logprob);
+    else
+      hipLaunchKernelGGL(sample_rows_kernel<true>, dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, out_ids, kept_count, logprob);
   } else {
     VT_REQUIRE(V <= VT_SAMPLE_ROWS_MAX_V, "vt_sample_rows: V=%d is beyond the history mask of the streaming form (V <= %d)", V,
                VT_SAMPLE_ROWS_MAX_V);
-    hipLaunchKernelGGL(sample_rows_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, out_ids, kept_count, logprob);
+    if (allow)
+      hipLaunchKernelGGL(sample_rows_allow_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, allow, out_ids,
+                         kept_count, logprob);
+    else
+      hipLaunchKernelGGL(sample_rows_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, out_ids, kept_count, logprob);
   }
   VT_LAUNCH_CHECK();
   return VT_OK;

@@ -457,13 +457,20 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
     def generate(self, input_ids=None, images=None, regions=None, attention_mask=None, do_sample=False,
                  temperature=1.0, top_p=1.0, top_k=None, max_new_tokens=None, max_length=None, use_cache=True,
                  stopping_criteria=None, eos_token_id=None, pad_token_id=None, num_beams=1, seed=None,
-                 return_logits=False, padded_batch=False, repetition_penalty=1.0, return_logprobs=False, **kwargs):
+                 return_logits=False, padded_batch=False, repetition_penalty=1.0, return_logprobs=False, suppress_tokens=None,
+                 begin_suppress_tokens=None, min_new_tokens=None, bad_words_ids=None, allowed_token_ids=None, **kwargs):
         """repetition_penalty (RepetitionPenaltyLogitsProcessor; 1.0 is off) and return_logprobs: with both at their defaults a step
         launches what it always did (vt_argmax / vt_sample_top_p). Otherwise every step is ONE vt_sample_rows launch (row b: stream = b,
         counter = step -- today's draws) whose penalty history -- the sample's non-negative prompt ids plus what it has generated -- lives
         and grows on the device. return_logprobs=True additionally returns a [B, n_new] fp32 tensor: log_softmax of the raw logits at every
         emitted id (for a row that has finished, of the id it would have emitted instead of the pad). Returns ids; (ids, all_logits) with
         return_logits; the log-probabilities come last: (ids, logprobs) or (ids, all_logits, logprobs).
+        Constraints on which ids may be emitted at all, for the whole batch: suppress_tokens
+        (SuppressTokensLogitsProcessor), begin_suppress_tokens (BeginSuppressTokensLogitsProcessor: the first generated token only),
+        min_new_tokens (MinNewTokensLengthLogitsProcessor: the EOS ids are banned while fewer tokens have been generated), bad_words_ids
+        (NoBadWordsLogitsProcessor, single-token entries only; a longer entry raises NotImplementedError) and this project's own
+        allowed_token_ids (only these ids). With any of them every step is ONE vt_sample_rows_allow launch; the few distinct masks a call
+        needs and the per-step pointer array are uploaded once before the loop. At the defaults nothing changes.
         padded_batch=True (B > 1, right padding): reproduce what the REFERENCE's batched generate() returns -- transformers 4.31 reads the
         first token of every sample from the last COLUMN of the padded logits (a pad row for the shorter samples) and the decode-step
         fix-up (llava_arch.py:196-205) attends the pad rows of the spliced batch while masking the rows that share an index with the
@@ -493,6 +500,47 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         check_sampling_values(temperature if do_sample else 0.0, top_p if (do_sample and top_p) else 1.0, int(top_k or 0), repetition_penalty,
                               "generate")
         use_rows = float(repetition_penalty) != 1.0 or bool(return_logprobs)
+        # ---- allow masks (constrained decoding): which ids any row may emit at step st, a pure function of st
+        banned_always = [int(t) for t in (suppress_tokens or ())]
+        for w in (bad_words_ids or ()):
+            if len(w) != 1:
+                raise NotImplementedError(f"generate(bad_words_ids=...): the multi-token entry {list(w)!r} is not implemented (single-token "
+                                          "entries only: the constraint is a mask over ids)")
+            banned_always.append(int(w[0]))
+        banned_begin = [int(t) for t in (begin_suppress_tokens or ())]
+        min_new = int(min_new_tokens or 0)
+        if min_new < 0:
+            raise ValueError(f"generate: min_new_tokens must be >= 0, got {min_new_tokens!r}")
+        allowed_ids = None if allowed_token_ids is None else [int(t) for t in allowed_token_ids]
+        allow_ptrs = None
+        if banned_always or banned_begin or allowed_ids is not None or (min_new > 0 and eos_set):
+            # at most four distinct masks (the first step / before min_new_tokens / after), uploaded ONCE with every step's pointer array
+            import numpy as np
+
+            from ...sampling import allow_mask
+            V = int(self.config.vocab_size)
+            eos_in = [int(e) for e in eos_set if 0 <= int(e) < V]
+            masks = {}
+            step_key = []
+            for st in range(max(int(max_new_tokens), 0)):
+                key = (st == 0 and bool(banned_begin), st < min_new and bool(eos_in))
+                if key not in masks:
+                    banned = banned_always + (banned_begin if key[0] else []) + (eos_in if key[1] else [])
+                    m = allow_mask(V, allowed_ids, banned)
+                    if not m.any():
+                        raise ValueError(f"generate: the constraints leave no token to emit at step {st}")
+                    masks[key] = None if (allowed_ids is None and not banned) else m
+                step_key.append(key)
+            live = [k for k, m in masks.items() if m is not None]
+            if live:     # (min_new_tokens without an EOS id in [0, V), or no step at all, masks nothing: the call stays what it was)
+                allow_dev = torch.from_numpy(np.stack([masks[k] for k in live]).view("<i4")).to(dev)            # [n_masks, words]
+                addr = {k: allow_dev[i].data_ptr() for i, k in enumerate(live)}
+                allow_ptrs = torch.tensor([[addr.get(k, 0)] * B for k in step_key], dtype=torch.int64).to(dev)    # [steps, B]
+        constrained = allow_ptrs is not None
+        if constrained and padded_batch:
+            raise NotImplementedError("generate(padded_batch=True) does not take suppress_tokens / begin_suppress_tokens / min_new_tokens / "
+                                      "bad_words_ids / allowed_token_ids; use the default packed batch")
+        use_rows = use_rows or constrained
 
         reuse = B == 1 and bool(getattr(self.config, "kv_prefix_reuse", True))
         cache = None
@@ -623,6 +671,8 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                  for st in range(max_new_tokens) for b in range(B)], dev).view(max_new_tokens, B, ROW_BYTES)
         try:   # (the prefill is inside: pages it took before a failure go back to the pool / the kept prefix below)
             logits = llama_forward(llama, self.kv, seqs, flat, lens, embeds_lo=flat_lo)     # [B, V]: last position of every sequence
+            if allow_ptrs is not None and logits.shape[1] != int(self.config.vocab_size):
+                raise RuntimeError(f"generate: the allow masks were built for V = {self.config.vocab_size}, the logits have {logits.shape[1]} columns")
             if pad_mode:
                 from ...engine import padded_batch_fixup
                 fix = padded_batch_fixup(llama, self.kv, seqs, S, ids_valid, input_ids.shape[1])
@@ -634,7 +684,8 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                 if return_logits:
                     all_logits.append(logits.clone())
                 if use_rows:    # per-row sampler: penalty over the device history, greedy or sampled, the chosen token's log-probability
-                    nxt = ops.sample_rows(logits, row_params[step], return_logprob=bool(return_logprobs))
+                    nxt = ops.sample_rows(logits, row_params[step], return_logprob=bool(return_logprobs),
+                                          _allow_ptrs=None if allow_ptrs is None else allow_ptrs[step])
                     if return_logprobs:
                         nxt, lp = nxt
                         all_lp.append(lp)

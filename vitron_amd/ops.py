@@ -508,10 +508,36 @@ def sample_top_p(logits: torch.Tensor, temperature: float, top_p: float, seed: i
     return (out, kept) if return_kept else out
 
 
-def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = False, return_logprob: bool = False):
+def allow_pointers(allow, rows: int, V: int, device) -> torch.Tensor:
+    """The device pointer array vt_sample_rows_allow reads (int64 [rows]) from one entry per row: None (NULL: everything allowed) or a
+    contiguous int32 / uint32 device tensor of ceil(V / 32) mask words (sampling.allow_mask). The caller keeps the masks alive until
+    the launch has run. One small host -> device copy."""
+    words = (V + 31) // 32
+    if isinstance(allow, torch.Tensor) or not hasattr(allow, "__len__") or len(allow) != rows:
+        raise _lib.VitronHipError(f"sample_rows.allow: expected a sequence of {rows} entries (one per row), each None or a mask tensor")
+    mask_dtypes = tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)
+    ptrs = []
+    for i, m in enumerate(allow):
+        if m is None:
+            ptrs.append(0)
+            continue
+        if not isinstance(m, torch.Tensor) or m.device != device or m.dtype not in mask_dtypes or not m.is_contiguous() \
+                or m.numel() != words:
+            raise _lib.VitronHipError(f"sample_rows.allow[{i}]: expected None or a contiguous int32 / uint32 tensor of {words} words "
+                                      f"(ceil(V / 32), V = {V}) on the logits' device")
+        ptrs.append(m.data_ptr())
+    return torch.tensor(ptrs, dtype=torch.int64).to(device)
+
+
+def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = False, return_logprob: bool = False, allow=None,
+                _allow_ptrs: Optional[torch.Tensor] = None):
     """One token id per row (int32, on device) with PER-ROW parameters: greedy and sampled rows, penalties and the chosen token's
     log-probability in one launch; see vt_sample_rows in include/vitron_hip.h. `params`: the device array of vt_sample_row that
-    sampling.pack_sample_rows builds (uint8 [rows, 48]). Returns ids, or (ids[, kept_count][, logprob]) when either is asked for."""
+    sampling.pack_sample_rows builds (uint8 [rows, 48]). Returns ids, or (ids[, kept_count][, logprob]) when either is asked for.
+    allow: per-row allow masks (vt_sample_rows_allow) -- a sequence of `rows` entries, each None or a device tensor of ceil(V / 32)
+    mask words; each is checked and the pointer array is built here. None: today's vt_sample_rows call.
+    _allow_ptrs (private; generate's single upload, tools/sampler_bench.py): a pointer array that allow_pointers -- or its caller, from
+    masks it has checked itself -- built earlier, int64 [rows]; its values are dereferenced on the device as they are."""
     from .sampling import ROW_BYTES
     lib = _lib.load_any()
     _chk_rows(logits, torch.float32, "sample_rows.logits")
@@ -523,8 +549,21 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = 
     out = torch.empty((rows,), device=logits.device, dtype=torch.int32)
     kept = torch.empty((rows,), device=logits.device, dtype=torch.int32) if return_kept else None
     lp = torch.empty((rows,), device=logits.device, dtype=torch.float32) if return_logprob else None
-    _lib.check(lib.vt_sample_rows(_p(logits), rows, V, logits.stride(0), _p(params), _p(out), _p(kept), _p(lp), _stream()),
-               "vt_sample_rows", lib)
+    if allow is not None and _allow_ptrs is not None:
+        raise _lib.VitronHipError("sample_rows: pass allow or _allow_ptrs, not both")
+    if allow is None and _allow_ptrs is None:
+        _lib.check(lib.vt_sample_rows(_p(logits), rows, V, logits.stride(0), _p(params), _p(out), _p(kept), _p(lp), _stream()),
+                   "vt_sample_rows", lib)
+    else:
+        if _allow_ptrs is not None:
+            ptrs = _allow_ptrs
+            if not isinstance(ptrs, torch.Tensor) or ptrs.dtype != torch.int64 or ptrs.device != logits.device or not ptrs.is_contiguous() \
+                    or ptrs.numel() != rows:
+                raise _lib.VitronHipError(f"sample_rows._allow_ptrs: expected a contiguous int64 [{rows}] tensor on the logits' device")
+        else:
+            ptrs = allow_pointers(allow, rows, V, logits.device)
+        _lib.check(lib.vt_sample_rows_allow(_p(logits), rows, V, logits.stride(0), _p(params), _p(ptrs), _p(out), _p(kept), _p(lp),
+                                            _stream()), "vt_sample_rows_allow", lib)
     res = (out,) + ((kept,) if return_kept else ()) + ((lp,) if return_logprob else ())
     return res if len(res) > 1 else out
 

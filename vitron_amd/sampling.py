@@ -2,13 +2,17 @@
 
 `SamplingParams` is what a caller hands to `ServingEngine.submit(..., sampling=)`; `pack_sample_rows` turns one tuple per logits row
 into the array `ops.sample_rows` / `vt_sample_rows` reads: one numpy structured array, one small host -> device copy.
+
+Constrained decoding: which ids a request may emit at all is a V-bit allow mask per row (`allow_mask`, the layout of
+vt_sample_rows_allow). `SamplingParams` carries the constraints; `step_allow_mask` is the pure host function that turns them and the
+tokens generated so far into the mask of the next pick.
 """
 from __future__ import annotations
 
 import math
 import numbers
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import Callable, Dict, Iterable, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -49,8 +53,26 @@ class SamplingParams:
     seed: int = 0
     repetition_penalty: float = 1.0
     logprobs: bool = False
+    # ---- constraints: which ids the request may emit at all (all off by default; they compose by intersection) ----
+    allowed_token_ids: Optional[Tuple[int, ...]] = None      # only these ids, at every step
+    banned_token_ids: Optional[Tuple[int, ...]] = None       # never these (SuppressTokensLogitsProcessor, single-token NoBadWords)
+    min_new_tokens: int = 0                                  # the request's EOS ids are banned while it has generated fewer tokens
+    choices: Optional[Tuple[Tuple[int, ...], ...]] = None    # the reply is exactly one of these id sequences, followed by EOS
+    allowed_tokens_fn: Optional[Callable] = None             # generated ids -> iterable of allowed ids, or None (PrefixConstrained)
 
     def __post_init__(self):
+        def ids(x, what):
+            if x is None:
+                return None
+            if isinstance(x, (str, bytes)) or not hasattr(x, "__iter__"):
+                raise ValueError(f"SamplingParams: {what} must be a sequence of token ids, got {x!r}")
+            return tuple(_as_id(t, what) for t in x)
+        object.__setattr__(self, "allowed_token_ids", ids(self.allowed_token_ids, "allowed_token_ids"))
+        object.__setattr__(self, "banned_token_ids", ids(self.banned_token_ids, "banned_token_ids"))
+        if self.choices is not None:
+            if isinstance(self.choices, (str, bytes)) or not hasattr(self.choices, "__iter__"):
+                raise ValueError(f"SamplingParams: choices must be a sequence of token-id sequences, got {self.choices!r}")
+            object.__setattr__(self, "choices", tuple(ids(c, "choices") for c in self.choices))
         self.validate()
 
     def validate(self) -> None:
@@ -59,11 +81,150 @@ class SamplingParams:
             raise ValueError(f"SamplingParams: seed must be an int, got {self.seed!r}")
         if not isinstance(self.logprobs, bool):
             raise ValueError(f"SamplingParams: logprobs must be a bool, got {self.logprobs!r}")
+        if not isinstance(self.min_new_tokens, numbers.Integral) or isinstance(self.min_new_tokens, bool) or self.min_new_tokens < 0:
+            raise ValueError(f"SamplingParams: min_new_tokens must be an int >= 0, got {self.min_new_tokens!r}")
+        if self.allowed_token_ids is not None and len(self.allowed_token_ids) == 0:
+            raise ValueError("SamplingParams: allowed_token_ids is empty: nothing could be emitted")
+        if self.choices is not None and (len(self.choices) == 0 or any(len(c) == 0 for c in self.choices)):
+            raise ValueError("SamplingParams: choices must hold at least one choice and no empty one")
+        if self.allowed_tokens_fn is not None and not callable(self.allowed_tokens_fn):
+            raise ValueError(f"SamplingParams: allowed_tokens_fn must be callable, got {self.allowed_tokens_fn!r}")
+
+    @property
+    def constrained(self) -> bool:
+        return (self.allowed_token_ids is not None or bool(self.banned_token_ids) or self.min_new_tokens > 0
+                or self.choices is not None or self.allowed_tokens_fn is not None)
 
     def resolved_top_k(self, config=None) -> int:
         if self.top_k is not None:
             return int(self.top_k)
         return int(getattr(config, "top_k", 50) or 0)
+
+
+def _as_id(t, what: str) -> int:
+    if not isinstance(t, numbers.Integral) or isinstance(t, bool):
+        raise ValueError(f"SamplingParams: {what} holds {t!r}, not a token id")
+    return int(t)
+
+
+# ---- allow masks: the word / bit layout of vt_sample_rows_allow ---------------------------------------------------------------------
+def mask_words(V: int) -> int:
+    return (int(V) + 31) // 32
+
+
+def allow_mask(V: int, allowed: Optional[Iterable[int]] = None, banned: Optional[Iterable[int]] = None) -> np.ndarray:
+    """uint32 [ceil(V / 32)]: token i may be chosen iff bit (i & 31) of word (i >> 5) is set. The allowed set (every id of [0, V) when
+    None) minus the banned ids; bits at positions >= V stay clear. An id outside [0, V) is a ValueError."""
+    V = int(V)
+    if V <= 0:
+        raise ValueError(f"allow_mask: V must be > 0, got {V}")
+
+    def ids(x, what):
+        a = np.asarray(x if isinstance(x, np.ndarray) else list(x), dtype=np.int64).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() >= V):
+            bad = a[(a < 0) | (a >= V)]
+            raise ValueError(f"allow_mask: {what} id {int(bad[0])} is outside [0, {V})")
+        return a
+    bits = np.zeros((mask_words(V) * 32,), dtype=bool)
+    if allowed is None:
+        bits[:V] = True
+    else:
+        bits[ids(allowed, "allowed")] = True
+    if banned is not None:
+        bits[ids(banned, "banned")] = False
+    return np.packbits(bits, bitorder="little").view("<u4").astype(np.uint32)
+
+
+def mask_ids(mask: np.ndarray, V: int) -> np.ndarray:
+    """The ids in [0, V) whose bit is set (the inverse of allow_mask)."""
+    bits = np.unpackbits(np.ascontiguousarray(mask, dtype="<u4").view(np.uint8), bitorder="little")[:V]
+    return np.nonzero(bits)[0]
+
+
+class TokenTrie:
+    """The choices of SamplingParams.choices as a trie over token ids: node = the ids generated so far; `children(prefix)` are the ids
+    that may come next, `ends(prefix)` says whether the prefix is a complete choice (EOS may follow)."""
+
+    def __init__(self, choices: Sequence[Sequence[int]]):
+        self.root: dict = {}
+        for c in choices:
+            node = self.root
+            for t in c:
+                node = node.setdefault(int(t), {})
+            node[None] = True               # end marker: a choice ends at this node
+
+    def _node(self, prefix: Sequence[int]):
+        node = self.root
+        for t in prefix:
+            node = node.get(int(t))
+            if node is None:
+                return None
+        return node
+
+    def children(self, prefix: Sequence[int]) -> list:
+        node = self._node(prefix)
+        return [] if node is None else sorted(t for t in node if t is not None)
+
+    def ends(self, prefix: Sequence[int]) -> bool:
+        node = self._node(prefix)
+        return node is not None and None in node
+
+
+def step_allow_mask(sampling: Optional[SamplingParams], n_generated: int, tokens: Sequence[int], eos: Iterable[int], V: int,
+                    cache: Optional[Dict] = None):
+    """The allow mask of a request's NEXT pick as a pure host function of (sampling, tokens generated so far, the request's EOS ids):
+    returns (key, mask). mask is None when the step is unconstrained (the row passes NULL), else uint32 [ceil(V / 32)]. key names a
+    mask that does not depend on the tokens ("pre": fewer than min_new_tokens generated, "post": after) so that its device copy can be
+    kept; it is None for a step-dependent mask (choices, allowed_tokens_fn). `cache` (a dict the caller keeps per request) holds the
+    static masks and the trie between calls. All constraints intersect; an empty result is a ValueError."""
+    if sampling is None or not sampling.constrained:
+        return None, None
+    cache = {} if cache is None else cache
+    eos_in = sorted(int(e) for e in eos if isinstance(e, numbers.Integral) and 0 <= int(e) < V)
+    key = "pre" if n_generated < sampling.min_new_tokens else "post"
+    if key not in cache:
+        static = None
+        banned = list(sampling.banned_token_ids or ()) + (eos_in if key == "pre" else [])
+        if sampling.allowed_token_ids is not None or banned:
+            static = allow_mask(V, sampling.allowed_token_ids, banned)
+            if not static.any():
+                raise ValueError(f"sampling constraints leave no token to emit ({'before' if key == 'pre' else 'after'} min_new_tokens)")
+        cache[key] = static
+    mask = cache[key]
+    dynamic = False
+    if sampling.choices is not None:
+        if not eos_in:
+            raise ValueError(f"choices need an EOS id inside [0, {V}) to end the reply")
+        trie = cache.get("trie")
+        if trie is None:
+            trie = cache["trie"] = TokenTrie(sampling.choices)
+        nxt = trie.children(tokens) + (eos_in if trie.ends(tokens) else [])
+        step = allow_mask(V, nxt)
+        mask, dynamic = step if mask is None else (mask & step), True
+    if sampling.allowed_tokens_fn is not None:
+        got = sampling.allowed_tokens_fn(list(tokens))
+        if got is not None:
+            step = allow_mask(V, got)
+            mask, dynamic = step if mask is None else (mask & step), True
+    if mask is not None and dynamic and not mask.any():
+        raise ValueError(f"sampling constraints leave no token to emit after {n_generated} generated token(s)")
+    return (None if dynamic else (key if mask is not None else None)), mask
+
+
+def check_constraints(sampling: Optional[SamplingParams], eos: Iterable[int], V: int) -> None:
+    """What submit() refuses before anything is queued: ids outside [0, V), choices without an EOS id in [0, V), a combination that
+    leaves nothing to emit (the static masks before / after min_new_tokens and the first step of `choices`; allowed_tokens_fn is not
+    called here)."""
+    if sampling is None or not sampling.constrained:
+        return
+    import dataclasses
+    sp = dataclasses.replace(sampling, allowed_tokens_fn=None)
+    for c in sp.choices or ():
+        allow_mask(V, c)
+    cache: Dict = {}
+    step_allow_mask(sp, 0, [], eos, V, cache)
+    if sp.min_new_tokens > 0:
+        step_allow_mask(dataclasses.replace(sp, choices=None), sp.min_new_tokens, [], eos, V, {})
 
 
 def sample_rows_array(rows: Sequence[tuple]) -> np.ndarray:

@@ -35,7 +35,7 @@ import torch
 
 from . import ops
 from .engine import PagedKVCache, SequenceState, llama_forward, pair_lo, parse_kv_cache_dtype
-from .sampling import SamplingParams, pack_sample_rows
+from .sampling import SamplingParams, check_constraints, pack_sample_rows, step_allow_mask
 
 
 @dataclass
@@ -59,6 +59,11 @@ class _Request:
     hist_len: int = 0
     last_lp: Optional[torch.Tensor] = None   # device fp32 [1]: log-probability of `last` (sampling.logprobs)
     logprobs: List[float] = field(default_factory=list)
+    allow_host: dict = field(default_factory=dict)   # step_allow_mask's cache: the static host masks, the choices trie
+    allow_dev: dict = field(default_factory=dict)    # static masks on the device ("pre" / "post"): uploaded once, released with hist
+    allow_cur: Optional[torch.Tensor] = None         # the mask of the next pick (a static one, a step-dependent upload, or None)
+    allow_at: int = -1                               # len(tokens) `allow_cur` was prepared for
+    mask_uploads: int = 0                            # host -> device mask copies this request has cost
 
 
 class ServingEngine:
@@ -104,6 +109,8 @@ class ServingEngine:
             sampling.validate()
         eos = self.model.config.eos_token_id if eos_token_id is None else eos_token_id
         eos_set = frozenset(eos) if isinstance(eos, (list, tuple, set, frozenset)) else (frozenset([eos]) if eos is not None else frozenset())
+        if sampling is not None and sampling.constrained:
+            check_constraints(sampling, eos_set, int(self.model.config.vocab_size))     # ValueError: nothing is queued
         r = _Request(self._next_id, ids.to(self.model.device), images, regions, int(max_new_tokens), eos_set, sampling=sampling)
         self._next_id += 1
         self.waiting.append(r)
@@ -118,6 +125,7 @@ class ServingEngine:
             if r.rid == rid:
                 self.waiting.remove(r)
                 r.flat = None
+                self._drop_masks(r)
                 return True
         return False
 
@@ -126,6 +134,7 @@ class ServingEngine:
         if r.seq.pages:
             self.model.kv.release(r.seq.pages)
         r.seq.pages, r.seq.length, r.last, r.flat, r.hist, r.last_lp = [], 0, None, None, None, None
+        self._drop_masks(r)
         r.error, r.done = exc, True
         self.failed[r.rid] = r
 
@@ -134,13 +143,39 @@ class ServingEngine:
         """Errors that are not one request's fault: the HIP runtime (status -2 of the C ABI), the allocator."""
         return isinstance(exc, torch.cuda.OutOfMemoryError) or "status -2" in str(exc) or "HIP error" in str(exc)
 
+    @staticmethod
+    def _drop_masks(r: _Request) -> None:
+        r.allow_dev, r.allow_host, r.allow_cur, r.allow_at = {}, {}, None, -1
+
+    def _prepare_allow(self, r: _Request) -> None:
+        """The allow mask of r's next pick: a pure host function of (r.sampling, r.tokens, r.eos) -- the host has read back
+        every token r has generated before the pick that follows. A static mask is uploaded once and kept on the request; a
+        step-dependent one (choices, allowed_tokens_fn) is one ceil(V / 32) * 4-byte upload for this row. Raises ValueError when the
+        constraints leave nothing to emit (the caller fails this request alone)."""
+        n = len(r.tokens)
+        if r.allow_at == n:
+            return
+        key, mask = step_allow_mask(r.sampling, n, r.tokens, r.eos, int(self.model.config.vocab_size), r.allow_host)
+        if mask is None:
+            r.allow_cur = None
+        elif key is not None and key in r.allow_dev:
+            r.allow_cur = r.allow_dev[key]
+        else:
+            r.allow_cur = torch.from_numpy(mask.view("<i4")).to(self.model.device)
+            r.mask_uploads += 1
+            if key is not None:
+                r.allow_dev[key] = r.allow_cur
+        r.allow_at = n
+
     # ---- one scheduling step ---------------------------------------------------------------------------------------------
     def _pick(self, logits: torch.Tensor, reqs: Optional[List[_Request]] = None) -> torch.Tensor:
         """One token per logits row (row i belongs to reqs[i]). While no row's request carries `sampling` this is the launch it always
         was: ops.argmax, or ops.sample_top_p with the engine's scalars. Otherwise ONE ops.sample_rows launch serves every row: a request
         with `sampling` draws from (its seed, the number of tokens it has generated, stream 0); a request without gets the parameters
         that reproduce its legacy draw (the engine's temperature / top_p, top_k 0, the engine's seed, counter = the engine's step,
-        stream = its batch row; greedy when the engine does not sample). Log-probabilities land in r.last_lp."""
+        stream = its batch row; greedy when the engine does not sample). Log-probabilities land in r.last_lp.
+        A request whose SamplingParams carry a constraint passes its allow mask (_prepare_allow) and the launch is vt_sample_rows_allow;
+        rows without one, and legacy rows, pass NULL. While no row has a mask the launches are exactly the ones above."""
         if reqs is None or all(r.sampling is None for r in reqs):
             if self.do_sample:
                 return ops.sample_top_p(logits, self.temperature, self.top_p, self.seed, self._step)
@@ -159,7 +194,15 @@ class ServingEngine:
             rows.append((sp.temperature, sp.resolved_top_k(self.model.config), sp.top_p, sp.repetition_penalty, sp.seed, len(r.tokens), 0,
                          r.hist.data_ptr() if r.hist is not None else 0, r.hist_len if r.hist is not None else 0))
         want_lp = any(r.sampling is not None and r.sampling.logprobs for r in reqs)
-        res = ops.sample_rows(logits, pack_sample_rows(rows, logits.device), return_logprob=want_lp)
+        allow = None
+        if any(r.sampling is not None and r.sampling.constrained for r in reqs):
+            for r in reqs:
+                if r.sampling is not None and r.sampling.constrained:
+                    self._prepare_allow(r)
+            allow = [r.allow_cur for r in reqs]
+            if all(a is None for a in allow):
+                allow = None
+        res = ops.sample_rows(logits, pack_sample_rows(rows, logits.device), return_logprob=want_lp, allow=allow)
         ids, lp = res if want_lp else (res, None)
         for i, r in enumerate(reqs):
             if r.sampling is not None and r.sampling.logprobs:
@@ -253,6 +296,16 @@ class ServingEngine:
 
         try:
             if self.batch_prefill and len(admitted) > 1:
+                for r in list(admitted):                    # the first pick's masks before the shared forward, as step() does: a request
+                    if r.sampling is not None and r.sampling.constrained:     # whose constraints leave nothing fails here, alone and once
+                        try:
+                            self._prepare_allow(r)
+                        except Exception as e:  # noqa: BLE001
+                            if self._is_device_error(e):
+                                raise
+                            admitted.remove(r)
+                            self._fail(r, e)
+            if self.batch_prefill and len(admitted) > 1:
                 try:
                     flats = [r.flat for r in admitted]
                     los = [getattr(r, "flat_lo", None) for r in admitted]
@@ -292,6 +345,7 @@ class ServingEngine:
         self.model.kv.release(r.seq.pages)
         r.seq.pages = []
         r.hist = r.last_lp = None
+        self._drop_masks(r)
         self.finished[r.rid] = r
 
     def step(self) -> List[Tuple[int, int]]:
@@ -319,6 +373,15 @@ class ServingEngine:
                 self._retire(r)
             else:
                 still.append(r)
+        for r in list(still):        # the masks of the coming pick, before the forward: a request whose constraints leave nothing fails alone
+            if r.sampling is not None and r.sampling.constrained:
+                try:
+                    self._prepare_allow(r)
+                except Exception as e:  # noqa: BLE001 -- the request's own constraint (allowed_tokens_fn included)
+                    if self._is_device_error(e):
+                        raise
+                    still.remove(r)
+                    self._fail(r, e)
         self.active = still
         if self.active:
             m = self.model
