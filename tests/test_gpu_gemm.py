@@ -432,3 +432,16 @@ def test_refusals_leave_c_untouched(dev):
     got = ops.gemm(ok_a, ok_w, None, EPI_BF16, out=cbuf[:, :N])
     torch.cuda.synchronize()
     assert bool((got.float() == K).all()) and bool(torch.isnan(cbuf[:, N:].float()).all())
+    # an epilogue id outside the seven public values is refused for every configuration (K = 256: nothing else is wrong for any of them);
+    # 0x1000 .. 0x10000 used to select a kernel family by accident, 0x4005 stored fp32 into a C laid out for 16 bits
+    K3 = 256
+    a3, w3 = torch.ones((M, K3), dtype=dtype, device=dev), torch.ones((N, K3), dtype=dtype, device=dev)
+    cbuf.fill_(NAN)
+    for cfg in (0, 5, 6, 10, 13, 15):
+        for e in (7, 11, -1, 0x1000, 0x4000, 0x4005, 0x10000):
+            refused(f"epilogue id {e:#x} on cfg {cfg}", lambda: ops.gemm(a3, w3, None, e, out=cbuf[:, :N], cfg=cfg))
+    for cfg in (0, 5, 6, 10, 13, 15):
+        cbuf.fill_(NAN)
+        got = ops.gemm(a3, w3, None, EPI_BF16, out=cbuf[:, :N], cfg=cfg)
+        torch.cuda.synchronize()
+        assert bool((got.float() == K3).all()) and bool(torch.isnan(cbuf[:, N:].float()).all()), f"EPI_BF16 on cfg {cfg}"

@@ -221,5 +221,16 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return base + idx;
 }
 
+// ---- grouped tile order of the GEMM tile kernels -------------------------------------------------
+// Place sid of the logical order -> tile (tm, tn): groups of group_m tile rows (the last group may be shorter), every group
+// swept along N with the rows of a group innermost, so concurrent workgroups share A and W tiles in L2.
+__device__ __forceinline__ void grouped_tile(int sid, int tiles_m, int tiles_n, int group_m, int& tm, int& tn) {
+  const int per_group = group_m * tiles_n;
+  const int first_m = (sid / per_group) * group_m;
+  const int gsz = min(tiles_m - first_m, group_m);
+  tm = first_m + (sid % per_group) % gsz;
+  tn = (sid % per_group) / gsz;
+}
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }

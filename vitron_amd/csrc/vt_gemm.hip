@@ -77,13 +77,8 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) void gemm_bt_kernel(GemmP p
   const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
   const int nwg = tiles_m * tiles_n;
   const int sid = xcd_remap(blockIdx.x, nwg);
-  constexpr int GROUP_M = 8;
-  const int per_group = GROUP_M * tiles_n;
-  const int gid = sid / per_group;
-  const int first_m = gid * GROUP_M;
-  const int gsz = min(tiles_m - first_m, GROUP_M);
-  const int tm = first_m + (sid % per_group) % gsz;
-  const int tn = (sid % per_group) / gsz;
+  int tm, tn;
+  grouped_tile(sid, tiles_m, tiles_n, 8, tm, tn);
   const int bm0 = tm * BM, bn0 = tn * BN;
 
   // ---- per-lane DMA source pointers (k = 0), advanced by BK elements per K tile -----------------
@@ -912,6 +907,9 @@ int vt_gemm_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, 
   VT_REQUIRE(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0 && ((uintptr_t)C % 16) == 0,
              "vt_gemm: A/W/C must be 16-byte aligned");
   VT_REQUIRE(ldc % 4 == 0, "vt_gemm: ldc must be a multiple of 4");
+  VT_REQUIRE(VtEpisPublic::has(epi), "vt_gemm: unknown epilogue %d", epi);
+  if (epi == VT_EPI_SWIGLU_BF16) VT_REQUIRE((N % 32) == 0, "vt_gemm(swiglu): N must be a multiple of 32");
+  const size_t esz = (epi == VT_EPI_F32 || epi == VT_EPI_F32_RESID) ? 4 : 2;   // bytes per element of C
   if (nf && !nf->row_scale && !nf->out_partials) nf = nullptr;
   if (nf) {   // folded RMSNorm on the MFMA tile kernels (vt_kernels.h)
     const bool tile_cfg = cfg == VT_GEMM_CFG_AUTO || cfg == VT_GEMM_CFG_256x256_P4 || cfg == VT_GEMM_CFG_256x256_P8 ||
@@ -931,7 +929,6 @@ int vt_gemm_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, 
   // stream), so the rows go through that kernel in two groups of 32 -- the weights are streamed twice (the repeat mostly from
   // the Infinity Cache), still faster than the tile grid up to N = 16384 (tools/skinny_bench.py).
   if (!nf && cfg == VT_GEMM_CFG_AUTO && M > 32 && M <= 64 && (K % 64) == 0 && N <= 16384) {
-    const size_t esz = (epi == VT_EPI_F32 || epi == VT_EPI_F32_RESID) ? 4 : 2;
     for (int m0 = 0; m0 < M; m0 += 32)
       VT_TRY(vt_gemm_launch(A + (size_t)m0 * lda, lda, W, ldw, (char*)C + (size_t)m0 * ldc * esz, ldc, bias, std::min(32, M - m0), N, K,
                             epi, VT_GEMM_CFG_SKINNY, s));
@@ -946,14 +943,12 @@ int vt_gemm_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, 
       const VtGemmPlan plan = vt_gemm_plan(M, N, K, epi, nf);
       cfg = plan.cfg;
       if (plan.N1 > 0) {   // column split: whole rounds of big tiles over the first N1 columns, the tail columns planned again
-        const size_t esz = (epi == VT_EPI_F32 || epi == VT_EPI_F32_RESID) ? 4 : 2;
         const size_t c_off = (epi == VT_EPI_SWIGLU_BF16 ? plan.N1 / 2 : plan.N1) * esz;     // SwiGLU: one output column per gate/up pair
         VT_TRY(vt_gemm_launch(A, lda, W, ldw, C, ldc, bias, M, plan.N1, K, epi, plan.cfg, s, nullptr));
         return vt_gemm_launch(A, lda, W + (size_t)plan.N1 * ldw, ldw, (char*)C + c_off, ldc, bias ? bias + plan.N1 : nullptr, M, N - plan.N1, K,
                               epi, VT_GEMM_CFG_AUTO, s, nullptr);
       }
       if (plan.M1 > 0) {
-        const size_t esz = (epi == VT_EPI_F32 || epi == VT_EPI_F32_RESID) ? 4 : 2;
         VT_TRY(vt_gemm_launch(A, lda, W, ldw, C, ldc, bias, plan.M1, N, K, epi, plan.cfg, s, nf));
         const VtGemmNormFuse rest = nf ? vt_nf_rows(*nf, plan.M1) : VtGemmNormFuse{};
         return vt_gemm_launch(A + (size_t)plan.M1 * lda, lda, W, ldw, (char*)C + (size_t)plan.M1 * ldc * esz, ldc, bias, M - plan.M1, N, K,
@@ -967,43 +962,24 @@ int vt_gemm_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, 
   if (skinny_path) {
     const bool fma = cfg == VT_GEMM_CFG_SKINNY_REG;   // register-operand kernel on request; it is also the ragged-K fallback
     VT_REQUIRE((K % 8) == 0, "vt_gemm(skinny): K=%d must be a multiple of 8", K);
-    switch (epi) {
-      case VT_EPI_BF16: return launch_skinny<VT_EPI_BF16>(p, s, fma);
-      case VT_EPI_BF16_GELU: return launch_skinny<VT_EPI_BF16_GELU>(p, s, fma);
-      case VT_EPI_BF16_QGELU: return launch_skinny<VT_EPI_BF16_QGELU>(p, s, fma);
-      case VT_EPI_BF16_RELU: return launch_skinny<VT_EPI_BF16_RELU>(p, s, fma);
-      case VT_EPI_F32_RESID: return launch_skinny<VT_EPI_F32_RESID>(p, s, fma);
-      case VT_EPI_F32: return launch_skinny<VT_EPI_F32>(p, s, fma);
-      case VT_EPI_SWIGLU_BF16:
-        VT_REQUIRE((N % 32) == 0, "vt_gemm(swiglu): N must be a multiple of 32");
-        return launch_skinny<VT_EPI_SWIGLU_BF16>(p, s, fma);
-      default: vt_set_error("vt_gemm: unknown epilogue %d", epi); return VT_ERR_ARG;
-    }
+    return vt_with_epi<VtEpisPublic>(epi, "vt_gemm", [&](auto e) { return launch_skinny<decltype(e)::value>(p, s, fma); });
   }
-  VT_REQUIRE((K % 64) == 0, "vt_gemm(tile): K=%d must be a multiple of 64", K);
-  if (epi == VT_EPI_SWIGLU_BF16) VT_REQUIRE((N % 32) == 0, "vt_gemm(swiglu): N must be a multiple of 32");
-  if (cfg == VT_GEMM_CFG_256x256_P8) return vt_gemm_p8_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, epi, s, nf);
-#ifdef VT_ABLATIONS   // timing ablations / main-loop A/B variants (results are garbage for 100..117): test library only
-  if (cfg >= 111 && cfg < 118) return vt_gemm_p8_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, ((cfg - 110) << 8) | 0x1000, s);
-  if (cfg >= 100 && cfg < 108) return vt_gemm_p8_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, (cfg - 100) << 8, s);
-  if (cfg >= 301 && cfg <= 303) return vt_gemm_rp_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, (cfg - 300) << 8, s);
+  switch (cfg) {
+    case VT_GEMM_CFG_256x256_P8:
+    case VT_GEMM_CFG_256x256_P4:
+    case VT_GEMM_CFG_256x256_W4:
+    case VT_GEMM_CFG_320x256_W4:
+    case VT_GEMM_CFG_224x256_W4:
+    case VT_GEMM_CFG_160x128_W4: return vt_gemm_p8_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, epi, cfg, s, nf);
+    case VT_GEMM_CFG_256x256_RP: return vt_gemm_rp_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, epi, s);
+    default: break;
+  }
+#ifdef VT_ABLATIONS   // timing ablations / main-loop A/B variants (bf16 epilogue; results are garbage for 101..117): test library only
+  if (cfg >= 111 && cfg < 118) return vt_gemm_p8_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, VT_EPI_BF16, VT_GEMM_CFG_256x256_P4, s, nullptr, cfg - 110);
+  if (cfg >= 100 && cfg < 108) return vt_gemm_p8_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, VT_EPI_BF16, VT_GEMM_CFG_256x256_P8, s, nullptr, cfg - 100);
+  if (cfg >= 301 && cfg <= 303) return vt_gemm_rp_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, VT_EPI_BF16, s, cfg - 300);
 #endif
-  if (cfg == VT_GEMM_CFG_256x256_P4) return vt_gemm_p8_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, epi | 0x1000, s, nf);
-  if (cfg == VT_GEMM_CFG_256x256_W4) return vt_gemm_p8_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, epi | 0x4000, s, nf);
-  if (cfg == VT_GEMM_CFG_320x256_W4) return vt_gemm_p8_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, epi | 0xc000, s, nf);
-  if (cfg == VT_GEMM_CFG_224x256_W4) return vt_gemm_p8_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, epi | 0x24000, s, nf);
-  if (cfg == VT_GEMM_CFG_160x128_W4) return vt_gemm_p8_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, epi | 0x10000, s, nf);
-  if (cfg == VT_GEMM_CFG_256x256_RP) return vt_gemm_rp_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, epi, s);
-  switch (epi) {
-    case VT_EPI_BF16: return launch_cfg<VT_EPI_BF16>(p, cfg, s);
-    case VT_EPI_BF16_GELU: return launch_cfg<VT_EPI_BF16_GELU>(p, cfg, s);
-    case VT_EPI_BF16_QGELU: return launch_cfg<VT_EPI_BF16_QGELU>(p, cfg, s);
-    case VT_EPI_BF16_RELU: return launch_cfg<VT_EPI_BF16_RELU>(p, cfg, s);
-    case VT_EPI_F32_RESID: return launch_cfg<VT_EPI_F32_RESID>(p, cfg, s);
-    case VT_EPI_F32: return launch_cfg<VT_EPI_F32>(p, cfg, s);
-    case VT_EPI_SWIGLU_BF16: return launch_cfg<VT_EPI_SWIGLU_BF16>(p, cfg, s);
-    default: vt_set_error("vt_gemm: unknown epilogue %d", epi); return VT_ERR_ARG;
-  }
+  return vt_with_epi<VtEpisPublic>(epi, "vt_gemm", [&](auto e) { return launch_cfg<decltype(e)::value>(p, cfg, s); });
 }
 
 int vt_gemm_skinny_norm_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, int ldc, int M, int N, int K, int epi,
@@ -1017,13 +993,7 @@ int vt_gemm_skinny_norm_launch(const bf16_t* A, int lda, const bf16_t* W, int ld
                "vt_gemm(norm-fused): consumer side needs in_n %% 64 == 0, in_n <= 512 (in_n=%d) and inv_dim", nf.in_n);
   GemmP p{A, W, C, nullptr, M, N, K, lda, ldw, ldc, nf};
   VtProfScope prof(VT_PROF_GEMM_SKINNY, 2.0 * (double)N * (double)K, s);
-  switch (epi) {
-    case VT_EPI_BF16: return launch_skinny<VT_EPI_BF16>(p, s, false);
-    case VT_EPI_F32_RESID: return launch_skinny<VT_EPI_F32_RESID>(p, s, false);
-    case VT_EPI_F32: return launch_skinny<VT_EPI_F32>(p, s, false);
-    case VT_EPI_SWIGLU_BF16: return launch_skinny<VT_EPI_SWIGLU_BF16>(p, s, false);
-    default: vt_set_error("vt_gemm(norm-fused): epilogue %d unsupported", epi); return VT_ERR_ARG;
-  }
+  return vt_with_epi<VtEpisDecode>(epi, "vt_gemm(norm-fused)", [&](auto e) { return launch_skinny<decltype(e)::value>(p, s, false); });
 }
 
 // Residual GEMM (C += A W^T + bias) with an optional split-K workspace. ksplit == 0: decide here -- split only when the 256x256

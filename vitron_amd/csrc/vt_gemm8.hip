@@ -91,12 +91,8 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(GemmP8 p) {
   const int ku = p.K >> 7;   // K in units of 128 (two K steps), balanced over the splits
   const int u_begin = (int)((long)ku * split / ksplit), u_end = (int)((long)ku * (split + 1) / ksplit);
   const int k_begin = u_begin * 128;
-  constexpr int GROUP_M = 8;
-  const int per_group = GROUP_M * tiles_n;
-  const int first_m = (sid / per_group) * GROUP_M;
-  const int gsz = min(tiles_m - first_m, GROUP_M);
-  const int tm = first_m + (sid % per_group) % gsz;
-  const int tn = (sid % per_group) / gsz;
+  int tm, tn;
+  grouped_tile(sid, tiles_m, tiles_n, 8, tm, tn);
   const int bm0 = tm * 256, bn0 = tn * 256;
 
   // ---- DMA source pointers: slot s, piece i (this wave stages pieces 2*wave + i of every half tile) ------------------
@@ -631,7 +627,7 @@ __global__ __launch_bounds__(512, 2) void gemm_p8_kernel(GemmP8 p) {
 template <int EPI, int MT>
 __device__ __forceinline__ void w4_epilogue_lds(const GemmP8& p, f32x4 (&acc)[MT][8], int bm0, int bn0, int wr, int wc, int lane, char* smem,
                                                 int wave) {
-  static_assert(EPI == VT_EPI_BF16 || EPI == VT_EPI_BF16_GELU || EPI == VT_EPI_BF16_QGELU || EPI == VT_EPI_BF16_RELU || EPI == VT_EPI_SWIGLU_BF16, "bf16 store epilogues");
+  static_assert(vt_epi_op16_store(EPI), "bf16 store epilogues");
   constexpr bool SW = EPI == VT_EPI_SWIGLU_BF16;
   constexpr int RC = (MT <= 8) ? MT : 5;             // fragment rows per pass (MT = 10: two passes of 80 rows)
   constexpr int ROWB = SW ? 128 : 256;               // bytes per parked row (64 | 128 bf16 columns)
@@ -874,6 +870,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // 657 -> 640 us over three interleaved runs, the C3 step -0.45 ms; groups of 2 / 3 the same, 1 and 16 / 20 slower; with 3-5 row blocks --
   // the single-image shapes -- a group of 4 leaves a ragged last group and measured +0.4 %): an XCD's 32 concurrent tiles are then
   // 4 row blocks x 8 column tiles instead of 8 x 4
+  // (written out, not grouped_tile(): with the run-time group size of the ablation build the call changed this kernel's generated code)
   const int GROUP_M = W4_KNOB(0, tiles_m >= 8 ? 4 : 8);
   const int per_group = GROUP_M * tiles_n;
   const int first_m = (sid / per_group) * GROUP_M;
@@ -1003,7 +1000,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #undef W4S_MFMA
 #undef W4S_DMA
 #undef W4S_DMA_X
-  constexpr bool bf16_store = EPI == VT_EPI_BF16 || EPI == VT_EPI_BF16_GELU || EPI == VT_EPI_BF16_QGELU || EPI == VT_EPI_BF16_RELU || EPI == VT_EPI_SWIGLU_BF16;
+  constexpr bool bf16_store = vt_epi_op16_store(EPI);
   if constexpr (ABL & 32) {                          // timing ablation: no epilogue stores at all
     float t = 0.f;
 #pragma unroll
@@ -1031,7 +1028,7 @@ template <int EPI, int MT = 8, int ABL = 0, int AUX_A = 0, int AUX_B = 0>
 int launch_w4(const GemmP8& p, hipStream_t s) {
   constexpr int BM = MT * 32;
   constexpr int smem = 2 * (BM * 128 + 256 * 128);  // 128 KiB | 144 KiB
-  constexpr bool bf16_store = EPI == VT_EPI_BF16 || EPI == VT_EPI_BF16_GELU || EPI == VT_EPI_BF16_QGELU || EPI == VT_EPI_BF16_RELU || EPI == VT_EPI_SWIGLU_BF16;
+  constexpr bool bf16_store = vt_epi_op16_store(EPI);
   if constexpr (bf16_store && !(ABL & (32 | 64))) {
     // the LDS-staged store epilogue writes 16-byte row chunks: rows 16-byte aligned and whole 8-column chunks inside the matrix,
     // otherwise the variant with the direct epilogue (which masks 4-column groups)
@@ -1077,7 +1074,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   const int tiles_m = (p.M + BM - 1) / BM, tiles_n = (p.N + BN - 1) / BN;
   const int nwg = tiles_m * tiles_n;
   const int sid = xcd_remap((int)blockIdx.x, nwg);
-  const int GROUP_M = W4_KNOB(1, 8);
+  const int GROUP_M = W4_KNOB(1, 8);   // (written out as in gemm_w4_kernel)
   const int per_group = GROUP_M * tiles_n;
   const int first_m = (sid / per_group) * GROUP_M;
   const int gsz = min(tiles_m - first_m, GROUP_M);
@@ -1213,12 +1210,8 @@ __global__ __launch_bounds__(512, 2) void gemm_rp_kernel(GemmP8 p) {
   const int tiles_m = (p.M + 255) / 256, tiles_n = (p.N + 255) / 256;
   const int nwg = tiles_m * tiles_n;
   const int sid = xcd_remap(blockIdx.x, nwg);
-  constexpr int GROUP_M = 8;
-  const int per_group = GROUP_M * tiles_n;
-  const int first_m = (sid / per_group) * GROUP_M;
-  const int gsz = min(tiles_m - first_m, GROUP_M);
-  const int tm = first_m + (sid % per_group) % gsz;
-  const int tn = (sid % per_group) / gsz;
+  int tm, tn;
+  grouped_tile(sid, tiles_m, tiles_n, 8, tm, tn);
   const int bm0 = tm * 256, bn0 = tn * 256;
 
   // DMA: 32 pieces (8 rows each) per operand tile; wave w stages pieces 4w..4w+3 of A and of B
@@ -1418,29 +1411,20 @@ int launch_p8(const GemmP8& p, hipStream_t s) {
 bool vt_gemm_p8_supported(int /*M*/, int N, int K) { return (K % 128) == 0 && K >= 256 && N % 32 == 0; }
 
 int vt_gemm_rp_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, int ldc, const float* bias, int M,
-                      int N, int K, int epi, hipStream_t s) {
+                      int N, int K, int epi, hipStream_t s, int abl) {
   VT_REQUIRE((K % 64) == 0 && N % 32 == 0, "vt_gemm(rp): needs K %% 64 == 0 and N %% 32 == 0 (K=%d N=%d)", K, N);
   VT_REQUIRE((size_t)M * lda * 2 < (1ull << 32) && (size_t)N * ldw * 2 < (1ull << 32), "vt_gemm(rp): operands must be < 4 GiB");
   GemmP8 p{A, W, C, bias, M, N, K, lda, ldw, ldc, 1, 0, VtGemmNormFuse{}};
 #ifdef VT_ABLATIONS
-  if (epi >= 0x100) {  // A/B variants of the main loop (bf16 epilogue only); test library only
-    switch (epi >> 8) {
+  if (abl) {  // A/B variants of the main loop (bf16 epilogue only); test library only
+    switch (abl) {
       case 1: return launch_rp<VT_EPI_BF16, 1>(p, s);
       case 2: return launch_rp<VT_EPI_BF16, 2>(p, s);
       default: return launch_rp<VT_EPI_BF16, 3>(p, s);
     }
   }
 #endif
-  switch (epi) {
-    case VT_EPI_BF16: return launch_rp<VT_EPI_BF16>(p, s);
-    case VT_EPI_BF16_GELU: return launch_rp<VT_EPI_BF16_GELU>(p, s);
-    case VT_EPI_BF16_QGELU: return launch_rp<VT_EPI_BF16_QGELU>(p, s);
-    case VT_EPI_BF16_RELU: return launch_rp<VT_EPI_BF16_RELU>(p, s);
-    case VT_EPI_F32_RESID: return launch_rp<VT_EPI_F32_RESID>(p, s);
-    case VT_EPI_F32: return launch_rp<VT_EPI_F32>(p, s);
-    case VT_EPI_SWIGLU_BF16: return launch_rp<VT_EPI_SWIGLU_BF16>(p, s);
-    default: vt_set_error("vt_gemm(rp): unknown epilogue %d", epi); return VT_ERR_ARG;
-  }
+  return vt_with_epi<VtEpisPublic>(epi, "vt_gemm(rp)", [&](auto e) { return launch_rp<decltype(e)::value>(p, s); });
 }
 
 // Residual GEMM as a two-pass split-K: pass 1 = the 4-phase ping-pong kernel over `ksplit` K ranges, fp32 partial products to
@@ -1538,138 +1522,56 @@ int vt_gemm_qkv_fused_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw,
 }
 
 int vt_gemm_p8_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, int ldc, const float* bias, int M,
-                      int N, int K, int epi, hipStream_t s, const VtGemmNormFuse* nf) {
+                      int N, int K, int epi, int cfg, hipStream_t s, const VtGemmNormFuse* nf, int abl) {
   VT_REQUIRE(vt_gemm_p8_supported(M, N, K), "vt_gemm(p8): needs K %% 128 == 0, K >= 256, N %% 32 == 0 (K=%d N=%d)", K, N);
   GemmP8 p{A, W, C, bias, M, N, K, lda, ldw, ldc, 1, 0, nf ? *nf : VtGemmNormFuse{}};
   if (p.nf.out_partials)
-    VT_REQUIRE((epi & 0xff) == VT_EPI_F32_RESID && p.nf.out_w && p.nf.out_xw && p.nf.out_np >= N / 32 && p.nf.out_ldp >= M,
+    VT_REQUIRE(epi == VT_EPI_F32_RESID && p.nf.out_w && p.nf.out_xw && p.nf.out_np >= N / 32 && p.nf.out_ldp >= M,
                "vt_gemm(p8): norm-fold producer needs the residual epilogue and its buffers");
 #ifdef VT_ABLATIONS
-  if (epi >= 0x100 && !(epi & 0x1d000)) {  // timing ablations (tools/gemm_ablate.py); test library only
-    switch (epi >> 8) {
-      case 1: return launch_p8<VT_EPI_BF16, 1>(p, s);
-      case 2: return launch_p8<VT_EPI_BF16, 2>(p, s);
-      case 3: return launch_p8<VT_EPI_BF16, 3>(p, s);
-      case 4: return launch_p8<VT_EPI_BF16, 4>(p, s);
-      case 5: return launch_p8<VT_EPI_BF16, 5>(p, s);
-      case 6: return launch_p8<VT_EPI_BF16, 6>(p, s);
-      default: return launch_p8<VT_EPI_BF16, 7>(p, s);
-    }
-  }
-  if ((epi & 0x1000) && (epi & 0x700)) {   // timing ablations of the 4-phase loop
-    switch ((epi >> 8) & 7) {
-      case 1: return launch_p8<VT_EPI_BF16, 1, true>(p, s);
-      case 2: return launch_p8<VT_EPI_BF16, 2, true>(p, s);
-      case 3: return launch_p8<VT_EPI_BF16, 3, true>(p, s);
-      case 4: return launch_p8<VT_EPI_BF16, 4, true>(p, s);
-      case 5: return launch_p8<VT_EPI_BF16, 5, true>(p, s);
-      case 6: return launch_p8<VT_EPI_BF16, 6, true>(p, s);
-      default: return launch_p8<VT_EPI_BF16, 7, true>(p, s);
-    }
+  if (abl && (cfg == VT_GEMM_CFG_256x256_P8 || cfg == VT_GEMM_CFG_256x256_P4)) {   // timing ablations of the main loop (tools/gemm_ablate.py): bf16
+    using Abl = VtIds<1, 2, 3, 4, 5, 6, 7>;                                          // epilogue, garbage results; test library only
+    const int a7 = Abl::has(abl) ? abl : 7;
+    if (cfg == VT_GEMM_CFG_256x256_P8) return Abl::dispatch(a7, "", [&](auto a) { return launch_p8<VT_EPI_BF16, decltype(a)::value>(p, s); });
+    return Abl::dispatch(a7, "", [&](auto a) { return launch_p8<VT_EPI_BF16, decltype(a)::value, true>(p, s); });
   }
 #endif
-  if (epi & 0x10000) {   // 4-wave kernel, 160x128 tile, four-deep ring
-    VT_REQUIRE(!nf && (K % 256) == 0, "vt_gemm(w4r): needs K %% 256 == 0 and no norm fold (K=%d)", K);
-    switch (epi & 0xff) {
-      case VT_EPI_BF16: return launch_w4r<VT_EPI_BF16>(p, s);
-      case VT_EPI_BF16_GELU: return launch_w4r<VT_EPI_BF16_GELU>(p, s);
-      case VT_EPI_BF16_QGELU: return launch_w4r<VT_EPI_BF16_QGELU>(p, s);
-      case VT_EPI_BF16_RELU: return launch_w4r<VT_EPI_BF16_RELU>(p, s);
-      case VT_EPI_F32_RESID: return launch_w4r<VT_EPI_F32_RESID>(p, s);
-      case VT_EPI_F32: return launch_w4r<VT_EPI_F32>(p, s);
-      case VT_EPI_SWIGLU_BF16: return launch_w4r<VT_EPI_SWIGLU_BF16>(p, s);
-      default: vt_set_error("vt_gemm(w4r): unknown epilogue %d", epi & 0xff); return VT_ERR_ARG;
-    }
-  }
+  switch (cfg) {   // (the cases stand in the order in which their kernels have always been emitted into the code object)
+    case VT_GEMM_CFG_160x128_W4:   // four-wave kernel, 160x128 tile, four-deep ring
+      VT_REQUIRE(!nf && (K % 256) == 0, "vt_gemm(w4r): needs K %% 256 == 0 and no norm fold (K=%d)", K);
+      return vt_with_epi<VtEpisPublic>(epi, "vt_gemm(w4r)", [&](auto e) { return launch_w4r<decltype(e)::value>(p, s); });
+    case VT_GEMM_CFG_224x256_W4:   // four-wave kernel: 112x128, 160x128 or 128x128 per wave
+    case VT_GEMM_CFG_320x256_W4:
+    case VT_GEMM_CFG_256x256_W4: {
+      VT_REQUIRE(!nf, "vt_gemm(w4): no norm fold in the 4-wave kernel");
 #ifdef VT_ABLATIONS
-  static const int w4_direct = getenv("VT_W4_EPI_DIRECT") ? atoi(getenv("VT_W4_EPI_DIRECT")) : 0;   // A/B: the direct store epilogue
-  if (w4_direct && (epi & 0x4000)) {
-    const bool t320 = (epi & 0x8000) != 0;
-    switch (epi & 0xff) {
-      case VT_EPI_BF16: return t320 ? launch_w4<VT_EPI_BF16, 10, 64>(p, s) : launch_w4<VT_EPI_BF16, 8, 64>(p, s);
-      case VT_EPI_BF16_GELU: return t320 ? launch_w4<VT_EPI_BF16_GELU, 10, 64>(p, s) : launch_w4<VT_EPI_BF16_GELU, 8, 64>(p, s);
-      case VT_EPI_SWIGLU_BF16: return t320 ? launch_w4<VT_EPI_SWIGLU_BF16, 10, 64>(p, s) : launch_w4<VT_EPI_SWIGLU_BF16, 8, 64>(p, s);
-      default: break;
-    }
-  }
+      // VT_W4_EPI_DIRECT: A/B of the direct store epilogue (ABL 64) on the 320-row tile and on the 256-row tile (which the 224-row
+      // configuration runs here as well); the other epilogues take the product path
+      static const int w4_direct = getenv("VT_W4_EPI_DIRECT") ? atoi(getenv("VT_W4_EPI_DIRECT")) : 0;
+      using Direct = VtIds<VT_EPI_BF16, VT_EPI_BF16_GELU, VT_EPI_SWIGLU_BF16>;
+      if (w4_direct && Direct::has(epi))
+        return vt_with_epi<Direct>(epi, "vt_gemm(w4)", [&](auto e) {
+          return cfg == VT_GEMM_CFG_320x256_W4 ? launch_w4<decltype(e)::value, 10, 64>(p, s) : launch_w4<decltype(e)::value, 8, 64>(p, s);
+        });
 #endif
-  if ((epi & 0x4000) && (epi & 0x20000)) {   // 4-wave kernel, 224-row tile (112x128 per wave)
-    VT_REQUIRE(!nf, "vt_gemm(w4): no norm fold in the 4-wave kernel");
-    switch (epi & 0xff) {
-      case VT_EPI_BF16: return launch_w4<VT_EPI_BF16, 7>(p, s);
-      case VT_EPI_BF16_GELU: return launch_w4<VT_EPI_BF16_GELU, 7>(p, s);
-      case VT_EPI_BF16_QGELU: return launch_w4<VT_EPI_BF16_QGELU, 7>(p, s);
-      case VT_EPI_BF16_RELU: return launch_w4<VT_EPI_BF16_RELU, 7>(p, s);
-      case VT_EPI_F32_RESID: return launch_w4<VT_EPI_F32_RESID, 7>(p, s);
-      case VT_EPI_F32: return launch_w4<VT_EPI_F32, 7>(p, s);
-      case VT_EPI_SWIGLU_BF16: return launch_w4<VT_EPI_SWIGLU_BF16, 7>(p, s);
-      default: vt_set_error("vt_gemm(w4, 224-row tile): epilogue %d not instantiated", epi & 0xff); return VT_ERR_ARG;
-    }
-  }
-  if ((epi & 0x4000) && (epi & 0x8000)) {   // 4-wave kernel, 320-row tile (160x128 per wave)
-    VT_REQUIRE(!nf, "vt_gemm(w4): no norm fold in the 4-wave kernel");
-    switch (epi & 0xff) {
-      case VT_EPI_BF16: return launch_w4<VT_EPI_BF16, 10>(p, s);
-      case VT_EPI_BF16_GELU: return launch_w4<VT_EPI_BF16_GELU, 10>(p, s);
-      case VT_EPI_BF16_QGELU: return launch_w4<VT_EPI_BF16_QGELU, 10>(p, s);
-      case VT_EPI_BF16_RELU: return launch_w4<VT_EPI_BF16_RELU, 10>(p, s);
-      case VT_EPI_F32_RESID: return launch_w4<VT_EPI_F32_RESID, 10>(p, s);
-      case VT_EPI_F32: return launch_w4<VT_EPI_F32, 10>(p, s);
-      case VT_EPI_SWIGLU_BF16: return launch_w4<VT_EPI_SWIGLU_BF16, 10>(p, s);
-      default: vt_set_error("vt_gemm(w4, 320-row tile): epilogue %d not instantiated", epi & 0xff); return VT_ERR_ARG;
-    }
-  }
-  if (epi & 0x4000) {   // 4-wave kernel (128x128 per wave)
-    VT_REQUIRE(!nf, "vt_gemm(w4): no norm fold in the 4-wave kernel");
-    switch (epi & 0xff) {
-      case VT_EPI_BF16: {
+      if (cfg == VT_GEMM_CFG_224x256_W4)
+        return vt_with_epi<VtEpisPublic>(epi, "vt_gemm(w4, 224-row tile)", [&](auto e) { return launch_w4<decltype(e)::value, 7>(p, s); });
+      if (cfg == VT_GEMM_CFG_320x256_W4)
+        return vt_with_epi<VtEpisPublic>(epi, "vt_gemm(w4, 320-row tile)", [&](auto e) { return launch_w4<decltype(e)::value, 10>(p, s); });
 #ifdef VT_ABLATIONS
-        static const int abl = getenv("VT_W4_ABL") ? atoi(getenv("VT_W4_ABL")) : 0;   // timing ablations, see the kernel
-        switch (abl) {
-          case 1: return launch_w4<VT_EPI_BF16, 8, 1>(p, s);
-          case 2: return launch_w4<VT_EPI_BF16, 8, 2>(p, s);
-          case 4: return launch_w4<VT_EPI_BF16, 8, 4>(p, s);
-          case 5: return launch_w4<VT_EPI_BF16, 8, 5>(p, s);
-          case 8: return launch_w4<VT_EPI_BF16, 8, 8>(p, s);
-          case 15: return launch_w4<VT_EPI_BF16, 8, 15>(p, s);
-          case 16: return launch_w4<VT_EPI_BF16, 8, 16>(p, s);
-          case 32: return launch_w4<VT_EPI_BF16, 8, 32>(p, s);     // no epilogue stores
-          case 64: return launch_w4<VT_EPI_BF16, 8, 64>(p, s);     // the direct (8 bytes per lane) store epilogue
-          default: break;
-        }
+      // VT_W4_ABL: timing ablations of the 256-row tile, bf16 epilogue (see the kernel; 32 = no epilogue stores, 64 = the direct store epilogue)
+      static const int w4_abl = getenv("VT_W4_ABL") ? atoi(getenv("VT_W4_ABL")) : 0;
+      using W4Abl = VtIds<1, 2, 4, 5, 8, 15, 16, 32, 64, 0>;   // 0 (and any other value): the product kernel
+      if (epi == VT_EPI_BF16)
+        return W4Abl::dispatch(W4Abl::has(w4_abl) ? w4_abl : 0, "", [&](auto a) { return launch_w4<VT_EPI_BF16, 8, decltype(a)::value>(p, s); });
 #endif
-        return launch_w4<VT_EPI_BF16>(p, s);
-      }
-      case VT_EPI_BF16_GELU: return launch_w4<VT_EPI_BF16_GELU>(p, s);
-      case VT_EPI_BF16_QGELU: return launch_w4<VT_EPI_BF16_QGELU>(p, s);
-      case VT_EPI_BF16_RELU: return launch_w4<VT_EPI_BF16_RELU>(p, s);
-      case VT_EPI_F32_RESID: return launch_w4<VT_EPI_F32_RESID>(p, s);
-      case VT_EPI_F32: return launch_w4<VT_EPI_F32>(p, s);
-      case VT_EPI_SWIGLU_BF16: return launch_w4<VT_EPI_SWIGLU_BF16>(p, s);
-      default: vt_set_error("vt_gemm(w4): epilogue %d not instantiated", epi & 0xff); return VT_ERR_ARG;
+      return vt_with_epi<VtEpisPublic>(epi, "vt_gemm(w4)", [&](auto e) { return launch_w4<decltype(e)::value, 8>(p, s); });
     }
-  }
-  if (epi & 0x1000) {   // 4-phase variant
-    switch (epi & 0xff) {
-      case VT_EPI_BF16: return launch_p8<VT_EPI_BF16, 0, true>(p, s);
-      case VT_EPI_BF16_GELU: return launch_p8<VT_EPI_BF16_GELU, 0, true>(p, s);
-      case VT_EPI_BF16_QGELU: return launch_p8<VT_EPI_BF16_QGELU, 0, true>(p, s);
-      case VT_EPI_BF16_RELU: return launch_p8<VT_EPI_BF16_RELU, 0, true>(p, s);
-      case VT_EPI_F32_RESID: return launch_p8<VT_EPI_F32_RESID, 0, true>(p, s);
-      case VT_EPI_F32: return launch_p8<VT_EPI_F32, 0, true>(p, s);
-      case VT_EPI_SWIGLU_BF16: return launch_p8<VT_EPI_SWIGLU_BF16, 0, true>(p, s);
-      default: vt_set_error("vt_gemm(p4): unknown epilogue %d", epi & 0xff); return VT_ERR_ARG;
-    }
-  }
-  switch (epi) {
-    case VT_EPI_BF16: return launch_p8<VT_EPI_BF16>(p, s);
-    case VT_EPI_BF16_GELU: return launch_p8<VT_EPI_BF16_GELU>(p, s);
-    case VT_EPI_BF16_QGELU: return launch_p8<VT_EPI_BF16_QGELU>(p, s);
-    case VT_EPI_BF16_RELU: return launch_p8<VT_EPI_BF16_RELU>(p, s);
-    case VT_EPI_F32_RESID: return launch_p8<VT_EPI_F32_RESID>(p, s);
-    case VT_EPI_F32: return launch_p8<VT_EPI_F32>(p, s);
-    case VT_EPI_SWIGLU_BF16: return launch_p8<VT_EPI_SWIGLU_BF16>(p, s);
-    default: vt_set_error("vt_gemm(p8): unknown epilogue %d", epi); return VT_ERR_ARG;
+    case VT_GEMM_CFG_256x256_P4:   // ping-pong kernel, 4-phase schedule
+      return vt_with_epi<VtEpisPublic>(epi, "vt_gemm(p4)", [&](auto e) { return launch_p8<decltype(e)::value, 0, true>(p, s); });
+    case VT_GEMM_CFG_256x256_P8:   // ping-pong kernel, 8-phase schedule
+      return vt_with_epi<VtEpisPublic>(epi, "vt_gemm(p8)", [&](auto e) { return launch_p8<decltype(e)::value>(p, s); });
+    default: vt_set_error("vt_gemm(p8): configuration %d is not one of the 256-row-family kernels", cfg); return VT_ERR_ARG;
   }
 }
 
@@ -1686,24 +1588,13 @@ int vt_gemm_mx_launch(const bf16_t* A, int lda, const uint8_t* A4, const uint8_t
   GemmP8 p{A, W, C, bias, M, N, K, lda, ldw, ldc, std::max(ksplit, 1), slab, VtGemmNormFuse{}};
   const GemmMx x{A4, aexp, W4, wexp, out4, oexp};
   VtProfScope prof(VT_PROF_GEMM_TILE, 2.0 * (double)M * (double)N * (double)K, s);
-  switch (epi) {
-    case VT_EPI_BF16: return launch_w4x<VT_EPI_BF16>(p, x, s);
-    case VT_EPI_BF16_GELU: return launch_w4x<VT_EPI_BF16_GELU>(p, x, s);
-    case VT_EPI_BF16_QGELU: return launch_w4x<VT_EPI_BF16_QGELU>(p, x, s);
-    case VT_EPI_F32_RESID: return launch_w4x<VT_EPI_F32_RESID>(p, x, s);
-    case VT_EPI_F32: return launch_w4x<VT_EPI_F32>(p, x, s);
-    case VT_EPI_SWIGLU_BF16: return launch_w4x<VT_EPI_SWIGLU_BF16>(p, x, s);
-    case VT_EPI_SWIGLU_MX:
-      VT_REQUIRE(out4 && oexp && (N % 128) == 0 && (ldc % 8) == 0 && (((size_t)C | (size_t)out4) & 15) == 0 && !bias,
-                 "vt_gemm_mx: the SwiGLU epilogue with the level 3 operand out needs N %% 128 == 0, aligned outputs and no bias");
-      return launch_w4x<VT_EPI_SWIGLU_MX>(p, x, s);
-    case VT_EPI_GELU_MX:
-    case VT_EPI_QGELU_MX:
-      VT_REQUIRE(out4 && oexp && (N % 64) == 0 && (ldc % 8) == 0 && (((size_t)C | (size_t)out4) & 15) == 0,
-                 "vt_gemm_mx: the GELU epilogues with the level 3 operand out need N %% 64 == 0 and aligned outputs");
-      return epi == VT_EPI_GELU_MX ? launch_w4x<VT_EPI_GELU_MX>(p, x, s) : launch_w4x<VT_EPI_QGELU_MX>(p, x, s);
-    default: vt_set_error("vt_gemm_mx: epilogue %d not instantiated", epi); return VT_ERR_ARG;
-  }
+  if (epi == VT_EPI_SWIGLU_MX)
+    VT_REQUIRE(out4 && oexp && (N % 128) == 0 && (ldc % 8) == 0 && (((size_t)C | (size_t)out4) & 15) == 0 && !bias,
+               "vt_gemm_mx: the SwiGLU epilogue with the level 3 operand out needs N %% 128 == 0, aligned outputs and no bias");
+  if (epi == VT_EPI_GELU_MX || epi == VT_EPI_QGELU_MX)
+    VT_REQUIRE(out4 && oexp && (N % 64) == 0 && (ldc % 8) == 0 && (((size_t)C | (size_t)out4) & 15) == 0,
+               "vt_gemm_mx: the GELU epilogues with the level 3 operand out need N %% 64 == 0 and aligned outputs");
+  return vt_with_epi<VtEpisMx>(epi, "vt_gemm_mx", [&](auto e) { return launch_w4x<decltype(e)::value>(p, x, s); });
 }
 
 // the residual GEMMs of level 3 (x += A.W^T + A4.W4^T: o_proj, down_proj). The kernel has ONE tile height (256 rows; the 4-bit image takes the

@@ -350,7 +350,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #undef W4X_DMA4
 #undef W4S_DMA
 #undef W4S_DMA_X
-  constexpr bool bf16_store = EPI == VT_EPI_BF16 || EPI == VT_EPI_BF16_GELU || EPI == VT_EPI_BF16_QGELU || EPI == VT_EPI_BF16_RELU || EPI == VT_EPI_SWIGLU_BF16;
+  constexpr bool bf16_store = vt_epi_op16_store(EPI);
   // The epilogue takes the lane id through an opaque copy: whatever it derives from it (row / column offsets, masks) is computed HERE, not hoisted
   // in front of the main loop -- where, with 256 + 256 registers taken, it was spilled between the prologue's DMA pieces and their counted
   // vmcnt wait (a scratch store counts in vmcnt and may retire out of order with the loads: the wait could return a piece early).

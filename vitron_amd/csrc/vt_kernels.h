@@ -1,6 +1,7 @@
 // vt_kernels.h -- internal launch prototypes shared by the .hip translation units and vt_api.hip.
 // Not part of the public C-ABI (that is include/vitron_hip.h).
 #pragma once
+#include <type_traits>
 #include <vector>
 #include "vt_common.h"
 #include "../../include/vitron_hip.h"
@@ -89,13 +90,16 @@ int vt_gemm_resid_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw, flo
                          const VtGemmNormFuse* nf = nullptr);
 int vt_gemm_p4_splitk_resid_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw, float* C, int ldc, const float* bias, int M,
                                    int N, int K, int ksplit, float* partials, hipStream_t s, const VtGemmNormFuse* nf = nullptr);
+// cfg = VT_GEMM_CFG_256x256_P8 / _P4 / 256x256_W4 / 320x256_W4 / 224x256_W4 / 160x128_W4; epi = one of the seven public ids;
+// abl (test library only, -DVT_ABLATIONS): timing-ablation selector of the P8 / P4 main loop, 0 = the product kernel
 int vt_gemm_p8_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, int ldc, const float* bias, int M,
-                      int N, int K, int epi, hipStream_t s, const VtGemmNormFuse* nf = nullptr);
+                      int N, int K, int epi, int cfg, hipStream_t s, const VtGemmNormFuse* nf = nullptr, int abl = 0);
 // tile-kernel norm fold: is (M, N, K) a shape whose residual GEMM can produce / whose GEMM can consume the folded norm?
 bool vt_gemm_norm_fold_supported(int M, int N, int K);
 
+// abl (test library only): A/B variant of the main loop, bf16 epilogue only
 int vt_gemm_rp_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, int ldc, const float* bias, int M,
-                      int N, int K, int epi, hipStream_t s);
+                      int N, int K, int epi, hipStream_t s, int abl = 0);
 
 // ---- vt_mx4.hip / vt_gemm8x.inc: precise level 3 (16-bit product + MX-FP4 product of the rounding remainder, one accumulator) -------------
 // W4 [N][K/2] + wexp[N] (one e8m0 exponent per output feature); A4 [M][K/2] + aexp (one exponent per row and 32 k, in the order the
@@ -115,6 +119,30 @@ int vt_gemm_mx_resid_launch(const bf16_t* A, int lda, const uint8_t* A4, const u
                             hipStream_t s);
 int vt_layernorm_mx_launch(const float* x, const float* gamma, const float* beta, bf16_t* y, uint8_t* A4, uint8_t* aexp, int rows, int D,
                            float eps, hipStream_t s);
+
+// ---- the epilogue dispatcher: runtime epilogue id -> compile-time constant ------------------------------------------------
+//   vt_with_epi<ALLOWED>(epi, "family", [&](auto e) { return launch<decltype(e)::value>(..); })
+// calls f with std::integral_constant<int, epi>. ALLOWED = VtIds<ids...> is the set of epilogues the family instantiates: an id
+// outside it is neither instantiated nor accepted -- the error names the family and VT_ERR_ARG is returned. The kernels are
+// instantiated (and emitted into the code object) in the order of the ids. The QKV-pages epilogue is launched directly.
+template <int... IDS>
+struct VtIds {
+  static constexpr bool has(int id) { return (... || (id == IDS)); }
+  template <class F>
+  static int dispatch(int id, const char* family, F&& f) {
+    int r = VT_ERR_ARG;
+    if (!(... || (id == IDS && ((r = f(std::integral_constant<int, IDS>{})), true)))) vt_set_error("%s: epilogue %d not supported", family, id);
+    return r;
+  }
+};
+using VtEpisPublic = VtIds<VT_EPI_BF16, VT_EPI_BF16_GELU, VT_EPI_BF16_QGELU, VT_EPI_BF16_RELU, VT_EPI_F32_RESID, VT_EPI_F32, VT_EPI_SWIGLU_BF16>;
+using VtEpisDecode = VtIds<VT_EPI_BF16, VT_EPI_F32, VT_EPI_F32_RESID, VT_EPI_SWIGLU_BF16>;   // NF4 and the norm-fused skinny launcher
+using VtEpisMx = VtIds<VT_EPI_BF16, VT_EPI_BF16_GELU, VT_EPI_BF16_QGELU, VT_EPI_F32_RESID, VT_EPI_F32, VT_EPI_SWIGLU_BF16, VT_EPI_SWIGLU_MX,
+                       VT_EPI_GELU_MX, VT_EPI_QGELU_MX>;
+template <class ALLOWED, class F>
+int vt_with_epi(int epi, const char* family, F&& f) { return ALLOWED::dispatch(epi, family, f); }
+// the epilogues that store 16-bit operands through the plain / LDS-staged store path
+constexpr bool vt_epi_op16_store(int epi) { return VtIds<VT_EPI_BF16, VT_EPI_BF16_GELU, VT_EPI_BF16_QGELU, VT_EPI_BF16_RELU, VT_EPI_SWIGLU_BF16>::has(epi); }
 
 // ---- vt_norm.hip ----------------------------------------------------------------------------------
 int vt_layernorm_launch(float* x, const float* temb, int T, int tokens_per_frame, const float* gamma,

@@ -287,10 +287,5 @@ int vt_gemm_nf4_launch(const bf16_t* A, int lda, const uint8_t* codes, const flo
     VT_REQUIRE(nf.in_n > 0 && (nf.in_n % 16) == 0 && nf.inv_dim > 0.f, "vt_gemm_nf4: consumer side needs in_n %% 16 == 0 (in_n=%d) and inv_dim", nf.in_n);
   Nf4P p{A, codes, absmax, C, M, N, K, lda, ldc, nf};
   VtProfScope prof(VT_PROF_GEMM_SKINNY, (double)N * (double)K * (0.5 + 4.0 / 64.0), s);
-  switch (epi) {
-    case VT_EPI_BF16: return launch_nf4<VT_EPI_BF16>(p, s);
-    case VT_EPI_F32: return launch_nf4<VT_EPI_F32>(p, s);
-    case VT_EPI_F32_RESID: return launch_nf4<VT_EPI_F32_RESID>(p, s);
-    default: return launch_nf4<VT_EPI_SWIGLU_BF16>(p, s);
-  }
+  return vt_with_epi<VtEpisDecode>(epi, "vt_gemm_nf4", [&](auto e) { return launch_nf4<decltype(e)::value>(p, s); });
 }
