@@ -89,6 +89,8 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
 /* 114 also carries vt_sample_rows and struct vt_sample_row WITHOUT a bump: one new symbol and one new struct; vt_sample_top_p and
  * vt_argmax keep their signatures and return what they returned, bit for bit. */
 /* 114 also carries vt_sample_rows_allow WITHOUT a bump: one new symbol; struct vt_sample_row and vt_sample_rows do not change. */
+/* 114 also carries vt_beam_step, vt_beam_step_scratch_bytes and vt_kv_copy_pages WITHOUT a bump: three new symbols, no struct and no
+ * existing signature changes. */
 #define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
@@ -391,6 +393,33 @@ int vt_sample_rows(const float* logits, int rows, int V, int ldl, const vt_sampl
 int vt_sample_rows_allow(const float* logits, int rows, int V, int ldl, const vt_sample_row* params,
                          const uint32_t* const* allow /* DEVICE array of `rows` device pointers, entries may be NULL */,
                          int* out_ids, int* kept_count, float* logprob, void* stream);
+
+/* BEAM SEARCH (the role of transformers' GenerationMixin beam search: log_softmax + running scores + torch.topk over
+ * num_beams * vocab, and the cache reorder behind it).
+ *
+ * vt_beam_step: row g * beams_in + b of `logits` (fp32, row stride ldl >= V) belongs to beam b of group g. The candidate score of token t is
+ *     s = (logits[r][t] - (m + logf(sum_i expf(logits[r][i] - m)))) + beam_scores[r],   m = the row maximum,   all in fp32
+ * -- vt_sample_rows' logprob plus one addition. Per group the n_out largest candidates over all beams_in * V are written in descending
+ * score: out_scores / out_tokens / out_beams, each [groups][n_out]. Exact ties are broken by the lower flat index b * V + t (this
+ * library's rule; torch.topk promises none). Nothing is read on the host and `logits` is not modified. A row needs a finite maximum; a
+ * NaN score is never selected, and a group with fewer than n_out selectable candidates ends with (-inf, -1, -1) entries.
+ * Limits, refused with VT_STATUS_ARG before any launch: 1 <= beams_in <= 16, 1 <= n_out <= 32, n_out <= V, V <= VT_SAMPLE_ROWS_MAX_V.
+ * scratch: vt_beam_step_scratch_bytes(groups, beams_in, n_out) bytes of device memory, 4-byte aligned (VT_STATUS_WORKSPACE when short).
+ * Two launches: one 1024-thread block per row (log-sum-exp, then the row's own n_out best; up to 32 * 1024 columns the row is held in
+ * registers, above that a thread re-reads its part of it when it looks for its next candidate), then one wave per group that merges the
+ * beams_in * n_out survivors. */
+size_t vt_beam_step_scratch_bytes(int groups, int beams_in, int n_out);
+int vt_beam_step(const float* logits, int ldl, int V, int groups, int beams_in, const float* beam_scores /* [groups*beams_in] */,
+                 int n_out, float* out_scores, int* out_tokens, int* out_beams /* each [groups][n_out] */,
+                 void* scratch, size_t scratch_bytes, void* stream);
+
+/* vt_kv_copy_pages: for every layer and every i < n, page src_pages[i] is copied onto page dst_pages[i] in both the K pool and the V^T
+ * pool (k / vt: [num_layers][num_pages][page_bytes] each). It counts in bytes -- page_bytes = heads * 64 * head_dim * element size, a
+ * multiple of 16 -- so one kernel serves the 16-bit pool and the e4m3 pool. src_pages / dst_pages: DEVICE int32 [n]. n == 0 is a no-op that
+ * returns OK. A pair with a page id outside [0, num_pages) is skipped on the device. The caller guarantees that no destination page is
+ * also a source (beam.plan_beam_reorder). Grid (pair, layer, K | V^T), 16-byte loads and stores. */
+int vt_kv_copy_pages(void* k, void* vt, int num_layers, int num_pages, size_t page_bytes /* heads*64*head_dim*element size */,
+                     const int* src_pages, const int* dst_pages /* device int32 [n] */, int n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * mm_projector: Linear(Din,Dh) -> GELU(erf) -> Linear(Dh,Dout)   ('mlp2x_gelu';  w2 == NULL -> 'linear')

@@ -457,6 +457,20 @@ int vt_sample_rows_allow(const float* logits, int rows, int V, int ldl, const vt
   return vt_sample_rows_launch(logits, rows, V, ldl, params, allow, out_ids, kept_count, logprob, S(stream));
 }
 
+// ---- beam search (vt_beam.hip) ----------------------------------------------------------------------------------------
+size_t vt_beam_step_scratch_bytes(int groups, int beams_in, int n_out) { return vt_beam_step_scratch_bytes_impl(groups, beams_in, n_out); }
+
+int vt_beam_step(const float* logits, int ldl, int V, int groups, int beams_in, const float* beam_scores, int n_out, float* out_scores,
+                 int* out_tokens, int* out_beams, void* scratch, size_t scratch_bytes, void* stream) {
+  return vt_beam_step_launch(logits, ldl, V, groups, beams_in, beam_scores, n_out, out_scores, out_tokens, out_beams, scratch,
+                             scratch_bytes, S(stream));
+}
+
+int vt_kv_copy_pages(void* k, void* vt, int num_layers, int num_pages, size_t page_bytes, const int* src_pages, const int* dst_pages,
+                     int n, void* stream) {
+  return vt_kv_copy_pages_launch(k, vt, num_layers, num_pages, page_bytes, src_pages, dst_pages, n, S(stream));
+}
+
 // ---- mm_projector ---------------------------------------------------------------------------------------------------
 size_t vt_projector_workspace_bytes(int M, int Dh) { return align_up((size_t)M * Dh * 2, 256) + 256; }
 

@@ -265,6 +265,13 @@ int vt_sample_top_p_launch(const float* logits, int rows, int V, int ldl, float 
 int vt_sample_rows_launch(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, const uint32_t* const* allow,
                           int* out_ids, int* kept_count, float* logprob, hipStream_t s);   // allow == NULL: vt_sample_rows
 
+// ---- vt_beam.hip ----------------------------------------------------------------------------------
+size_t vt_beam_step_scratch_bytes_impl(int groups, int beams_in, int n_out);
+int vt_beam_step_launch(const float* logits, int ldl, int V, int groups, int beams_in, const float* beam_scores, int n_out,
+                        float* out_scores, int* out_tokens, int* out_beams, void* scratch, size_t scratch_bytes, hipStream_t s);
+int vt_kv_copy_pages_launch(void* k, void* vt, int num_layers, int num_pages, size_t page_bytes, const int* src_pages,
+                            const int* dst_pages, int n, hipStream_t s);
+
 // ---- vt_preproc.hip -------------------------------------------------------------------------------
 int vt_preprocess_launch(const void* src, int src_u8, int hwc, int F, int H, int W, int bicubic, int S, const float* mean,
                          const float* std, int flip, void* dst, int dst_dtype, long dst_sc, long dst_sf, hipStream_t s);

@@ -130,6 +130,7 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         self._prefix = None
         self._vis_cache = None
         self.last_generate_stats = {}
+        self.last_beam_scores = None      # fp32 [B * num_return_sequences]: the hypotheses' scores of the last generate(num_beams > 1)
 
     # ---- module-like plumbing -----------------------------------------------------------------------------------
     def get_model(self):
@@ -458,7 +459,8 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                  temperature=1.0, top_p=1.0, top_k=None, max_new_tokens=None, max_length=None, use_cache=True,
                  stopping_criteria=None, eos_token_id=None, pad_token_id=None, num_beams=1, seed=None,
                  return_logits=False, padded_batch=False, repetition_penalty=1.0, return_logprobs=False, suppress_tokens=None,
-                 begin_suppress_tokens=None, min_new_tokens=None, bad_words_ids=None, allowed_token_ids=None, **kwargs):
+                 begin_suppress_tokens=None, min_new_tokens=None, bad_words_ids=None, allowed_token_ids=None, num_return_sequences=1,
+                 length_penalty=1.0, early_stopping=False, **kwargs):
         """repetition_penalty (RepetitionPenaltyLogitsProcessor; 1.0 is off) and return_logprobs: with both at their defaults a step
         launches what it always did (vt_argmax / vt_sample_top_p). Otherwise every step is ONE vt_sample_rows launch (row b: stream = b,
         counter = step -- today's draws) whose penalty history -- the sample's non-negative prompt ids plus what it has generated -- lives
@@ -475,9 +477,28 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         first token of every sample from the last COLUMN of the padded logits (a pad row for the shorter samples) and the decode-step
         fix-up (llava_arch.py:196-205) attends the pad rows of the spliced batch while masking the rows that share an index with the
         ids-length mask's zeros (engine.padded_batch_fixup; pinned by tests/golden/greedy_batch.npz). Default False: sequences are packed
-        and every sample gets the ids the reference returns for it ALONE."""
-        if num_beams != 1:
-            raise NotImplementedError("beam search is not implemented (the reference entry points sample or go greedy)")
+        and every sample gets the ids the reference returns for it ALONE.
+        num_beams = k > 1: greedy beam search in packed mode for B >= 1 prompts, transformers' algorithm (the release
+        this project is tested against) with num_return_sequences (<= num_beams), length_penalty and early_stopping (False / True /
+        "never"). One ordinary prefill per prompt, then per step one decoder pass over the live groups' B * k rows, one vt_beam_step and
+        one read-back of the candidates; the k beams of a prompt share its whole prompt pages and own their tails (vitron_amd.beam).
+        Returns a LongTensor [B * num_return_sequences, longest] that starts with the prompt's ids and is padded with pad_token_id; the
+        hypotheses' scores are left in self.last_beam_scores (fp32 [B * num_return_sequences]). The call neither reuses nor leaves a KV
+        prefix. Refused with NotImplementedError before any page is taken: do_sample, padded_batch, repetition_penalty != 1, every
+        constraint argument above, stopping_criteria, return_logits / return_logprobs, num_beams > 16, and a candidate list
+        (max(2, 1 + number of EOS ids) * num_beams per step, as in transformers) beyond the vocabulary or beyond vt_beam_step's 32.
+        num_beams = 1 runs the code it always ran."""
+        num_beams = int(num_beams)
+        if num_beams < 1:
+            raise ValueError(f"generate: num_beams must be >= 1, got {num_beams}")
+        if num_beams > 1:
+            self._check_beam_arguments(num_beams, num_return_sequences, early_stopping, eos_token_id, do_sample=do_sample,
+                                       padded_batch=padded_batch, repetition_penalty=repetition_penalty, suppress_tokens=suppress_tokens,
+                                       begin_suppress_tokens=begin_suppress_tokens, min_new_tokens=min_new_tokens,
+                                       bad_words_ids=bad_words_ids, allowed_token_ids=allowed_token_ids,
+                                       stopping_criteria=stopping_criteria, return_logits=return_logits, return_logprobs=return_logprobs)
+        elif int(num_return_sequences) != 1:
+            raise NotImplementedError("generate(num_return_sequences=...) needs num_beams > 1")
         if padded_batch and parse_kv_cache_dtype(getattr(self.config, "kv_cache_dtype", None)) == "fp8":
             raise NotImplementedError("generate(padded_batch=True) cannot run on the fp8 KV cache: its fix-up edits views of the 16-bit pages "
                                       "(engine.padded_batch_fixup); call set_kv_cache_dtype('16bit') first")
@@ -544,7 +565,9 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
 
         reuse = B == 1 and bool(getattr(self.config, "kv_prefix_reuse", True))
         cache = None
-        if reuse and int(getattr(self.config, "vis_cache_entries", 16)) > 0:
+        use_vis_cache = reuse
+        reuse = reuse and num_beams == 1               # a beam call neither reuses nor leaves a KV prefix
+        if use_vis_cache and int(getattr(self.config, "vis_cache_entries", 16)) > 0:
             if self._vis_cache is None:
                 from ...prefix_cache import VisualFeatureCache
                 self._vis_cache = VisualFeatureCache(int(getattr(self.config, "vis_cache_entries", 16)))
@@ -599,6 +622,9 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                 self._prefix = None
         elif self._prefix is not None:
             self.reset_prefix_cache()
+        if num_beams > 1:
+            return self._generate_beams(input_ids, seqs, flat, flat_lo, lens, num_beams, int(num_return_sequences), float(length_penalty),
+                                        early_stopping, int(max_new_tokens), sorted(eos_set), pad)
         pad_mode = bool(padded_batch) and B > 1
         if pad_mode and not embeds_spliced:
             # a text-only batch never reaches the reference's decode-step fix-up (llava_arch.py:196 returns early when images is
@@ -735,6 +761,112 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         if return_logits:
             return out, all_logits
         return out
+
+
+    # ---- beam search ---------------------------------------------------------------------------
+    def _check_beam_arguments(self, num_beams, num_return_sequences, early_stopping, eos_token_id, **other):
+        """Everything a beam call refuses, before any page is taken or given back."""
+        from ...beam import num_candidates
+        if other["do_sample"]:
+            raise NotImplementedError("generate(num_beams > 1, do_sample=True): beam sampling is not implemented (greedy beam search only)")
+        if other["padded_batch"]:
+            raise NotImplementedError("generate(num_beams > 1, padded_batch=True) is not implemented: beams run in the packed batch")
+        if float(other["repetition_penalty"]) != 1.0:
+            raise NotImplementedError("generate(num_beams > 1, repetition_penalty != 1) is not implemented")
+        for name in ("suppress_tokens", "begin_suppress_tokens", "min_new_tokens", "bad_words_ids", "allowed_token_ids",
+                     "stopping_criteria"):
+            if other[name]:
+                raise NotImplementedError(f"generate(num_beams > 1, {name}=...) is not implemented")
+        for name in ("return_logits", "return_logprobs"):
+            if other[name]:
+                raise NotImplementedError(f"generate(num_beams > 1, {name}=True) is not implemented")
+        if num_beams > 16:
+            raise NotImplementedError(f"generate(num_beams={num_beams}): at most 16 beams (vt_beam_step)")
+        if early_stopping not in (False, True, "never"):
+            raise ValueError(f"generate: early_stopping must be False, True or 'never', got {early_stopping!r}")
+        if not 1 <= int(num_return_sequences) <= num_beams:
+            raise ValueError(f"generate: num_return_sequences={num_return_sequences} must lie in [1, num_beams={num_beams}]")
+        eos = self.config.eos_token_id if eos_token_id is None else eos_token_id
+        n_eos = len(set(eos)) if isinstance(eos, (list, tuple)) else int(eos is not None)
+        n_cand = num_candidates(num_beams, n_eos)
+        V = int(self.config.vocab_size)
+        if n_cand > V:
+            raise NotImplementedError(f"generate(num_beams={num_beams}): a step keeps {n_cand} candidates (max(2, 1 + EOS ids) * num_beams), "
+                                      f"more than the vocabulary of {V}")
+        if n_cand > 32:
+            raise NotImplementedError(f"generate(num_beams={num_beams}, eos_token_id=...): a step keeps max(2, 1 + {n_eos} EOS ids) * num_beams "
+                                      f"= {n_cand} candidates, vt_beam_step returns at most 32")
+
+    def _generate_beams(self, input_ids, seqs, flat, flat_lo, lens, k, n_return, length_penalty, early_stopping, max_new_tokens, eos_ids,
+                        pad):
+        """The beam branch of generate(): `seqs` are fresh SequenceStates, `flat` the packed prompt rows. One host round trip per step."""
+        from ...beam import BeamGroup, BeamScorer
+        if max_new_tokens < 1:
+            raise ValueError(f"generate(num_beams > 1): max_new_tokens must be >= 1, got {max_new_tokens}")
+        dev = self.device
+        llama = self.model.llama
+        B = len(seqs)
+        need = sum((l + 63) // 64 + 1 + k * ((l + max_new_tokens + 63) // 64 - l // 64) for l in lens)
+        if self.kv is None or len(self.kv.free) < need:
+            self._ensure_kv(need)
+        self.last_generate_stats = {"prompt_rows": int(sum(lens)), "reused_tokens": 0, "prefill_rows": int(sum(lens)),
+                                    "tower_items": self.last_tower_items, "num_beams": k, "beam_steps": 0}
+        scorer = BeamScorer(B, k, max_new_tokens, eos_ids, length_penalty, early_stopping)
+        n_cand = scorer.num_candidates
+        groups = []
+
+        def read_back(res):     # one copy of the 3 * n_cand values per group: scores (as bits), tokens, beams
+            host = res.cpu()
+            return host[0].view(torch.float32).tolist(), host[1].tolist(), host[2].tolist()
+
+        try:
+            logits = llama_forward(llama, self.kv, seqs, flat, lens, embeds_lo=flat_lo)       # [B, V]: the prefill, as in every mode
+            # the first step: one row per prompt (transformers starts its k identical beams at [0, -1e9, ...]: only beam 0 counts)
+            cs, ct, _ = read_back(ops.beam_step(logits, torch.zeros((B,), dtype=torch.float32, device=dev), B, 1, n_cand, packed=True))
+            groups = [BeamGroup(llama, self.kv, seqs[g], k, max_new_tokens) for g in range(B)]
+            slot_tokens, slot_scores, slot_of_child = {}, {}, {}
+            for g in range(B):
+                toks, _, scs = scorer.process(g, cs[g], [0] * n_cand, ct[g])
+                slot_of_child[g] = list(range(len(toks)))      # every slot holds the prompt alone: child c takes slot c, no copy
+                slot_tokens[g], slot_scores[g] = toks, scs
+            self.last_generate_stats["beam_steps"] = 1
+            while True:
+                live = [g for g in range(B) if not scorer.is_done(g)]
+                if not live:
+                    break
+                plan = torch.tensor([[0, t] for g in live for t in slot_tokens[g]], dtype=torch.int32).to(dev)
+                x = ops.embed_splice(llama.embed, None, None, plan)
+                logits = llama_forward(llama, self.kv, [s for g in live for s in groups[g].seqs], x, [1] * (len(live) * k))
+                scores_t = torch.tensor([v for g in live for v in slot_scores[g]], dtype=torch.float32).to(dev)
+                cs, ct, cb = read_back(ops.beam_step(logits, scores_t, len(live), k, n_cand, packed=True))
+                self.last_generate_stats["beam_steps"] += 1
+                for j, g in enumerate(live):
+                    child_of_slot = {s: c for c, s in enumerate(slot_of_child[g])}
+                    toks, parents, scs = scorer.process(g, cs[j], [child_of_slot[s] for s in cb[j]], ct[j])
+                    if scorer.is_done(g) or not toks:
+                        continue
+                    new_slots = groups[g].reorder([slot_of_child[g][p] for p in parents])
+                    slot_of_child[g] = new_slots
+                    slot_tokens[g], slot_scores[g] = [0] * k, [0.0] * k
+                    for c, s in enumerate(new_slots):
+                        slot_tokens[g][s], slot_scores[g][s] = toks[c], scs[c]
+        finally:
+            for grp in groups:
+                grp.release()
+            for s in seqs:          # prompts no group took over (a failure before or inside the prefill)
+                self.kv.release(s.pages)
+                s.pages, s.length = [], 0
+        best = scorer.finalize(n_return)
+        L0 = input_ids.shape[1]
+        longest = L0 + max(len(h) for grp in best for _, h in grp)
+        out = torch.full((B * n_return, longest), int(pad), dtype=torch.long)
+        ids_host = input_ids.cpu()
+        for g, grp in enumerate(best):
+            for r, (_, h) in enumerate(grp):
+                out[g * n_return + r, :L0] = ids_host[g]
+                out[g * n_return + r, L0:L0 + len(h)] = torch.tensor(h, dtype=torch.long)
+        self.last_beam_scores = torch.tensor([sc for grp in best for sc, _ in grp], dtype=torch.float32).to(dev)
+        return out.to(dev)
 
 
 VitronLlamaForCausalLM = LlavaLlamaForCausalLM  # name used by BASELINE.json's north_star; the reference class is LlavaLlamaForCausalLM

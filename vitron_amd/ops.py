@@ -568,6 +568,61 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = 
     return res if len(res) > 1 else out
 
 
+def beam_step(logits: torch.Tensor, beam_scores: torch.Tensor, groups: int, beams_in: int, n_out: int, packed: bool = False):
+    """The n_out best continuations of every beam group, on the device; see vt_beam_step in include/vitron_hip.h. logits: fp32
+    [groups * beams_in, V] with contiguous rows (row g * beams_in + b: beam b of group g), beam_scores: fp32 [groups * beams_in].
+    Returns (scores fp32, tokens int32, beams int32), each [groups, n_out], in descending score; exact ties by the lower b * V + t.
+    packed=True returns the one int32 tensor [3, groups, n_out] behind them instead (the scores as their bits): one read-back.
+    The limits (beams_in <= 16, n_out <= 32, n_out <= V) are the library's and raise through it."""
+    lib = _lib.load_any()
+    _chk_rows(logits, torch.float32, "beam_step.logits")
+    rows, V = logits.shape
+    groups, beams_in, n_out = int(groups), int(beams_in), int(n_out)
+    if groups < 1 or beams_in < 1 or rows != groups * beams_in:
+        raise _lib.VitronHipError(f"beam_step: logits has {rows} rows, groups * beams_in = {groups} * {beams_in}")
+    if not isinstance(beam_scores, torch.Tensor) or beam_scores.device != logits.device or beam_scores.dtype != torch.float32 \
+            or not beam_scores.is_contiguous() or beam_scores.numel() != rows:
+        raise _lib.VitronHipError(f"beam_step.beam_scores: expected a contiguous fp32 tensor of {rows} values on the logits' device")
+    dev = logits.device
+    # one allocation: the three outputs [3][groups][n_out], then the scratch
+    n_res = 3 * groups * max(n_out, 0)
+    nbytes = int(lib.vt_beam_step_scratch_bytes(groups, beams_in, n_out))
+    buf = torch.empty((n_res + (nbytes + 3) // 4,), device=dev, dtype=torch.int32)
+    res = buf[:n_res].view(3, groups, max(n_out, 0))
+    base = buf.data_ptr()
+    plane = 4 * groups * max(n_out, 0)
+    _lib.check(lib.vt_beam_step(_p(logits), logits.stride(0), V, groups, beams_in, _p(beam_scores), n_out, base, base + plane,
+                                base + 2 * plane, base + 3 * plane, nbytes, _stream()), "vt_beam_step", lib)
+    if packed:
+        return res
+    return res[0].view(torch.float32), res[1], res[2]
+
+
+def kv_copy_pages(kv, src_pages, dst_pages) -> None:
+    """Copy page src_pages[i] onto page dst_pages[i] of a PagedKVCache, in every layer and both pools (vt_kv_copy_pages; either pool
+    format). The ids are host sequences: each is checked against the pool here, and no destination may also be a source."""
+    lib = _lib.load_any()
+    src = [int(p) for p in src_pages]
+    dst = [int(p) for p in dst_pages]
+    if len(src) != len(dst):
+        raise _lib.VitronHipError(f"kv_copy_pages: {len(src)} sources, {len(dst)} destinations")
+    for name, ids in (("src_pages", src), ("dst_pages", dst)):
+        for p in ids:
+            if not 0 <= p < kv.num_pages:
+                raise _lib.VitronHipError(f"kv_copy_pages.{name}: page {p} outside the pool of {kv.num_pages} pages")
+    if set(src) & set(dst) or len(set(dst)) != len(dst):
+        raise _lib.VitronHipError("kv_copy_pages: a destination page is also a source, or is written twice")
+    if not src:
+        return
+    llama = kv.llama
+    page_bytes = llama.heads * 64 * llama.hd * kv.k.element_size()
+    if kv.vt.element_size() != kv.k.element_size():
+        raise _lib.VitronHipError("kv_copy_pages: the K and V^T pools differ in element size")
+    ids = torch.tensor([src, dst], dtype=torch.int32).to(kv.k.device)
+    _lib.check(lib.vt_kv_copy_pages(_p(kv.k), _p(kv.vt), llama.L, kv.num_pages, page_bytes, _p(ids[0]), _p(ids[1]), len(src), _stream()),
+               "vt_kv_copy_pages", lib)
+
+
 def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, ignore_index: int = -100) -> torch.Tensor:
     """Mean cross entropy of fp32 logits [rows, V] against int labels [rows] (rows with `ignore_index` skipped); 0-dim tensor."""
     lib = _lib.load_any()
