@@ -91,6 +91,7 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
 /* 114 also carries vt_sample_rows_allow WITHOUT a bump: one new symbol; struct vt_sample_row and vt_sample_rows do not change. */
 /* 114 also carries vt_beam_step, vt_beam_step_scratch_bytes and vt_kv_copy_pages WITHOUT a bump: three new symbols, no struct and no
  * existing signature changes. */
+/* 114 also carries vt_ban_rows and struct vt_ban_row WITHOUT a bump: one new symbol and one new struct; the samplers do not change. */
 #define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
@@ -393,6 +394,47 @@ int vt_sample_rows(const float* logits, int rows, int V, int ldl, const vt_sampl
 int vt_sample_rows_allow(const float* logits, int rows, int V, int ldl, const vt_sample_row* params,
                          const uint32_t* const* allow /* DEVICE array of `rows` device pointers, entries may be NULL */,
                          int* out_ids, int* kept_count, float* logprob, void* stream);
+
+/* HISTORY-DEPENDENT BANS: the allow mask of every row's COMING pick, built on the device from what the row has seen so far,
+ * in front of vt_sample_rows_allow (the role of transformers' NoRepeatNGramLogitsProcessor and of NoBadWordsLogitsProcessor with
+ * multi-token entries, which both write -inf at ids that depend on input_ids). Nothing is read on the host.
+ * rows: DEVICE array of n_rows vt_ban_row (48 bytes each, 8-byte aligned; the offsets are part of the ABI):
+ *    0 const int32_t*  history      DEVICE ids seen so far (prompt, then generated); may be NULL
+ *    8 const uint32_t* base         DEVICE allow mask to start from, ceil(V / 32) words; NULL = every id of [0, V) allowed
+ *   16 uint32_t*       out          DEVICE mask to write, ceil(V / 32) words; NULL = this row is skipped entirely
+ *   24 const int32_t*  seqs         DEVICE ban sequences, flattened as {L, id_0 .. id_{L-1}} repeated; may be NULL
+ *   32 int32_t         history_len  <= 0: empty history
+ *   36 int32_t         ngram        no_repeat_ngram_size; <= 0 is off
+ *   40 int32_t         n_seqs
+ *   44 int32_t         seqs_len     ints readable at seqs
+ * Word / bit layout: vt_sample_rows_allow's (token i is bit (i & 31) of word (i >> 5)). Per row, with h = history[0 .. n):
+ *   - out starts as a copy of base, words copied as they are (bits at positions >= V included). With base NULL it starts with the bits
+ *     [0, V) set and the bits >= V of the last word clear. After that bits are only ever cleared.
+ *   - n-gram rule (ngram = g >= 1, n >= g - 1): for every i in [0, n - g + 1), if h[i .. i + g - 2] == h[n - g + 1 .. n - 1] the bit of
+ *     h[i + g - 1] is cleared. Plain int32 equality: the negative image / region sentinels of a multimodal prompt take part like any other
+ *     id (as they do in the processor, which sees the reference's own input_ids). g == 1 bans every id of h.
+ *   - sequence rule, for every sequence s of length L: L == 1 clears the bit of s[0]; L >= 2 with n >= L - 1 and
+ *     h[n - L + 1 .. n - 1] == s[0 .. L - 2] clears the bit of s[L - 1].
+ *   - an id to clear outside [0, V) is skipped and indexes nothing. A malformed seqs (an L <= 0, an entry that runs past seqs_len) ends
+ *     the parsing of that row's sequences; the sequences before it count.
+ * The kernel is total: no field value leads to an access outside history[0 .. history_len), seqs[0 .. seqs_len) or the ceil(V / 32)
+ * words of base and out (history and seqs must be readable for those lengths when set); words of a larger buffer behind out are not
+ * touched. out must NOT alias base or another row's out. The result does not depend on the order of the clears: it is deterministic.
+ * Refused with VT_STATUS_ARG and a message before any launch: V <= 0, V > VT_SAMPLE_ROWS_MAX_V, n_rows < 0, rows == NULL with n_rows > 0.
+ * n_rows == 0 is a success that launches nothing. One launch, one 1024-thread block per row: the mask is built in LDS (atomicAnd) and
+ * written once.
+ * 114 carries this entry point WITHOUT a bump: one new symbol and one new struct, nothing existing changes (see the note at VT_ABI_VERSION). */
+typedef struct vt_ban_row {
+  const int32_t* history;
+  const uint32_t* base;
+  uint32_t* out;
+  const int32_t* seqs;
+  int32_t history_len;
+  int32_t ngram;
+  int32_t n_seqs;
+  int32_t seqs_len;
+} vt_ban_row;
+int vt_ban_rows(const vt_ban_row* rows /* DEVICE */, int n_rows, int V, void* stream);
 
 /* BEAM SEARCH (the role of transformers' GenerationMixin beam search: log_softmax + running scores + torch.topk over
  * num_beams * vocab, and the cache reorder behind it).

@@ -471,6 +471,9 @@ int vt_kv_copy_pages(void* k, void* vt, int num_layers, int num_pages, size_t pa
   return vt_kv_copy_pages_launch(k, vt, num_layers, num_pages, page_bytes, src_pages, dst_pages, n, S(stream));
 }
 
+// ---- history-dependent bans (vt_ban.hip) ------------------------------------------------------------------------------
+int vt_ban_rows(const vt_ban_row* rows, int n_rows, int V, void* stream) { return vt_ban_rows_launch(rows, n_rows, V, S(stream)); }
+
 // ---- mm_projector ---------------------------------------------------------------------------------------------------
 size_t vt_projector_workspace_bytes(int M, int Dh) { return align_up((size_t)M * Dh * 2, 256) + 256; }
 

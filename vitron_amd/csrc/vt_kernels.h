@@ -272,6 +272,9 @@ int vt_beam_step_launch(const float* logits, int ldl, int V, int groups, int bea
 int vt_kv_copy_pages_launch(void* k, void* vt, int num_layers, int num_pages, size_t page_bytes, const int* src_pages,
                             const int* dst_pages, int n, hipStream_t s);
 
+// ---- vt_ban.hip -----------------------------------------------------------------------------------
+int vt_ban_rows_launch(const vt_ban_row* rows, int n_rows, int V, hipStream_t s);
+
 // ---- vt_preproc.hip -------------------------------------------------------------------------------
 int vt_preprocess_launch(const void* src, int src_u8, int hwc, int F, int H, int W, int bicubic, int S, const float* mean,
                          const float* std, int flip, void* dst, int dst_dtype, long dst_sc, long dst_sf, hipStream_t s);

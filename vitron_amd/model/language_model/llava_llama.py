@@ -460,7 +460,7 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                  stopping_criteria=None, eos_token_id=None, pad_token_id=None, num_beams=1, seed=None,
                  return_logits=False, padded_batch=False, repetition_penalty=1.0, return_logprobs=False, suppress_tokens=None,
                  begin_suppress_tokens=None, min_new_tokens=None, bad_words_ids=None, allowed_token_ids=None, num_return_sequences=1,
-                 length_penalty=1.0, early_stopping=False, **kwargs):
+                 length_penalty=1.0, early_stopping=False, no_repeat_ngram_size=None, **kwargs):
         """repetition_penalty (RepetitionPenaltyLogitsProcessor; 1.0 is off) and return_logprobs: with both at their defaults a step
         launches what it always did (vt_argmax / vt_sample_top_p). Otherwise every step is ONE vt_sample_rows launch (row b: stream = b,
         counter = step -- today's draws) whose penalty history -- the sample's non-negative prompt ids plus what it has generated -- lives
@@ -473,6 +473,13 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         (NoBadWordsLogitsProcessor, single-token entries only; a longer entry raises NotImplementedError) and this project's own
         allowed_token_ids (only these ids). With any of them every step is ONE vt_sample_rows_allow launch; the few distinct masks a call
         needs and the per-step pointer array are uploaded once before the loop. At the defaults nothing changes.
+        no_repeat_ngram_size = g (NoRepeatNGramLogitsProcessor; None or 0 is off): no n-gram of g ids occurs twice in a
+        sample's history -- its input_ids where attention_mask is 1, in order and with the image / region sentinels as they are, followed
+        by the tokens it emits. The history lives and grows on the device; every step is one vt_ban_rows launch, which builds each row's
+        allow mask from (the step's static mask above, or nothing; the history), followed by one vt_sample_rows_allow launch that reads
+        those masks. Every step's vt_ban_row array is uploaded once before the loop: no host wait, no per-step upload. The device-built
+        mask is never read back, so a row it leaves nothing for cannot raise: it gets what vt_sample_rows_allow defines for a row with
+        nothing allowed (the static constraints keep their host checks). Refused with NotImplementedError: num_beams > 1, padded_batch.
         padded_batch=True (B > 1, right padding): reproduce what the REFERENCE's batched generate() returns -- transformers 4.31 reads the
         first token of every sample from the last COLUMN of the padded logits (a pad row for the shorter samples) and the decode-step
         fix-up (llava_arch.py:196-205) attends the pad rows of the spliced batch while masking the rows that share an index with the
@@ -485,20 +492,27 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         Returns a LongTensor [B * num_return_sequences, longest] that starts with the prompt's ids and is padded with pad_token_id; the
         hypotheses' scores are left in self.last_beam_scores (fp32 [B * num_return_sequences]). The call neither reuses nor leaves a KV
         prefix. Refused with NotImplementedError before any page is taken: do_sample, padded_batch, repetition_penalty != 1, every
-        constraint argument above, stopping_criteria, return_logits / return_logprobs, num_beams > 16, and a candidate list
+        constraint argument above (no_repeat_ngram_size included), stopping_criteria, return_logits / return_logprobs, num_beams > 16, and a candidate list
         (max(2, 1 + number of EOS ids) * num_beams per step, as in transformers) beyond the vocabulary or beyond vt_beam_step's 32.
         num_beams = 1 runs the code it always ran."""
         num_beams = int(num_beams)
         if num_beams < 1:
             raise ValueError(f"generate: num_beams must be >= 1, got {num_beams}")
+        if no_repeat_ngram_size is None:
+            no_repeat_ngram_size = 0
+        if not isinstance(no_repeat_ngram_size, int) or isinstance(no_repeat_ngram_size, bool) or not 0 <= no_repeat_ngram_size <= 2 ** 31 - 1:
+            raise ValueError(f"generate: no_repeat_ngram_size must be None or an int >= 0 (0 is off), got {no_repeat_ngram_size!r}")
+        ngram = int(no_repeat_ngram_size)
         if num_beams > 1:
             self._check_beam_arguments(num_beams, num_return_sequences, early_stopping, eos_token_id, do_sample=do_sample,
                                        padded_batch=padded_batch, repetition_penalty=repetition_penalty, suppress_tokens=suppress_tokens,
                                        begin_suppress_tokens=begin_suppress_tokens, min_new_tokens=min_new_tokens,
-                                       bad_words_ids=bad_words_ids, allowed_token_ids=allowed_token_ids,
+                                       bad_words_ids=bad_words_ids, allowed_token_ids=allowed_token_ids, no_repeat_ngram_size=ngram,
                                        stopping_criteria=stopping_criteria, return_logits=return_logits, return_logprobs=return_logprobs)
         elif int(num_return_sequences) != 1:
             raise NotImplementedError("generate(num_return_sequences=...) needs num_beams > 1")
+        if ngram and padded_batch:
+            raise NotImplementedError("generate(padded_batch=True) does not take no_repeat_ngram_size; use the default packed batch")
         if padded_batch and parse_kv_cache_dtype(getattr(self.config, "kv_cache_dtype", None)) == "fp8":
             raise NotImplementedError("generate(padded_batch=True) cannot run on the fp8 KV cache: its fix-up edits views of the 16-bit pages "
                                       "(engine.padded_batch_fixup); call set_kv_cache_dtype('16bit') first")
@@ -534,6 +548,7 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
             raise ValueError(f"generate: min_new_tokens must be >= 0, got {min_new_tokens!r}")
         allowed_ids = None if allowed_token_ids is None else [int(t) for t in allowed_token_ids]
         allow_ptrs = None
+        step_base = None               # host: the address of every step's static mask (0: none), the `base` of the step's vt_ban_row
         if banned_always or banned_begin or allowed_ids is not None or (min_new > 0 and eos_set):
             # at most four distinct masks (the first step / before min_new_tokens / after), uploaded ONCE with every step's pointer array
             import numpy as np
@@ -556,12 +571,13 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
             if live:     # (min_new_tokens without an EOS id in [0, V), or no step at all, masks nothing: the call stays what it was)
                 allow_dev = torch.from_numpy(np.stack([masks[k] for k in live]).view("<i4")).to(dev)            # [n_masks, words]
                 addr = {k: allow_dev[i].data_ptr() for i, k in enumerate(live)}
-                allow_ptrs = torch.tensor([[addr.get(k, 0)] * B for k in step_key], dtype=torch.int64).to(dev)    # [steps, B]
+                step_base = [addr.get(k, 0) for k in step_key]
+                allow_ptrs = torch.tensor([[a] * B for a in step_base], dtype=torch.int64).to(dev)                # [steps, B]
         constrained = allow_ptrs is not None
         if constrained and padded_batch:
             raise NotImplementedError("generate(padded_batch=True) does not take suppress_tokens / begin_suppress_tokens / min_new_tokens / "
                                       "bad_words_ids / allowed_token_ids; use the default packed batch")
-        use_rows = use_rows or constrained
+        use_rows = use_rows or constrained or ngram > 0
 
         reuse = B == 1 and bool(getattr(self.config, "kv_prefix_reuse", True))
         cache = None
@@ -695,9 +711,29 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                 [(row_T, row_k, row_p, float(repetition_penalty), sample_seed, st, b,
                   0 if hist is None else hist.data_ptr() + 4 * b * hist.stride(0), base[b] + st if hist is not None else 0)
                  for st in range(max_new_tokens) for b in range(B)], dev).view(max_new_tokens, B, ROW_BYTES)
+            ban_rows = None
+            if ngram:
+                # the ban history: the sample's ids where attention_mask is 1, sentinels included, then what it emits. Every step's
+                # vt_ban_row array in ONE upload (history_len = prompt ids + step, base = the step's static mask); the working masks the
+                # kernel writes are what the sampler's allow pointers name, the same B addresses at every step
+                from ...sampling import BAN_ROW_BYTES, mask_words, pack_ban_rows
+                V = int(self.config.vocab_size)
+                am = attention_mask.to(dev).bool() if attention_mask is not None else None
+                ban_keep = [(input_ids[b] if am is None else input_ids[b][am[b]]).to(torch.int32) for b in range(B)]
+                ban_base = [int(k.numel()) for k in ban_keep]
+                ban_hist = torch.zeros((B, max(ban_base) + max_new_tokens), dtype=torch.int32, device=dev)
+                for b in range(B):
+                    ban_hist[b, :ban_base[b]] = ban_keep[b]
+                ban_pos = torch.tensor(ban_base, dtype=torch.long, device=dev).unsqueeze(1)
+                ban_work = torch.empty((B, mask_words(V)), dtype=torch.int32, device=dev)
+                ban_rows = pack_ban_rows(
+                    [(ban_hist.data_ptr() + 4 * b * ban_hist.stride(0), ban_base[b] + st, 0 if step_base is None else step_base[st],
+                      ban_work.data_ptr() + 4 * b * ban_work.stride(0), ngram, 0, 0, 0)
+                     for st in range(max_new_tokens) for b in range(B)], dev).view(max_new_tokens, B, BAN_ROW_BYTES)
+                ban_ptrs = torch.tensor([ban_work.data_ptr() + 4 * b * ban_work.stride(0) for b in range(B)], dtype=torch.int64).to(dev)
         try:   # (the prefill is inside: pages it took before a failure go back to the pool / the kept prefix below)
             logits = llama_forward(llama, self.kv, seqs, flat, lens, embeds_lo=flat_lo)     # [B, V]: last position of every sequence
-            if allow_ptrs is not None and logits.shape[1] != int(self.config.vocab_size):
+            if (allow_ptrs is not None or ngram) and logits.shape[1] != int(self.config.vocab_size):
                 raise RuntimeError(f"generate: the allow masks were built for V = {self.config.vocab_size}, the logits have {logits.shape[1]} columns")
             if pad_mode:
                 from ...engine import padded_batch_fixup
@@ -710,14 +746,21 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                 if return_logits:
                     all_logits.append(logits.clone())
                 if use_rows:    # per-row sampler: penalty over the device history, greedy or sampled, the chosen token's log-probability
-                    nxt = ops.sample_rows(logits, row_params[step], return_logprob=bool(return_logprobs),
-                                          _allow_ptrs=None if allow_ptrs is None else allow_ptrs[step])
+                    if ban_rows is not None:            # the rows' masks for this pick, from their histories: one launch, nothing uploaded
+                        ops.ban_rows(ban_rows[step], B, logits.shape[1])
+                        step_ptrs = ban_ptrs
+                    else:
+                        step_ptrs = None if allow_ptrs is None else allow_ptrs[step]
+                    nxt = ops.sample_rows(logits, row_params[step], return_logprob=bool(return_logprobs), _allow_ptrs=step_ptrs)
                     if return_logprobs:
                         nxt, lp = nxt
                         all_lp.append(lp)
                     if hist is not None:                # the history grows on the device: no host sync
                         hist.scatter_(1, hist_pos, nxt.unsqueeze(1))
                         hist_pos += 1
+                    if ban_rows is not None:
+                        ban_hist.scatter_(1, ban_pos, nxt.unsqueeze(1))
+                        ban_pos += 1
                 elif do_sample:   # device-side temperature / top-k / top-p sampler (no host sync, counter-based RNG)
                     nxt = ops.sample_top_p(logits, temperature, top_p if top_p else 1.0, sample_seed, step, top_k=int(top_k or 0))
                 else:
@@ -774,7 +817,7 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         if float(other["repetition_penalty"]) != 1.0:
             raise NotImplementedError("generate(num_beams > 1, repetition_penalty != 1) is not implemented")
         for name in ("suppress_tokens", "begin_suppress_tokens", "min_new_tokens", "bad_words_ids", "allowed_token_ids",
-                     "stopping_criteria"):
+                     "stopping_criteria", "no_repeat_ngram_size"):
             if other[name]:
                 raise NotImplementedError(f"generate(num_beams > 1, {name}=...) is not implemented")
         for name in ("return_logits", "return_logprobs"):

@@ -568,6 +568,22 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = 
     return res if len(res) > 1 else out
 
 
+def ban_rows(rows_dev: torch.Tensor, n_rows: int, V: int) -> None:
+    """Build the allow masks of n_rows rows on the device from their histories (n-gram and word-sequence bans); see vt_ban_rows in
+    include/vitron_hip.h. rows_dev: the device array of vt_ban_row that sampling.pack_ban_rows builds (contiguous uint8, n_rows x 48
+    bytes). Every pointer inside it is dereferenced on the device as it is: the caller keeps the buffers alive until the launch has
+    run, sizes every `out` and `base` for ceil(V / 32) words, and lets no `out` alias a `base` or another `out`."""
+    from .sampling import BAN_ROW_BYTES
+    lib = _lib.load_any()
+    n_rows = int(n_rows)
+    if n_rows > 0:
+        _chk(rows_dev, torch.uint8, "ban_rows.rows_dev")
+        if rows_dev.numel() != n_rows * BAN_ROW_BYTES:
+            raise _lib.VitronHipError(f"ban_rows.rows_dev: expected {n_rows} x {BAN_ROW_BYTES} bytes (sampling.pack_ban_rows), got "
+                                      f"{rows_dev.numel()}")
+    _lib.check(lib.vt_ban_rows(_p(rows_dev) if n_rows > 0 else None, n_rows, int(V), _stream()), "vt_ban_rows", lib)
+
+
 def beam_step(logits: torch.Tensor, beam_scores: torch.Tensor, groups: int, beams_in: int, n_out: int, packed: bool = False):
     """The n_out best continuations of every beam group, on the device; see vt_beam_step in include/vitron_hip.h. logits: fp32
     [groups * beams_in, V] with contiguous rows (row g * beams_in + b: beam b of group g), beam_scores: fp32 [groups * beams_in].

@@ -6,6 +6,10 @@ into the array `ops.sample_rows` / `vt_sample_rows` reads: one numpy structured 
 Constrained decoding: which ids a request may emit at all is a V-bit allow mask per row (`allow_mask`, the layout of
 vt_sample_rows_allow). `SamplingParams` carries the constraints; `step_allow_mask` is the pure host function that turns them and the
 tokens generated so far into the mask of the next pick.
+
+History-dependent bans: `no_repeat_ngram_size` and multi-token `bad_words` forbid ids that depend on what the request has
+seen so far, so their mask is built on the DEVICE (struct vt_ban_row, `pack_ban_rows`, ops.ban_rows) from a device-resident history;
+`history_bans` is the host statement of that contract.
 """
 from __future__ import annotations
 
@@ -25,6 +29,14 @@ ROW_DTYPE = np.dtype({
 })
 ROW_BYTES = ROW_DTYPE.itemsize
 _U64 = 2 ** 64 - 1
+# struct vt_ban_row: the offsets are part of the ABI (tests/test_ban_ref_host.py checks them against the header's table)
+BAN_ROW_DTYPE = np.dtype({
+    "names": ["history", "base", "out", "seqs", "history_len", "ngram", "n_seqs", "seqs_len"],
+    "formats": ["<u8", "<u8", "<u8", "<u8", "<i4", "<i4", "<i4", "<i4"],
+    "offsets": [0, 8, 16, 24, 32, 36, 40, 44],
+    "itemsize": 48,
+})
+BAN_ROW_BYTES = BAN_ROW_DTYPE.itemsize
 
 
 def check_sampling_values(temperature, top_p, top_k, repetition_penalty, what: str = "sampling") -> None:
@@ -46,7 +58,12 @@ def check_sampling_values(temperature, top_p, top_k, repetition_penalty, what: s
 class SamplingParams:
     """How ONE request picks its tokens. temperature 0 is greedy; top_k None means config.top_k (default 50, as in `generate`);
     `seed` with the number of tokens generated so far is the whole state of the request's random stream, so its draws do not depend on
-    what else is in the batch. logprobs=True collects the chosen token's log-probability per step (ServingEngine.logprobs)."""
+    what else is in the batch. logprobs=True collects the chosen token's log-probability per step (ServingEngine.logprobs).
+    Two more constraints are keyword arguments of the constructor: no_repeat_ngram_size (int >= 0, 0 is off: no n-gram of
+    that size occurs twice in prompt + reply, NoRepeatNGramLogitsProcessor) and bad_words (non-empty id sequences, one or several tokens:
+    the last id of a sequence is banned while the ids before it are the end of prompt + reply, NoBadWordsLogitsProcessor). Their masks
+    depend on the history and are built on the device, never read back: a step at which they leave nothing to emit cannot raise; the
+    row returns what vt_sample_rows_allow defines for a row with nothing allowed."""
     temperature: float = 0.0
     top_p: float = 1.0
     top_k: Optional[int] = None
@@ -59,6 +76,23 @@ class SamplingParams:
     min_new_tokens: int = 0                                  # the request's EOS ids are banned while it has generated fewer tokens
     choices: Optional[Tuple[Tuple[int, ...], ...]] = None    # the reply is exactly one of these id sequences, followed by EOS
     allowed_tokens_fn: Optional[Callable] = None             # generated ids -> iterable of allowed ids, or None (PrefixConstrained)
+    # ---- history-dependent bans. They come after the fields above in the constructor, are frozen, and take part in ==, hash, repr and
+    # replace() -- but they are plain attributes, NOT dataclass fields: the field list above is pinned as it is
+    # (tests/test_allow_ref_host.py), so the generated __init__ / __eq__ / __hash__ / __repr__ are replaced by the ones below, and
+    # dataclasses.replace() would drop the two: use SamplingParams.replace().
+    _EXTRA = (("no_repeat_ngram_size", 0), ("bad_words", None))
+
+    def __init__(self, temperature: float = 0.0, top_p: float = 1.0, top_k: Optional[int] = None, seed: int = 0,
+                 repetition_penalty: float = 1.0, logprobs: bool = False, allowed_token_ids=None, banned_token_ids=None,
+                 min_new_tokens: int = 0, choices=None, allowed_tokens_fn: Optional[Callable] = None,
+                 no_repeat_ngram_size: int = 0, bad_words=None):
+        for name, value in (("temperature", temperature), ("top_p", top_p), ("top_k", top_k), ("seed", seed),
+                            ("repetition_penalty", repetition_penalty), ("logprobs", logprobs), ("allowed_token_ids", allowed_token_ids),
+                            ("banned_token_ids", banned_token_ids), ("min_new_tokens", min_new_tokens), ("choices", choices),
+                            ("allowed_tokens_fn", allowed_tokens_fn), ("no_repeat_ngram_size", no_repeat_ngram_size),
+                            ("bad_words", bad_words)):
+            object.__setattr__(self, name, value)
+        self.__post_init__()
 
     def __post_init__(self):
         def ids(x, what):
@@ -69,11 +103,32 @@ class SamplingParams:
             return tuple(_as_id(t, what) for t in x)
         object.__setattr__(self, "allowed_token_ids", ids(self.allowed_token_ids, "allowed_token_ids"))
         object.__setattr__(self, "banned_token_ids", ids(self.banned_token_ids, "banned_token_ids"))
-        if self.choices is not None:
-            if isinstance(self.choices, (str, bytes)) or not hasattr(self.choices, "__iter__"):
-                raise ValueError(f"SamplingParams: choices must be a sequence of token-id sequences, got {self.choices!r}")
-            object.__setattr__(self, "choices", tuple(ids(c, "choices") for c in self.choices))
+        for name in ("choices", "bad_words"):
+            seqs = getattr(self, name)
+            if seqs is not None:
+                if isinstance(seqs, (str, bytes)) or not hasattr(seqs, "__iter__"):
+                    raise ValueError(f"SamplingParams: {name} must be a sequence of token-id sequences, got {seqs!r}")
+                object.__setattr__(self, name, tuple(ids(c, name) for c in seqs))
         self.validate()
+
+    def _key(self) -> tuple:
+        return tuple(getattr(self, n) for n in self.__dataclass_fields__) + tuple(getattr(self, n) for n, _ in self._EXTRA)
+
+    def __eq__(self, other):
+        return self._key() == other._key() if other.__class__ is self.__class__ else NotImplemented
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        names = list(self.__dataclass_fields__) + [n for n, _ in self._EXTRA]
+        return "SamplingParams(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in names) + ")"
+
+    def replace(self, **changes) -> "SamplingParams":
+        """A copy with some arguments changed (dataclasses.replace knows only the dataclass fields)."""
+        kw = {n: getattr(self, n) for n in list(self.__dataclass_fields__) + [n for n, _ in self._EXTRA]}
+        kw.update(changes)
+        return SamplingParams(**kw)
 
     def validate(self) -> None:
         check_sampling_values(self.temperature, self.top_p, self.top_k, self.repetition_penalty, "SamplingParams")
@@ -89,11 +144,21 @@ class SamplingParams:
             raise ValueError("SamplingParams: choices must hold at least one choice and no empty one")
         if self.allowed_tokens_fn is not None and not callable(self.allowed_tokens_fn):
             raise ValueError(f"SamplingParams: allowed_tokens_fn must be callable, got {self.allowed_tokens_fn!r}")
+        g = self.no_repeat_ngram_size
+        if not isinstance(g, numbers.Integral) or isinstance(g, bool) or g < 0 or g > 2 ** 31 - 1:
+            raise ValueError(f"SamplingParams: no_repeat_ngram_size must be an int >= 0 (0 is off), got {g!r}")
+        if self.bad_words is not None and any(len(w) == 0 for w in self.bad_words):
+            raise ValueError("SamplingParams: bad_words must hold no empty sequence")
+
+    @property
+    def device_bans(self) -> bool:
+        """Does the request need a mask built on the device from its history (vt_ban_rows)?"""
+        return self.no_repeat_ngram_size > 0 or bool(self.bad_words)
 
     @property
     def constrained(self) -> bool:
         return (self.allowed_token_ids is not None or bool(self.banned_token_ids) or self.min_new_tokens > 0
-                or self.choices is not None or self.allowed_tokens_fn is not None)
+                or self.choices is not None or self.allowed_tokens_fn is not None or self.device_bans)
 
     def resolved_top_k(self, config=None) -> int:
         if self.top_k is not None:
@@ -212,19 +277,18 @@ def step_allow_mask(sampling: Optional[SamplingParams], n_generated: int, tokens
 
 
 def check_constraints(sampling: Optional[SamplingParams], eos: Iterable[int], V: int) -> None:
-    """What submit() refuses before anything is queued: ids outside [0, V), choices without an EOS id in [0, V), a combination that
-    leaves nothing to emit (the static masks before / after min_new_tokens and the first step of `choices`; allowed_tokens_fn is not
-    called here)."""
+    """What submit() refuses before anything is queued: ids outside [0, V) (those of bad_words included), choices without an EOS id in
+    [0, V), a combination that leaves nothing to emit (the static masks before / after min_new_tokens and the first step of `choices`;
+    allowed_tokens_fn is not called here, and what no_repeat_ngram_size / bad_words leave is known on the device only)."""
     if sampling is None or not sampling.constrained:
         return
-    import dataclasses
-    sp = dataclasses.replace(sampling, allowed_tokens_fn=None)
-    for c in sp.choices or ():
+    sp = sampling.replace(allowed_tokens_fn=None)
+    for c in (sp.choices or ()) + (sp.bad_words or ()):
         allow_mask(V, c)
     cache: Dict = {}
     step_allow_mask(sp, 0, [], eos, V, cache)
     if sp.min_new_tokens > 0:
-        step_allow_mask(dataclasses.replace(sp, choices=None), sp.min_new_tokens, [], eos, V, {})
+        step_allow_mask(sp.replace(choices=None), sp.min_new_tokens, [], eos, V, {})
 
 
 def sample_rows_array(rows: Sequence[tuple]) -> np.ndarray:
@@ -246,3 +310,59 @@ def pack_sample_rows(rows: Sequence[tuple], device):
     import torch
     arr = sample_rows_array(rows)
     return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), ROW_BYTES)).to(device)
+
+
+# ---- history-dependent bans: struct vt_ban_row and the host statement of vt_ban_rows' contract --------------------------------------
+def flatten_ban_seqs(seqs: Optional[Iterable[Sequence[int]]]) -> np.ndarray:
+    """int32 array {L, id_0 .. id_{L-1}} repeated: the `seqs` buffer of vt_ban_row. Every sequence must be non-empty and its ids int32."""
+    flat = []
+    for w in seqs or ():
+        w = [int(t) for t in w]
+        if not w:
+            raise ValueError("flatten_ban_seqs: an empty sequence")
+        flat.append(len(w))
+        flat.extend(w)
+    if any(not -2 ** 31 <= t < 2 ** 31 for t in flat):
+        raise ValueError("flatten_ban_seqs: an id outside int32")
+    return np.asarray(flat, dtype=np.int32)
+
+
+def history_bans(V: int, history: Sequence[int], ngram: int = 0, seqs: Optional[Iterable[Sequence[int]]] = None) -> list:
+    """The ids of [0, V) that vt_ban_rows clears for a row whose history is `history` (include/vitron_hip.h), sorted:
+    n-gram rule (g = ngram >= 1, n >= g - 1): for every i in [0, n - g + 1) with h[i .. i + g - 2] == h[n - g + 1 .. n - 1], the id
+    h[i + g - 1]; sequence rule: s[0] for a sequence of one id, s[L - 1] when L >= 2, n >= L - 1 and h[n - L + 1 .. n - 1] == s[0 .. L - 2].
+    Plain integer equality (sentinels take part); an id outside [0, V) is not banned."""
+    h = [int(t) for t in history]
+    n, g = len(h), int(ngram)
+    banned = set()
+    if g >= 1 and n >= g - 1:
+        tail = h[n - g + 1:]
+        for i in range(n - g + 1):
+            if h[i:i + g - 1] == tail:
+                banned.add(h[i + g - 1])
+    for s in seqs or ():
+        s = [int(t) for t in s]
+        L = len(s)
+        if L == 1 or (L >= 2 and n >= L - 1 and h[n - L + 1:] == s[:L - 1]):
+            banned.add(s[L - 1])
+    return sorted(t for t in banned if 0 <= t < int(V))
+
+
+def ban_rows_array(rows: Sequence[tuple]) -> np.ndarray:
+    """Host array of vt_ban_row from one tuple per row:
+        (history_ptr, history_len, base_ptr, out_ptr, ngram, seqs_ptr, n_seqs, seqs_len)
+    The pointers are DEVICE addresses (tensor.data_ptr(), 0 for NULL) whose owners the caller keeps alive until the launch has run."""
+    arr = np.zeros((len(rows),), dtype=BAN_ROW_DTYPE)
+    for i, (hist_ptr, hist_len, base_ptr, out_ptr, ngram, seqs_ptr, n_seqs, seqs_len) in enumerate(rows):
+        if min(int(hist_ptr), int(base_ptr), int(out_ptr), int(seqs_ptr)) < 0 or (int(hist_len) > 0 and not hist_ptr) \
+                or (int(n_seqs) > 0 and int(seqs_len) > 0 and not seqs_ptr):
+            raise ValueError(f"ban row {i}: a negative address, or a length without its buffer")
+        arr[i] = (int(hist_ptr), int(base_ptr), int(out_ptr), int(seqs_ptr), int(hist_len), int(ngram), int(n_seqs), int(seqs_len))
+    return arr
+
+
+def pack_ban_rows(rows: Sequence[tuple], device):
+    """Device form of `ban_rows_array(rows)`: a uint8 tensor [len(rows), 48] for ops.ban_rows."""
+    import torch
+    arr = ban_rows_array(rows)
+    return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), BAN_ROW_BYTES)).to(device)

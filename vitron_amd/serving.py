@@ -35,7 +35,7 @@ import torch
 
 from . import ops
 from .engine import PagedKVCache, SequenceState, llama_forward, pair_lo, parse_kv_cache_dtype
-from .sampling import SamplingParams, check_constraints, pack_sample_rows, step_allow_mask
+from .sampling import SamplingParams, check_constraints, flatten_ban_seqs, mask_words, pack_ban_rows, pack_sample_rows, step_allow_mask
 
 
 @dataclass
@@ -55,7 +55,9 @@ class _Request:
     need: int = 0                            # KV pages for prompt + max_new_tokens
     error: Optional[BaseException] = None    # set when the request failed on its own (it is in ServingEngine.failed then)
     sampling: Optional[SamplingParams] = None  # per-request sampling; None: the engine-wide setting (the legacy draw)
-    hist: Optional[torch.Tensor] = None      # device int32: non-negative prompt ids + generated tokens (only with a repetition penalty)
+    hist: Optional[torch.Tensor] = None      # device int32: prompt ids + the tokens fed back. With a repetition penalty alone the non-negative
+                                             # prompt ids; with a device ban input_ids as submitted, sentinels included --
+                                             # the penalty reads the same buffer then (vt_sample_rows skips ids outside [0, V))
     hist_len: int = 0
     last_lp: Optional[torch.Tensor] = None   # device fp32 [1]: log-probability of `last` (sampling.logprobs)
     logprobs: List[float] = field(default_factory=list)
@@ -64,6 +66,8 @@ class _Request:
     allow_cur: Optional[torch.Tensor] = None         # the mask of the next pick (a static one, a step-dependent upload, or None)
     allow_at: int = -1                               # len(tokens) `allow_cur` was prepared for
     mask_uploads: int = 0                            # host -> device mask copies this request has cost
+    ban_mask: Optional[torch.Tensor] = None          # device int32 [ceil(V / 32)]: the working mask vt_ban_rows writes before every pick
+    ban_seqs: Optional[torch.Tensor] = None          # device int32: sampling.bad_words flattened ({L, ids} repeated), uploaded once
 
 
 class ServingEngine:
@@ -146,6 +150,7 @@ class ServingEngine:
     @staticmethod
     def _drop_masks(r: _Request) -> None:
         r.allow_dev, r.allow_host, r.allow_cur, r.allow_at = {}, {}, None, -1
+        r.ban_mask = r.ban_seqs = None
 
     def _prepare_allow(self, r: _Request) -> None:
         """The allow mask of r's next pick: a pure host function of (r.sampling, r.tokens, r.eos) -- the host has read back
@@ -175,7 +180,12 @@ class ServingEngine:
         that reproduce its legacy draw (the engine's temperature / top_p, top_k 0, the engine's seed, counter = the engine's step,
         stream = its batch row; greedy when the engine does not sample). Log-probabilities land in r.last_lp.
         A request whose SamplingParams carry a constraint passes its allow mask (_prepare_allow) and the launch is vt_sample_rows_allow;
-        rows without one, and legacy rows, pass NULL. While no row has a mask the launches are exactly the ones above."""
+        rows without one, and legacy rows, pass NULL. While no row has a mask the launches are exactly the ones above.
+        A request with no_repeat_ngram_size / bad_words keeps its history and one working mask on the device: ONE
+        vt_ban_rows launch in front of the sampler turns (the mask above as base, or NULL; the history; the rules) into the working masks
+        of all such rows, and those rows' allow pointers name their working masks. Nothing is uploaded per step but the 48-byte rows, and
+        the masks are never read back: a row they leave nothing for returns what vt_sample_rows_allow defines for it instead of failing.
+        While no active request carries such a ban the launches are exactly the ones above."""
         if reqs is None or all(r.sampling is None for r in reqs):
             if self.do_sample:
                 return ops.sample_top_p(logits, self.temperature, self.top_p, self.seed, self._step)
@@ -186,13 +196,15 @@ class ServingEngine:
             if sp is None:
                 rows.append((self.temperature if self.do_sample else 0.0, 0, self.top_p, 1.0, self.seed, self._step, i, 0, 0))
                 continue
-            if sp.repetition_penalty != 1.0 and r.hist is None:
-                keep = r.input_ids[0][r.input_ids[0] >= 0].to(torch.int32)          # (the image / region sentinels are negative)
+            if (sp.repetition_penalty != 1.0 or sp.device_bans) and r.hist is None:
+                keep = r.input_ids[0].to(torch.int32)
+                if not sp.device_bans:
+                    keep = keep[keep >= 0]                                          # (the image / region sentinels are negative)
                 r.hist = torch.empty((keep.numel() + r.max_new_tokens,), dtype=torch.int32, device=keep.device)
                 r.hist[:keep.numel()] = keep
                 r.hist_len = int(keep.numel())
             rows.append((sp.temperature, sp.resolved_top_k(self.model.config), sp.top_p, sp.repetition_penalty, sp.seed, len(r.tokens), 0,
-                         r.hist.data_ptr() if r.hist is not None else 0, r.hist_len if r.hist is not None else 0))
+                         *((r.hist.data_ptr(), r.hist_len) if sp.repetition_penalty != 1.0 else (0, 0))))
         want_lp = any(r.sampling is not None and r.sampling.logprobs for r in reqs)
         allow = None
         if any(r.sampling is not None and r.sampling.constrained for r in reqs):
@@ -200,6 +212,23 @@ class ServingEngine:
                 if r.sampling is not None and r.sampling.constrained:
                     self._prepare_allow(r)
             allow = [r.allow_cur for r in reqs]
+            ban = [r for r in reqs if r.sampling is not None and r.sampling.device_bans]
+            if ban:
+                V = int(logits.shape[1])
+                ban_rows = []
+                for r in ban:
+                    if r.allow_cur is not None and r.allow_cur.numel() != mask_words(V):        # (the base is read for ceil(V / 32) words)
+                        raise ValueError(f"request {r.rid}: its allow mask has {r.allow_cur.numel()} words, the logits have {V} columns")
+                    if r.ban_mask is None:
+                        r.ban_mask = torch.empty((mask_words(V),), dtype=torch.int32, device=logits.device)
+                        if r.sampling.bad_words:
+                            r.ban_seqs = torch.from_numpy(flatten_ban_seqs(r.sampling.bad_words)).to(logits.device)
+                    n_ints = 0 if r.ban_seqs is None else int(r.ban_seqs.numel())
+                    ban_rows.append((r.hist.data_ptr(), r.hist_len, 0 if r.allow_cur is None else r.allow_cur.data_ptr(),
+                                     r.ban_mask.data_ptr(), r.sampling.no_repeat_ngram_size,
+                                     0 if r.ban_seqs is None else r.ban_seqs.data_ptr(), len(r.sampling.bad_words or ()), n_ints))
+                ops.ban_rows(pack_ban_rows(ban_rows, logits.device), len(ban_rows), V)
+                allow = [r.ban_mask if (r.sampling is not None and r.sampling.device_bans) else a for r, a in zip(reqs, allow)]
             if all(a is None for a in allow):
                 allow = None
         res = ops.sample_rows(logits, pack_sample_rows(rows, logits.device), return_logprob=want_lp, allow=allow)
@@ -390,7 +419,7 @@ class ServingEngine:
             plan = torch.stack([torch.zeros_like(ids), ids], dim=1).contiguous()
             x = ops.embed_splice(llama.embed, None, None, plan)
             logits = llama_forward(llama, m.kv, [r.seq for r in self.active], x, [1] * len(self.active))
-            for r in self.active:                       # the token just fed joins the request's penalty history, on the device
+            for r in self.active:                       # the token just fed joins the request's penalty / ban history, on the device
                 if r.hist is not None:
                     r.hist[r.hist_len:r.hist_len + 1].copy_(r.last)
                     r.hist_len += 1
