@@ -188,7 +188,8 @@ def test_sampling_params_constraint_fields():
     assert not d.constrained and not SamplingParams(temperature=0.7, repetition_penalty=1.2, logprobs=True).constrained
     names = list(SamplingParams.__dataclass_fields__)
     assert names[:6] == ["temperature", "top_p", "top_k", "seed", "repetition_penalty", "logprobs"]      # the new fields come after
-    assert names[6:] == ["allowed_token_ids", "banned_token_ids", "min_new_tokens", "choices", "allowed_tokens_fn"]
+    assert names[6:] == ["allowed_token_ids", "banned_token_ids", "min_new_tokens", "choices", "allowed_tokens_fn",
+                         "no_repeat_ngram_size", "bad_words"]
     sp = SamplingParams(allowed_token_ids=[3, 4], banned_token_ids=np.array([4]), choices=[[1, 2], (3,)], min_new_tokens=2)
     assert sp.allowed_token_ids == (3, 4) and sp.banned_token_ids == (4,) and sp.choices == ((1, 2), (3,)) and sp.constrained
     assert isinstance(hash(sp), int) and sp == SamplingParams(allowed_token_ids=(3, 4), banned_token_ids=(4,), choices=((1, 2), (3,)),

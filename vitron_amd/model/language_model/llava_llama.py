@@ -347,6 +347,27 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         self.kv = None
         self.kv = self.new_kv_pool(n)
 
+    def _pack_rows(self, embeds, mask_host):
+        """The valid rows of a padded batch: embeds [B, S, H] and a host 0 / 1 mask [B][S] -> (the rows where the mask is 1 packed as
+        [rows, H], their low halves or None, the samples' lengths, the rows' indices in the flattened [B * S] batch). Padding never
+        enters the decoder; when there is any, the rows are gathered by the splice kernel (embeds of another float dtype are legal: the
+        gather moves rows in the model's operand dtype)."""
+        B, S, H = embeds.shape
+        lens = [sum(r) for r in mask_host]
+        idx = [b * S + j for b in range(B) for j in range(S) if mask_host[b][j]]
+        flat = embeds.reshape(B * S, H)
+        flat_lo = pair_lo(embeds)                        # precise level 2: the embeddings came out of the splice as an operand pair
+        if flat_lo is not None:
+            flat_lo = flat_lo.reshape(B * S, H)
+        if len(idx) != B * S:
+            dtype = self.model.llama.dtype
+            rowsel = torch.tensor(idx, dtype=torch.int32, device=flat.device)
+            gather = torch.stack([torch.zeros_like(rowsel), rowsel], 1).contiguous()
+            flat = ops.embed_splice(flat.to(dtype).contiguous(), None, None, gather)
+            if flat_lo is not None:
+                flat_lo = ops.embed_splice(flat_lo.to(dtype).contiguous(), None, None, gather)
+        return flat, flat_lo, lens, idx
+
     # ---- reference llava_llama.py:57-102 ----------------------------------------------------------------------
     @torch.no_grad()
     def forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None, inputs_embeds=None,
@@ -370,32 +391,19 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         else:
             mask_host = [[1] * S for _ in range(B)]
         if past_key_values is None:
-            lens = [sum(r) for r in mask_host]
             seqs = [SequenceState() for _ in range(B)]
-            need = sum((l + 63) // 64 + 1 for l in lens)
+            need = sum((sum(r) + 63) // 64 + 1 for r in mask_host)
             if use_cache:
                 self._ensure_kv(need + B * 2)
             else:
                 self._ensure_kv(need)
             past = PagedPast(self.kv, seqs, S)
-            idx = [b * S + j for b in range(B) for j in range(S) if mask_host[b][j]]
         else:
             past = past_key_values
             seqs = past.seqs
-            lens = [S] * B
-            idx = list(range(B * S))
+            mask_host = [[1] * S] * B                    # a continuation has no padding: every row is fed
             past.padded_len += S
-        flat = inputs_embeds.reshape(B * S, H)
-        flat_lo = pair_lo(inputs_embeds)                 # precise level 2: the embeddings came out of the splice as an operand pair
-        if flat_lo is not None:
-            flat_lo = flat_lo.reshape(B * S, H)
-        if len(idx) != B * S:   # pack the valid rows (padding never enters the decoder): a row gather by the splice kernel
-            rowsel = torch.tensor(idx, dtype=torch.int32, device=flat.device)
-            gather = torch.stack([torch.zeros_like(rowsel), rowsel], 1).contiguous()
-            # (inputs_embeds of another float dtype are legal here: the gather kernel moves rows in the model's operand dtype)
-            flat = ops.embed_splice(flat.to(llama.dtype).contiguous(), None, None, gather)
-            if flat_lo is not None:
-                flat_lo = ops.embed_splice(flat_lo.to(llama.dtype).contiguous(), None, None, gather)
+        flat, flat_lo, lens, idx = self._pack_rows(inputs_embeds, mask_host)
         rows = flat.shape[0]
         if output_attentions:
             # (the reference's eager LlamaAttention returns the [B, heads, S, S] probabilities of every layer; the flash kernels never
@@ -495,284 +503,65 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         constraint argument above (no_repeat_ngram_size included), stopping_criteria, return_logits / return_logprobs, num_beams > 16, and a candidate list
         (max(2, 1 + number of EOS ids) * num_beams per step, as in transformers) beyond the vocabulary or beyond vt_beam_step's 32.
         num_beams = 1 runs the code it always ran."""
-        num_beams = int(num_beams)
-        if num_beams < 1:
-            raise ValueError(f"generate: num_beams must be >= 1, got {num_beams}")
-        if no_repeat_ngram_size is None:
-            no_repeat_ngram_size = 0
-        if not isinstance(no_repeat_ngram_size, int) or isinstance(no_repeat_ngram_size, bool) or not 0 <= no_repeat_ngram_size <= 2 ** 31 - 1:
-            raise ValueError(f"generate: no_repeat_ngram_size must be None or an int >= 0 (0 is off), got {no_repeat_ngram_size!r}")
-        ngram = int(no_repeat_ngram_size)
-        if num_beams > 1:
-            self._check_beam_arguments(num_beams, num_return_sequences, early_stopping, eos_token_id, do_sample=do_sample,
-                                       padded_batch=padded_batch, repetition_penalty=repetition_penalty, suppress_tokens=suppress_tokens,
-                                       begin_suppress_tokens=begin_suppress_tokens, min_new_tokens=min_new_tokens,
-                                       bad_words_ids=bad_words_ids, allowed_token_ids=allowed_token_ids, no_repeat_ngram_size=ngram,
-                                       stopping_criteria=stopping_criteria, return_logits=return_logits, return_logprobs=return_logprobs)
-        elif int(num_return_sequences) != 1:
-            raise NotImplementedError("generate(num_return_sequences=...) needs num_beams > 1")
-        if ngram and padded_batch:
-            raise NotImplementedError("generate(padded_batch=True) does not take no_repeat_ngram_size; use the default packed batch")
-        if padded_batch and parse_kv_cache_dtype(getattr(self.config, "kv_cache_dtype", None)) == "fp8":
-            raise NotImplementedError("generate(padded_batch=True) cannot run on the fp8 KV cache: its fix-up edits views of the 16-bit pages "
-                                      "(engine.padded_batch_fixup); call set_kv_cache_dtype('16bit') first")
+        from ...picker import StepPicker, resolve_generate_args
+        a = resolve_generate_args(
+            self.config, input_ids.shape[1], do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k,
+            max_new_tokens=max_new_tokens, max_length=max_length, stopping_criteria=stopping_criteria, eos_token_id=eos_token_id,
+            pad_token_id=pad_token_id, num_beams=num_beams, seed=seed, return_logits=return_logits, padded_batch=padded_batch,
+            repetition_penalty=repetition_penalty, return_logprobs=return_logprobs, suppress_tokens=suppress_tokens,
+            begin_suppress_tokens=begin_suppress_tokens, min_new_tokens=min_new_tokens, bad_words_ids=bad_words_ids,
+            allowed_token_ids=allowed_token_ids, num_return_sequences=num_return_sequences, length_penalty=length_penalty,
+            early_stopping=early_stopping, no_repeat_ngram_size=no_repeat_ngram_size)
         dev = self.device
         input_ids = input_ids.to(dev)
-        B = input_ids.shape[0]
-        eos = self.config.eos_token_id if eos_token_id is None else eos_token_id
-        eos_set = set(eos) if isinstance(eos, (list, tuple)) else ({eos} if eos is not None else set())
-        pad = pad_token_id if pad_token_id is not None else (self.config.pad_token_id if self.config.pad_token_id is not None else 0)
-        if max_new_tokens is None:
-            max_new_tokens = (max_length - input_ids.shape[1]) if max_length else 20
-        if top_k is None:     # GenerationConfig's default: the reference's sampling calls (app.py:562-571) run TopKLogitsWarper(50)
-            top_k = int(getattr(self.config, "top_k", 50) or 0)
-        # seed of the counter-based sampler: drawn from torch's global CPU generator (so torch.manual_seed makes sampling
-        # reproducible, as with GenerationMixin.sample) and only when sampling -- greedy calls leave the RNG state alone
-        sample_seed = 0
-        if do_sample:
-            sample_seed = int(seed) if seed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
-        from ...sampling import ROW_BYTES, check_sampling_values, pack_sample_rows
-        check_sampling_values(temperature if do_sample else 0.0, top_p if (do_sample and top_p) else 1.0, int(top_k or 0), repetition_penalty,
-                              "generate")
-        use_rows = float(repetition_penalty) != 1.0 or bool(return_logprobs)
-        # ---- allow masks (constrained decoding): which ids any row may emit at step st, a pure function of st
-        banned_always = [int(t) for t in (suppress_tokens or ())]
-        for w in (bad_words_ids or ()):
-            if len(w) != 1:
-                raise NotImplementedError(f"generate(bad_words_ids=...): the multi-token entry {list(w)!r} is not implemented (single-token "
-                                          "entries only: the constraint is a mask over ids)")
-            banned_always.append(int(w[0]))
-        banned_begin = [int(t) for t in (begin_suppress_tokens or ())]
-        min_new = int(min_new_tokens or 0)
-        if min_new < 0:
-            raise ValueError(f"generate: min_new_tokens must be >= 0, got {min_new_tokens!r}")
-        allowed_ids = None if allowed_token_ids is None else [int(t) for t in allowed_token_ids]
-        allow_ptrs = None
-        step_base = None               # host: the address of every step's static mask (0: none), the `base` of the step's vt_ban_row
-        if banned_always or banned_begin or allowed_ids is not None or (min_new > 0 and eos_set):
-            # at most four distinct masks (the first step / before min_new_tokens / after), uploaded ONCE with every step's pointer array
-            import numpy as np
-
-            from ...sampling import allow_mask
-            V = int(self.config.vocab_size)
-            eos_in = [int(e) for e in eos_set if 0 <= int(e) < V]
-            masks = {}
-            step_key = []
-            for st in range(max(int(max_new_tokens), 0)):
-                key = (st == 0 and bool(banned_begin), st < min_new and bool(eos_in))
-                if key not in masks:
-                    banned = banned_always + (banned_begin if key[0] else []) + (eos_in if key[1] else [])
-                    m = allow_mask(V, allowed_ids, banned)
-                    if not m.any():
-                        raise ValueError(f"generate: the constraints leave no token to emit at step {st}")
-                    masks[key] = None if (allowed_ids is None and not banned) else m
-                step_key.append(key)
-            live = [k for k, m in masks.items() if m is not None]
-            if live:     # (min_new_tokens without an EOS id in [0, V), or no step at all, masks nothing: the call stays what it was)
-                allow_dev = torch.from_numpy(np.stack([masks[k] for k in live]).view("<i4")).to(dev)            # [n_masks, words]
-                addr = {k: allow_dev[i].data_ptr() for i, k in enumerate(live)}
-                step_base = [addr.get(k, 0) for k in step_key]
-                allow_ptrs = torch.tensor([[a] * B for a in step_base], dtype=torch.int64).to(dev)                # [steps, B]
-        constrained = allow_ptrs is not None
-        if constrained and padded_batch:
-            raise NotImplementedError("generate(padded_batch=True) does not take suppress_tokens / begin_suppress_tokens / min_new_tokens / "
-                                      "bad_words_ids / allowed_token_ids; use the default packed batch")
-        use_rows = use_rows or constrained or ngram > 0
-
+        B, L0 = input_ids.shape
+        max_new_tokens, eos_ids = a.max_new_tokens, sorted(a.eos)
         reuse = B == 1 and bool(getattr(self.config, "kv_prefix_reuse", True))
-        cache = None
-        use_vis_cache = reuse
-        reuse = reuse and num_beams == 1               # a beam call neither reuses nor leaves a KV prefix
-        if use_vis_cache and int(getattr(self.config, "vis_cache_entries", 16)) > 0:
-            if self._vis_cache is None:
-                from ...prefix_cache import VisualFeatureCache
-                self._vis_cache = VisualFeatureCache(int(getattr(self.config, "vis_cache_entries", 16)))
-            cache = self._vis_cache
-        self._last_row_sig = None
-        self.last_tower_items = None
-        (_, _, _, _, embeds, _) = self.prepare_inputs_labels_for_multimodal(input_ids, None, attention_mask, None, None,
-                                                                            images, regions, feature_cache=cache)
-        llama = self.model.llama
-        embeds_spliced = embeds is not None
-        if embeds is None:
-            embeds = self.model.embed_tokens(input_ids)
-            mask_host = attention_mask.to(torch.int32).tolist() if attention_mask is not None else [[1] * input_ids.shape[1]] * B
-        else:
-            mask_host = self._last_splice[0]
-        S, H = embeds.shape[1], embeds.shape[2]
-        lens = [sum(r) for r in mask_host]
-        idx = [b * S + j for b in range(B) for j in range(S) if mask_host[b][j]]
-        flat = embeds.reshape(B * S, H)
-        flat_lo = pair_lo(embeds)                        # precise level 2: the spliced embeddings are an operand pair
-        if flat_lo is not None:
-            flat_lo = flat_lo.reshape(B * S, H)
-        if len(idx) != B * S:
-            rowsel = torch.tensor(idx, dtype=torch.int32, device=dev)
-            gather = torch.stack([torch.zeros_like(rowsel), rowsel], 1).contiguous()
-            flat = ops.embed_splice(flat.to(llama.dtype).contiguous(), None, None, gather)
-            if flat_lo is not None:
-                flat_lo = ops.embed_splice(flat_lo.to(llama.dtype).contiguous(), None, None, gather)
+        embeds, mask_host, embeds_spliced = self._embed_prompt(input_ids, attention_mask, images, regions, use_vis_cache=reuse)
+        S = embeds.shape[1]
+        flat, flat_lo, lens, _ = self._pack_rows(embeds, mask_host)
         seqs = [SequenceState() for _ in range(B)]
-        # ---- multi-turn KV reuse (batch 1): keep the pages of the longest common whole-page prefix of the last call ------------
-        sig = None
-        kept = 0
-        if reuse:
-            import numpy as np
-
-            from ...prefix_cache import reusable_tokens
-            if self._last_row_sig is not None:
-                sig = self._last_row_sig[0][np.asarray(mask_host[0], dtype=bool)]
-            elif embeds_spliced:
-                # visual rows were spliced in without the feature cache (config.vis_cache_entries = 0): there is no per-row
-                # signature of the spliced sequence, so this call neither reuses nor leaves a KV prefix
-                reuse = False
-                if self._prefix is not None:
-                    self.reset_prefix_cache()
-            else:
-                sig = input_ids[0].cpu().numpy().astype(np.int64)[np.asarray(mask_host[0], dtype=bool)]
-            if reuse and self._prefix is not None:
-                kept = reusable_tokens(self._prefix.sig, sig) if self.kv is not None else 0
-                seqs[0].pages = self._prefix.pages[:kept // 64]
-                seqs[0].length = kept
-                self.kv.release(self._prefix.pages[kept // 64:])
-                self._prefix = None
-        elif self._prefix is not None:
-            self.reset_prefix_cache()
-        if num_beams > 1:
-            return self._generate_beams(input_ids, seqs, flat, flat_lo, lens, num_beams, int(num_return_sequences), float(length_penalty),
-                                        early_stopping, int(max_new_tokens), sorted(eos_set), pad)
-        pad_mode = bool(padded_batch) and B > 1
-        if pad_mode and not embeds_spliced:
-            # ADVICE r5: a text-only batch never reaches the reference's decode-step fix-up (llava_arch.py:196 returns early when images is
-            # None); transformers then reads a shorter sample's first token from embed(pad_token_id) at position 1 -- another behaviour than
-            # the one reproduced here (a ZERO row at position 0), so refuse instead of returning different ids silently
-            raise NotImplementedError("generate(padded_batch=True) reproduces the reference's B > 1 result for MULTIMODAL (spliced) batches; a "
-                                      "text-only batch takes another path in the reference (llava_arch.py:196-205) -- use the default packed batch")
-        if pad_mode:
-            am_rows = attention_mask.to(torch.int32).tolist() if attention_mask is not None else [[1] * input_ids.shape[1]] * B
-            side = getattr(self.config, "tokenizer_padding_side", "right")
-            if side == "left":
-                # LEFT-padded batches (llava_arch.py:379-386): the first token comes from the last column, which is a real row; at a decode step
-                # the fix-up (:196-205) extends the ids-length mask with ones, so sample i is denied the first p_ids[i] rows of its padded cache
-                # (its padding in ID space) and gets position sum(mask) - 1. When every sample's padding in ID space equals its padding in
-                # the SPLICED space -- the same number of <image> / <objs> rows in every sample, what a batched app.py turn looks like -- those
-                # are exactly its pad rows and the position is its own length + step: the reference's ids ARE the ids each sample gets alone,
-                # i.e. the packed batch below. Any other left-padded batch attends pad rows / loses real rows in the reference; not reproduced.
-                if any(any(a > b_ for a, b_ in zip(r, r[1:])) for r in am_rows):
-                    raise NotImplementedError("generate(padded_batch=True): with tokenizer_padding_side = 'left' the attention_mask must be left-padded (zeros, then ones)")
-                p_ids = [len(r) - sum(r) for r in am_rows]
-                p_sp = [S - l for l in lens]
-                if p_ids != p_sp:
-                    raise NotImplementedError(f"generate(padded_batch=True), left-padded: the samples' padding differs between the id space {p_ids} and the "
-                                              f"spliced space {p_sp} (unequal numbers of visual rows): the reference then attends pad rows / masks real rows "
-                                              "at decode steps (llava_arch.py:196-205); not reproduced -- use the default packed batch")
-                pad_mode = False
-            elif side != "right":
-                raise NotImplementedError(f"generate(padded_batch=True): tokenizer_padding_side = {side!r}")
-        if pad_mode:
-            if any(any(a < b_ for a, b_ in zip(r, r[1:])) for r in am_rows):
-                raise NotImplementedError("generate(padded_batch=True): attention_mask must be right-padded (ones, then zeros)")
-            ids_valid = [sum(r) for r in am_rows]
-        need = sum((l + max_new_tokens + 63) // 64 + 1 for l in lens) - kept // 64
-        if pad_mode:     # pad rows join the cache, and the compaction needs a second set of pages for a moment
-            need = sum(2 * ((S + 63) // 64 + 2) + (max_new_tokens + 63) // 64 + 1 for _ in lens)
-        if self.kv is None or len(self.kv.free) < need:
-            if kept:                                                          # cannot grow the pool around live pages: start over
-                self.kv.release(seqs[0].pages)
-                seqs[0].pages, seqs[0].length, kept = [], 0, 0
-                need = sum((l + max_new_tokens + 63) // 64 + 1 for l in lens)
-            self._ensure_kv(need)
+        # (a beam call neither reuses nor leaves a KV prefix)
+        sig, kept = self._take_prefix(reuse and a.num_beams == 1, input_ids, mask_host, embeds_spliced, seqs[0])
+        if a.num_beams > 1:
+            return self._generate_beams(a, input_ids, seqs, flat, flat_lo, lens)
+        pad_mode, ids_valid = self._padded_batch_rules(a.padded_batch, input_ids, attention_mask, embeds_spliced, S, lens)
+        kept = self._ensure_generate_pages(seqs, lens, max_new_tokens, kept, S if pad_mode else None)
         self.last_generate_stats = {"prompt_rows": int(sum(lens)), "reused_tokens": int(kept),
                                     "prefill_rows": int(sum(lens) - kept), "tower_items": self.last_tower_items}
         if kept:
             flat, lens = flat[kept:], [lens[0] - kept]
             flat_lo = None if flat_lo is None else flat_lo[kept:]
+        picker = StepPicker(a, input_ids, attention_mask, int(self.config.vocab_size))
         # ---- decode loop: device-resident step state, the next pass is enqueued before the host has seen the token it consumes
-        L0 = input_ids.shape[1]
+        llama = self.model.llama
         out_host = torch.empty((B, L0 + max_new_tokens), dtype=torch.long)
         out_host[:, :L0] = input_ids.cpu()
         n_out = L0
         all_logits = []
-        all_lp = []
         state = None
-        if use_rows:
-            # every step's vt_sample_row array in ONE upload (counter = step, history_len = prompt ids + step): no per-step copy
-            hist = hist_pos = None
-            base = [0] * B
-            if float(repetition_penalty) != 1.0:
-                keep = [input_ids[b][input_ids[b] >= 0].to(torch.int32) for b in range(B)]        # (image / region sentinels are negative)
-                base = [int(k.numel()) for k in keep]
-                hist = torch.zeros((B, max(base) + max_new_tokens), dtype=torch.int32, device=dev)
-                for b in range(B):
-                    hist[b, :base[b]] = keep[b]
-                hist_pos = torch.tensor(base, dtype=torch.long, device=dev).unsqueeze(1)
-            row_T, row_p, row_k = (float(temperature), float(top_p if top_p else 1.0), int(top_k or 0)) if do_sample else (0.0, 1.0, 0)
-            row_params = pack_sample_rows(
-                [(row_T, row_k, row_p, float(repetition_penalty), sample_seed, st, b,
-                  0 if hist is None else hist.data_ptr() + 4 * b * hist.stride(0), base[b] + st if hist is not None else 0)
-                 for st in range(max_new_tokens) for b in range(B)], dev).view(max_new_tokens, B, ROW_BYTES)
-            ban_rows = None
-            if ngram:
-                # the ban history: the sample's ids where attention_mask is 1, sentinels included, then what it emits. Every step's
-                # vt_ban_row array in ONE upload (history_len = prompt ids + step, base = the step's static mask); the working masks the
-                # kernel writes are what the sampler's allow pointers name, the same B addresses at every step
-                from ...sampling import BAN_ROW_BYTES, mask_words, pack_ban_rows
-                V = int(self.config.vocab_size)
-                am = attention_mask.to(dev).bool() if attention_mask is not None else None
-                ban_keep = [(input_ids[b] if am is None else input_ids[b][am[b]]).to(torch.int32) for b in range(B)]
-                ban_base = [int(k.numel()) for k in ban_keep]
-                ban_hist = torch.zeros((B, max(ban_base) + max_new_tokens), dtype=torch.int32, device=dev)
-                for b in range(B):
-                    ban_hist[b, :ban_base[b]] = ban_keep[b]
-                ban_pos = torch.tensor(ban_base, dtype=torch.long, device=dev).unsqueeze(1)
-                ban_work = torch.empty((B, mask_words(V)), dtype=torch.int32, device=dev)
-                ban_rows = pack_ban_rows(
-                    [(ban_hist.data_ptr() + 4 * b * ban_hist.stride(0), ban_base[b] + st, 0 if step_base is None else step_base[st],
-                      ban_work.data_ptr() + 4 * b * ban_work.stride(0), ngram, 0, 0, 0)
-                     for st in range(max_new_tokens) for b in range(B)], dev).view(max_new_tokens, B, BAN_ROW_BYTES)
-                ban_ptrs = torch.tensor([ban_work.data_ptr() + 4 * b * ban_work.stride(0) for b in range(B)], dtype=torch.int64).to(dev)
         try:   # (the prefill is inside: pages it took before a failure go back to the pool / the kept prefix below)
             logits = llama_forward(llama, self.kv, seqs, flat, lens, embeds_lo=flat_lo)     # [B, V]: last position of every sequence
-            if (allow_ptrs is not None or ngram) and logits.shape[1] != int(self.config.vocab_size):
-                raise RuntimeError(f"generate: the allow masks were built for V = {self.config.vocab_size}, the logits have {logits.shape[1]} columns")
+            picker.check_width(logits)
             if pad_mode:
                 from ...engine import padded_batch_fixup
-                fix = padded_batch_fixup(llama, self.kv, seqs, S, ids_valid, input_ids.shape[1])
+                fix = padded_batch_fixup(llama, self.kv, seqs, S, ids_valid, L0)
                 logits = logits.clone()
                 for b, lg in fix["pad_logits"].items():       # shorter samples: the first token comes from their last PAD row
                     logits[b] = lg
                 self.last_generate_stats["padded_batch"] = {"pad_rows": {b: S - lens[b] for b in fix["pad_logits"]}, "masked_rows": fix["holes"]}
             for step in range(max_new_tokens):
-                if return_logits:
+                if a.return_logits:
                     all_logits.append(logits.clone())
-                if use_rows:    # per-row sampler: penalty over the device history, greedy or sampled, the chosen token's log-probability
-                    if ban_rows is not None:            # the rows' masks for this pick, from their histories: one launch, nothing uploaded
-                        ops.ban_rows(ban_rows[step], B, logits.shape[1])
-                        step_ptrs = ban_ptrs
-                    else:
-                        step_ptrs = None if allow_ptrs is None else allow_ptrs[step]
-                    nxt = ops.sample_rows(logits, row_params[step], return_logprob=bool(return_logprobs), _allow_ptrs=step_ptrs)
-                    if return_logprobs:
-                        nxt, lp = nxt
-                        all_lp.append(lp)
-                    if hist is not None:                # the history grows on the device: no host sync
-                        hist.scatter_(1, hist_pos, nxt.unsqueeze(1))
-                        hist_pos += 1
-                    if ban_rows is not None:
-                        ban_hist.scatter_(1, ban_pos, nxt.unsqueeze(1))
-                        ban_pos += 1
-                elif do_sample:   # device-side temperature / top-k / top-p sampler (no host sync, counter-based RNG)
-                    nxt = ops.sample_top_p(logits, temperature, top_p if top_p else 1.0, sample_seed, step, top_k=int(top_k or 0))
-                else:
-                    nxt = ops.argmax(logits)
+                nxt = picker.pick(step, logits)
                 last = step + 1 == max_new_tokens
                 scores = logits
                 if state is None and last:    # single-token call (prefill benchmarks, scoring): no decode state to set up
                     toks = nxt.tolist()
-                    fin = [t in eos_set for t in toks]
+                    fin = [t in a.eos for t in toks]
                 else:
                     if state is None:
-                        state = DecodeState(llama, self.kv, seqs, max_new_tokens, sorted(eos_set), pad)
+                        state = DecodeState(llama, self.kv, seqs, max_new_tokens, eos_ids, a.pad)
                     slot = state.feed(nxt)
                     if not last:
                         logits = state.forward()          # speculative: rolled back below if this token ends the run
@@ -787,63 +576,136 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                         state.rollback()
                     break
         finally:
-            if reuse and sig is not None and seqs[0].length > 0:
-                import numpy as np
-
-                from ...prefix_cache import PrefixKV
-                gen_ids = out_host[0, L0:n_out].numpy().astype(np.int64)
-                full = np.concatenate([sig, gen_ids])[:seqs[0].length]      # the last sampled token was never fed back
-                self._prefix = PrefixKV(full, seqs[0].pages)
-            else:
-                for s in seqs:
-                    self.kv.release(s.pages)
+            self._leave_prefix(sig, seqs, out_host[0, L0:n_out])
         out = out_host[:, :n_out].to(dev)
-        if return_logprobs:
-            lps = torch.stack(all_lp, 1)[:, :n_out - L0] if all_lp else torch.empty((B, 0), dtype=torch.float32, device=dev)
-            return (out, all_logits, lps) if return_logits else (out, lps)
-        if return_logits:
+        if a.return_logprobs:
+            lps = picker.logprobs(n_out - L0)
+            return (out, all_logits, lps) if a.return_logits else (out, lps)
+        if a.return_logits:
             return out, all_logits
         return out
 
+    # ---- the phases of generate() -------------------------------------------------------------------------------
+    def _embed_prompt(self, input_ids, attention_mask, images, regions, use_vis_cache):
+        """The prompt's embeddings with the visual rows spliced in (through the encoded-image cache for a batch of one): returns
+        (embeds [B, S, H], the host 0 / 1 mask of their valid rows, whether anything was spliced)."""
+        cache = None
+        if use_vis_cache and int(getattr(self.config, "vis_cache_entries", 16)) > 0:
+            if self._vis_cache is None:
+                from ...prefix_cache import VisualFeatureCache
+                self._vis_cache = VisualFeatureCache(int(getattr(self.config, "vis_cache_entries", 16)))
+            cache = self._vis_cache
+        self._last_row_sig = None
+        self.last_tower_items = None
+        (_, _, _, _, embeds, _) = self.prepare_inputs_labels_for_multimodal(input_ids, None, attention_mask, None, None,
+                                                                            images, regions, feature_cache=cache)
+        if embeds is not None:
+            return embeds, self._last_splice[0], True
+        B, L = input_ids.shape
+        mask_host = attention_mask.to(torch.int32).tolist() if attention_mask is not None else [[1] * L] * B
+        return self.model.embed_tokens(input_ids), mask_host, False
+
+    def _take_prefix(self, reuse, input_ids, mask_host, embeds_spliced, seq):
+        """Multi-turn KV reuse (batch 1): `seq` takes over the pages of the longest common whole-page prefix of the last call, the rest of
+        the kept conversation goes back to the pool. Returns (the per-row signature of this prompt, or None when the call neither reuses
+        nor leaves a prefix; the number of tokens taken over). A call that does not reuse drops the kept conversation."""
+        if not reuse:
+            if self._prefix is not None:
+                self.reset_prefix_cache()
+            return None, 0
+        import numpy as np
+
+        from ...prefix_cache import reusable_tokens
+        valid = np.asarray(mask_host[0], dtype=bool)
+        if self._last_row_sig is not None:
+            sig = self._last_row_sig[0][valid]
+        elif embeds_spliced:
+            # visual rows were spliced in without the feature cache (config.vis_cache_entries = 0): there is no per-row
+            # signature of the spliced sequence, so this call neither reuses nor leaves a KV prefix
+            if self._prefix is not None:
+                self.reset_prefix_cache()
+            return None, 0
+        else:
+            sig = input_ids[0].cpu().numpy().astype(np.int64)[valid]
+        kept = 0
+        if self._prefix is not None:
+            kept = reusable_tokens(self._prefix.sig, sig) if self.kv is not None else 0
+            seq.pages = self._prefix.pages[:kept // 64]
+            seq.length = kept
+            self.kv.release(self._prefix.pages[kept // 64:])
+            self._prefix = None
+        return sig, kept
+
+    def _leave_prefix(self, sig, seqs, new_ids):
+        """The end of a generate() call, failed or not: a batch-1 call with a signature keeps its pages as the next call's prefix (the
+        signature extended by the ids it generated), every other call gives its pages back."""
+        if sig is not None and seqs[0].length > 0:
+            import numpy as np
+
+            from ...prefix_cache import PrefixKV
+            full = np.concatenate([sig, new_ids.numpy().astype(np.int64)])[:seqs[0].length]      # the last sampled token was never fed back
+            self._prefix = PrefixKV(full, seqs[0].pages)
+        else:
+            for s in seqs:
+                self.kv.release(s.pages)
+
+    def _padded_batch_rules(self, padded_batch, input_ids, attention_mask, embeds_spliced, S, lens):
+        """Which padded_batch=True calls are admitted (B > 1): returns (pad_mode, the samples' numbers of valid ids). A
+        right-padded multimodal batch runs the reference's padded loop (pad_mode True). A left-padded one whose padding is the same in
+        the id space and in the spliced space IS the packed batch (pad_mode False). Everything else is refused."""
+        B = input_ids.shape[0]
+        if not (bool(padded_batch) and B > 1):
+            return False, None
+        if not embeds_spliced:
+            # ADVICE r5: a text-only batch never reaches the reference's decode-step fix-up (llava_arch.py:196 returns early when images is
+            # None); transformers then reads a shorter sample's first token from embed(pad_token_id) at position 1 -- another behaviour than
+            # the one reproduced here (a ZERO row at position 0), so refuse instead of returning different ids silently
+            raise NotImplementedError("generate(padded_batch=True) reproduces the reference's B > 1 result for MULTIMODAL (spliced) batches; a "
+                                      "text-only batch takes another path in the reference (llava_arch.py:196-205) -- use the default packed batch")
+        am_rows = attention_mask.to(torch.int32).tolist() if attention_mask is not None else [[1] * input_ids.shape[1]] * B
+        side = getattr(self.config, "tokenizer_padding_side", "right")
+        if side == "left":
+            # LEFT-padded batches (llava_arch.py:379-386): the first token comes from the last column, which is a real row; at a decode step
+            # the fix-up (:196-205) extends the ids-length mask with ones, so sample i is denied the first p_ids[i] rows of its padded cache
+            # (its padding in ID space) and gets position sum(mask) - 1. When every sample's padding in ID space equals its padding in
+            # the SPLICED space -- the same number of <image> / <objs> rows in every sample, what a batched app.py turn looks like -- those
+            # are exactly its pad rows and the position is its own length + step: the reference's ids ARE the ids each sample gets alone,
+            # i.e. the packed batch. Any other left-padded batch attends pad rows / loses real rows in the reference; not reproduced.
+            if any(any(x > y for x, y in zip(r, r[1:])) for r in am_rows):
+                raise NotImplementedError("generate(padded_batch=True): with tokenizer_padding_side = 'left' the attention_mask must be left-padded (zeros, then ones)")
+            p_ids = [len(r) - sum(r) for r in am_rows]
+            p_sp = [S - l for l in lens]
+            if p_ids != p_sp:
+                raise NotImplementedError(f"generate(padded_batch=True), left-padded: the samples' padding differs between the id space {p_ids} and the "
+                                          f"spliced space {p_sp} (unequal numbers of visual rows): the reference then attends pad rows / masks real rows "
+                                          "at decode steps (llava_arch.py:196-205); not reproduced -- use the default packed batch")
+            return False, None
+        if side != "right":
+            raise NotImplementedError(f"generate(padded_batch=True): tokenizer_padding_side = {side!r}")
+        if any(any(x < y for x, y in zip(r, r[1:])) for r in am_rows):
+            raise NotImplementedError("generate(padded_batch=True): attention_mask must be right-padded (ones, then zeros)")
+        return True, [sum(r) for r in am_rows]
+
+    def _ensure_generate_pages(self, seqs, lens, max_new_tokens, kept, padded_S=None):
+        """Make the pool hold the pages of prompt + max_new_tokens for every sequence, less the `kept` tokens' pages seqs[0] took over;
+        in the padded mode (padded_S: the padded length) the pad rows join the cache and the compaction needs a second set of pages for a
+        moment. The pool cannot grow around live pages: when it is too small the taken-over prefix is given up. Returns `kept` (then 0)."""
+        packed = sum((l + max_new_tokens + 63) // 64 + 1 for l in lens)
+        need = packed - kept // 64
+        if padded_S is not None:
+            need = sum(2 * ((padded_S + 63) // 64 + 2) + (max_new_tokens + 63) // 64 + 1 for _ in lens)
+        if self.kv is None or len(self.kv.free) < need:
+            if kept:
+                self.kv.release(seqs[0].pages)
+                seqs[0].pages, seqs[0].length, kept, need = [], 0, 0, packed
+            self._ensure_kv(need)
+        return kept
 
     # ---- beam search (DESIGN.md 9.5) ---------------------------------------------------------------------------
-    def _check_beam_arguments(self, num_beams, num_return_sequences, early_stopping, eos_token_id, **other):
-        """Everything a beam call refuses, before any page is taken or given back."""
-        from ...beam import num_candidates
-        if other["do_sample"]:
-            raise NotImplementedError("generate(num_beams > 1, do_sample=True): beam sampling is not implemented (greedy beam search only)")
-        if other["padded_batch"]:
-            raise NotImplementedError("generate(num_beams > 1, padded_batch=True) is not implemented: beams run in the packed batch")
-        if float(other["repetition_penalty"]) != 1.0:
-            raise NotImplementedError("generate(num_beams > 1, repetition_penalty != 1) is not implemented")
-        for name in ("suppress_tokens", "begin_suppress_tokens", "min_new_tokens", "bad_words_ids", "allowed_token_ids",
-                     "stopping_criteria", "no_repeat_ngram_size"):
-            if other[name]:
-                raise NotImplementedError(f"generate(num_beams > 1, {name}=...) is not implemented")
-        for name in ("return_logits", "return_logprobs"):
-            if other[name]:
-                raise NotImplementedError(f"generate(num_beams > 1, {name}=True) is not implemented")
-        if num_beams > 16:
-            raise NotImplementedError(f"generate(num_beams={num_beams}): at most 16 beams (vt_beam_step)")
-        if early_stopping not in (False, True, "never"):
-            raise ValueError(f"generate: early_stopping must be False, True or 'never', got {early_stopping!r}")
-        if not 1 <= int(num_return_sequences) <= num_beams:
-            raise ValueError(f"generate: num_return_sequences={num_return_sequences} must lie in [1, num_beams={num_beams}]")
-        eos = self.config.eos_token_id if eos_token_id is None else eos_token_id
-        n_eos = len(set(eos)) if isinstance(eos, (list, tuple)) else int(eos is not None)
-        n_cand = num_candidates(num_beams, n_eos)
-        V = int(self.config.vocab_size)
-        if n_cand > V:
-            raise NotImplementedError(f"generate(num_beams={num_beams}): a step keeps {n_cand} candidates (max(2, 1 + EOS ids) * num_beams), "
-                                      f"more than the vocabulary of {V}")
-        if n_cand > 32:
-            raise NotImplementedError(f"generate(num_beams={num_beams}, eos_token_id=...): a step keeps max(2, 1 + {n_eos} EOS ids) * num_beams "
-                                      f"= {n_cand} candidates, vt_beam_step returns at most 32")
-
-    def _generate_beams(self, input_ids, seqs, flat, flat_lo, lens, k, n_return, length_penalty, early_stopping, max_new_tokens, eos_ids,
-                        pad):
+    def _generate_beams(self, a, input_ids, seqs, flat, flat_lo, lens):
         """The beam branch of generate(): `seqs` are fresh SequenceStates, `flat` the packed prompt rows. One host round trip per step."""
         from ...beam import BeamGroup, BeamScorer
+        k, n_return, max_new_tokens, pad = a.num_beams, a.num_return_sequences, int(a.max_new_tokens), a.pad
         if max_new_tokens < 1:
             raise ValueError(f"generate(num_beams > 1): max_new_tokens must be >= 1, got {max_new_tokens}")
         dev = self.device
@@ -854,7 +716,7 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
             self._ensure_kv(need)
         self.last_generate_stats = {"prompt_rows": int(sum(lens)), "reused_tokens": 0, "prefill_rows": int(sum(lens)),
                                     "tower_items": self.last_tower_items, "num_beams": k, "beam_steps": 0}
-        scorer = BeamScorer(B, k, max_new_tokens, eos_ids, length_penalty, early_stopping)
+        scorer = BeamScorer(B, k, max_new_tokens, sorted(a.eos), a.length_penalty, a.early_stopping)
         n_cand = scorer.num_candidates
         groups = []
 

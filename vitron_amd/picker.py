@@ -1,0 +1,279 @@
+"""What generate() decides before it touches the device, and how a step's logits become the next ids.
+
+`resolve_generate_args` turns generate()'s keyword arguments into one frozen `GenerateArgs` and raises every refusal that needs no device
+work, in a fixed order. `StepPicker` is built from that record once, before the prefill: it uploads everything the picks of ALL steps
+need (the static allow masks and every step's pointer array, every step's vt_sample_row / vt_ban_row array, the device histories) and
+then serves `pick(step, logits) -> ids` without an upload or a host wait. `device_history` is the one builder of a penalty / ban
+history; ServingEngine fills a request's `hist` with it too.
+"""
+from __future__ import annotations
+
+import dataclasses
+from dataclasses import dataclass
+from typing import Any, FrozenSet, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from . import ops
+from .engine import parse_kv_cache_dtype
+from .sampling import BAN_ROW_BYTES, ROW_BYTES, allow_mask, check_sampling_values, mask_words, pack_ban_rows, pack_sample_rows
+
+
+@dataclass(frozen=True, eq=False)
+class GenerateArgs:
+    """generate()'s arguments, resolved: the defaults of the config filled in, the lists converted, the static masks built on the host."""
+    num_beams: int
+    num_return_sequences: int
+    length_penalty: float
+    early_stopping: Any
+    do_sample: bool
+    temperature: float
+    top_p: float
+    top_k: int                                   # None resolved to config.top_k (GenerationConfig's 50)
+    repetition_penalty: float
+    return_logits: bool
+    return_logprobs: bool
+    padded_batch: bool
+    eos: FrozenSet[int]
+    pad: int
+    max_new_tokens: int
+    ngram: int
+    given: Tuple[str, ...]                       # the optional arguments a beam call refuses, as "name=..." in the order they are refused
+    sample_seed: int = 0                         # of the counter-based sampler; 0 for a greedy call
+    banned_always: Tuple[int, ...] = ()          # suppress_tokens and the single-token bad_words_ids
+    banned_begin: Tuple[int, ...] = ()           # begin_suppress_tokens: the first generated token only
+    min_new: int = 0
+    allowed_ids: Optional[Tuple[int, ...]] = None
+    masks: Optional[np.ndarray] = None           # uint32 [n_masks, ceil(V / 32)]: the distinct static allow masks, or None (unconstrained)
+    step_mask: Tuple[int, ...] = ()              # per step: the row of `masks` in force, -1 for none
+
+    @property
+    def constrained(self) -> bool:
+        return self.masks is not None
+
+    @property
+    def per_row(self) -> bool:
+        """Does a step need the per-row sampler (vt_sample_rows) instead of vt_argmax / vt_sample_top_p?"""
+        return float(self.repetition_penalty) != 1.0 or bool(self.return_logprobs) or self.constrained or self.ngram > 0
+
+
+def static_mask_schedule(V: int, steps: int, banned_always, banned_begin, min_new: int, eos, allowed_ids):
+    """Which ids any row may emit at step st is a pure function of st: at most four distinct masks, keyed by (the first step and something
+    is begin-suppressed, st < min_new_tokens and there is an EOS id in [0, V)). Returns (masks uint32 [n, words], per-step row of masks or
+    -1), or (None, ()) when no step masks anything (min_new_tokens without an EOS id inside the vocabulary, or no step at all)."""
+    eos_in = [int(e) for e in eos if 0 <= int(e) < V]
+    masks = {}
+    step_key = []
+    for st in range(max(int(steps), 0)):
+        key = (st == 0 and bool(banned_begin), st < min_new and bool(eos_in))
+        if key not in masks:
+            banned = list(banned_always) + (list(banned_begin) if key[0] else []) + (eos_in if key[1] else [])
+            m = allow_mask(V, allowed_ids, banned)
+            if not m.any():
+                raise ValueError(f"generate: the constraints leave no token to emit at step {st}")
+            masks[key] = None if (allowed_ids is None and not banned) else m
+        step_key.append(key)
+    live = [k for k, m in masks.items() if m is not None]
+    if not live:
+        return None, ()
+    return np.stack([masks[k] for k in live]), tuple(live.index(k) if k in live else -1 for k in step_key)
+
+
+def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top_p, top_k, max_new_tokens, max_length, stopping_criteria,
+                          eos_token_id, pad_token_id, num_beams, seed, return_logits, padded_batch, repetition_penalty, return_logprobs,
+                          suppress_tokens, begin_suppress_tokens, min_new_tokens, bad_words_ids, allowed_token_ids, num_return_sequences,
+                          length_penalty, early_stopping, no_repeat_ngram_size) -> GenerateArgs:
+    """generate()'s keyword arguments as a GenerateArgs. Raises, in this order and before any device work: the argument errors of
+    num_beams / no_repeat_ngram_size, everything a beam call refuses, the padded_batch refusals that depend on arguments alone, the
+    sampling values, the constraint arguments, a step the constraints leave no token for, constraints with padded_batch. The sample seed
+    is drawn from torch's global CPU generator (so torch.manual_seed makes sampling reproducible, as with GenerationMixin.sample) and
+    only when sampling without `seed`, after the beam refusals: greedy and refused calls leave the RNG state alone."""
+    num_beams = int(num_beams)
+    if num_beams < 1:
+        raise ValueError(f"generate: num_beams must be >= 1, got {num_beams}")
+    if no_repeat_ngram_size is None:
+        no_repeat_ngram_size = 0
+    if not isinstance(no_repeat_ngram_size, int) or isinstance(no_repeat_ngram_size, bool) or not 0 <= no_repeat_ngram_size <= 2 ** 31 - 1:
+        raise ValueError(f"generate: no_repeat_ngram_size must be None or an int >= 0 (0 is off), got {no_repeat_ngram_size!r}")
+    eos = config.eos_token_id if eos_token_id is None else eos_token_id
+    if max_new_tokens is None:
+        max_new_tokens = (max_length - input_len) if max_length else 20
+    if top_k is None:     # GenerationConfig's default: the reference's sampling calls (app.py:562-571) run TopKLogitsWarper(50)
+        top_k = int(getattr(config, "top_k", 50) or 0)
+    optional = (("suppress_tokens", suppress_tokens), ("begin_suppress_tokens", begin_suppress_tokens), ("min_new_tokens", min_new_tokens),
+                ("bad_words_ids", bad_words_ids), ("allowed_token_ids", allowed_token_ids), ("stopping_criteria", stopping_criteria),
+                ("no_repeat_ngram_size", no_repeat_ngram_size))
+    a = GenerateArgs(
+        num_beams=num_beams, num_return_sequences=int(num_return_sequences), length_penalty=float(length_penalty), early_stopping=early_stopping,
+        do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k, repetition_penalty=repetition_penalty,
+        return_logits=return_logits, return_logprobs=return_logprobs, padded_batch=padded_batch,
+        eos=frozenset(eos) if isinstance(eos, (list, tuple)) else (frozenset([eos]) if eos is not None else frozenset()),
+        pad=pad_token_id if pad_token_id is not None else (config.pad_token_id if config.pad_token_id is not None else 0),
+        max_new_tokens=max_new_tokens, ngram=int(no_repeat_ngram_size),
+        given=tuple(f"{name}=..." for name, value in optional if value)
+        + tuple(f"{name}=True" for name, value in (("return_logits", return_logits), ("return_logprobs", return_logprobs)) if value))
+    if num_beams > 1:
+        check_beam_arguments(a, int(config.vocab_size))
+    elif a.num_return_sequences != 1:
+        raise NotImplementedError("generate(num_return_sequences=...) needs num_beams > 1")
+    if a.ngram and padded_batch:
+        raise NotImplementedError("generate(padded_batch=True) does not take no_repeat_ngram_size; use the default packed batch")
+    if padded_batch and parse_kv_cache_dtype(getattr(config, "kv_cache_dtype", None)) == "fp8":
+        raise NotImplementedError("generate(padded_batch=True) cannot run on the fp8 KV cache: its fix-up edits views of the 16-bit pages "
+                                  "(engine.padded_batch_fixup); call set_kv_cache_dtype('16bit') first")
+    sample_seed = 0
+    if do_sample:
+        sample_seed = int(seed) if seed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+    check_sampling_values(temperature if do_sample else 0.0, top_p if (do_sample and top_p) else 1.0, int(top_k or 0), repetition_penalty,
+                          "generate")
+    banned_always = [int(t) for t in (suppress_tokens or ())]
+    for w in (bad_words_ids or ()):
+        if len(w) != 1:
+            raise NotImplementedError(f"generate(bad_words_ids=...): the multi-token entry {list(w)!r} is not implemented (single-token "
+                                      "entries only: the constraint is a mask over ids)")
+        banned_always.append(int(w[0]))
+    banned_begin = [int(t) for t in (begin_suppress_tokens or ())]
+    min_new = int(min_new_tokens or 0)
+    if min_new < 0:
+        raise ValueError(f"generate: min_new_tokens must be >= 0, got {min_new_tokens!r}")
+    allowed_ids = None if allowed_token_ids is None else tuple(int(t) for t in allowed_token_ids)
+    masks, step_mask = None, ()
+    if banned_always or banned_begin or allowed_ids is not None or (min_new > 0 and a.eos):
+        masks, step_mask = static_mask_schedule(int(config.vocab_size), max_new_tokens, banned_always, banned_begin, min_new, a.eos, allowed_ids)
+    if masks is not None and padded_batch:
+        raise NotImplementedError("generate(padded_batch=True) does not take suppress_tokens / begin_suppress_tokens / min_new_tokens / "
+                                  "bad_words_ids / allowed_token_ids; use the default packed batch")
+    return dataclasses.replace(a, sample_seed=sample_seed, banned_always=tuple(banned_always), banned_begin=tuple(banned_begin),
+                               min_new=min_new, allowed_ids=allowed_ids, masks=masks, step_mask=step_mask)
+
+
+def check_beam_arguments(a: GenerateArgs, V: int) -> None:
+    """Everything a beam call refuses, before any page is taken or given back."""
+    from .beam import num_candidates
+    if a.do_sample:
+        raise NotImplementedError("generate(num_beams > 1, do_sample=True): beam sampling is not implemented (greedy beam search only)")
+    if a.padded_batch:
+        raise NotImplementedError("generate(num_beams > 1, padded_batch=True) is not implemented: beams run in the packed batch")
+    if float(a.repetition_penalty) != 1.0:
+        raise NotImplementedError("generate(num_beams > 1, repetition_penalty != 1) is not implemented")
+    if a.given:
+        raise NotImplementedError(f"generate(num_beams > 1, {a.given[0]}) is not implemented")
+    if a.num_beams > 16:
+        raise NotImplementedError(f"generate(num_beams={a.num_beams}): at most 16 beams (vt_beam_step)")
+    if a.early_stopping not in (False, True, "never"):
+        raise ValueError(f"generate: early_stopping must be False, True or 'never', got {a.early_stopping!r}")
+    if not 1 <= a.num_return_sequences <= a.num_beams:
+        raise ValueError(f"generate: num_return_sequences={a.num_return_sequences} must lie in [1, num_beams={a.num_beams}]")
+    n_cand = num_candidates(a.num_beams, len(a.eos))
+    if n_cand > V:
+        raise NotImplementedError(f"generate(num_beams={a.num_beams}): a step keeps {n_cand} candidates (max(2, 1 + EOS ids) * num_beams), "
+                                  f"more than the vocabulary of {V}")
+    if n_cand > 32:
+        raise NotImplementedError(f"generate(num_beams={a.num_beams}, eos_token_id=...): a step keeps max(2, 1 + {len(a.eos)} EOS ids) * num_beams "
+                                  f"= {n_cand} candidates, vt_beam_step returns at most 32")
+
+
+def device_history(input_ids: torch.Tensor, room: int, attention_mask: Optional[torch.Tensor] = None, nonneg: bool = False):
+    """The histories vt_sample_rows / vt_ban_rows read: int32 [B, longest + room] on input_ids' device, row b holding sample b's prompt
+    ids -- those where attention_mask is 1 when a mask is given, only the non-negative ones (the image / region sentinels are negative)
+    with nonneg -- followed by `room` slots for what it emits. Returns (buffer, the rows' prompt lengths)."""
+    keep = []
+    for b in range(input_ids.shape[0]):
+        row = input_ids[b] if attention_mask is None else input_ids[b][attention_mask[b].to(input_ids.device).bool()]
+        keep.append((row[row >= 0] if nonneg else row).to(torch.int32))
+    lens = [int(k.numel()) for k in keep]
+    buf = torch.zeros((len(keep), max(lens) + room), dtype=torch.int32, device=input_ids.device)
+    for b, k in enumerate(keep):
+        buf[b, :lens[b]] = k
+    return buf, lens
+
+
+class _History:
+    """A device_history that grows on the device: `append` writes one id per row behind what the row holds, with no host wait."""
+
+    def __init__(self, input_ids, room, attention_mask=None, nonneg=False):
+        self.buf, self.lens = device_history(input_ids, room, attention_mask, nonneg)
+        self._pos = torch.tensor(self.lens, dtype=torch.long, device=self.buf.device).unsqueeze(1)
+
+    def row_ptr(self, b: int) -> int:
+        return self.buf.data_ptr() + 4 * b * self.buf.stride(0)
+
+    def append(self, ids: torch.Tensor) -> None:
+        self.buf.scatter_(1, self._pos, ids.unsqueeze(1))
+        self._pos += 1
+
+
+class StepPicker:
+    """pick(step, logits) -> the [B] next ids of a generate() call, in one of three modes chosen once: ops.argmax; ops.sample_top_p; or
+    ONE ops.sample_rows launch per step (row b: stream = b, counter = step -- the draws of the scalar sampler), preceded by ONE
+    ops.ban_rows launch when an n-gram ban is on. Everything the per-row mode reads is uploaded here, once, for all steps:
+      - the static allow masks and the [steps, B] array of their addresses (vt_sample_rows_allow reads row `step` of it);
+      - the [steps, B] vt_sample_row array (counter = step, history_len = prompt ids + step);
+      - the penalty history (the non-negative prompt ids, then the picks) -- with a repetition penalty;
+      - with no_repeat_ngram_size: the ban history (the ids where attention_mask is 1, sentinels included, then the picks), the [steps, B]
+        vt_ban_row array (history_len = prompt ids + step, base = the step's static mask or NULL) and the B working masks vt_ban_rows
+        writes, which are what the sampler's allow pointers name then -- the same B addresses at every step.
+    Both histories grow on the device. The device-built masks are never read back."""
+
+    def __init__(self, a: GenerateArgs, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], V: int):
+        self.a = a
+        self.V = int(V)
+        self.B = B = input_ids.shape[0]
+        self.device = input_ids.device
+        self.mode = "rows" if a.per_row else ("top_p" if a.do_sample else "argmax")
+        self._lp: List[torch.Tensor] = []
+        if self.mode != "rows":
+            return
+        dev, steps = self.device, a.max_new_tokens
+        self.allow_ptrs = None
+        step_base = [0] * max(steps, 0)          # host: the address of every step's static mask (0: none), the `base` of its vt_ban_row
+        if a.constrained:
+            self.allow_dev = torch.from_numpy(a.masks.view("<i4")).to(dev)                                      # [n_masks, words]
+            step_base = [0 if i < 0 else self.allow_dev[i].data_ptr() for i in a.step_mask]
+            self.allow_ptrs = torch.tensor([[p] * B for p in step_base], dtype=torch.int64).to(dev)             # [steps, B]
+        self.hist = _History(input_ids, steps, nonneg=True) if float(a.repetition_penalty) != 1.0 else None
+        T, p, k = (float(a.temperature), float(a.top_p if a.top_p else 1.0), int(a.top_k or 0)) if a.do_sample else (0.0, 1.0, 0)
+        self.rows = pack_sample_rows(
+            [(T, k, p, float(a.repetition_penalty), a.sample_seed, st, b,
+              0 if self.hist is None else self.hist.row_ptr(b), 0 if self.hist is None else self.hist.lens[b] + st)
+             for st in range(steps) for b in range(B)], dev).view(steps, B, ROW_BYTES)
+        self.ban_rows = None
+        if a.ngram:
+            self.ban_hist = h = _History(input_ids, steps, attention_mask)
+            self.ban_work = w = torch.empty((B, mask_words(self.V)), dtype=torch.int32, device=dev)
+            work_ptr = [w.data_ptr() + 4 * b * w.stride(0) for b in range(B)]
+            self.ban_rows = pack_ban_rows([(h.row_ptr(b), h.lens[b] + st, step_base[st], work_ptr[b], a.ngram, 0, 0, 0)
+                                           for st in range(steps) for b in range(B)], dev).view(steps, B, BAN_ROW_BYTES)
+            self.ban_ptrs = torch.tensor(work_ptr, dtype=torch.int64).to(dev)
+
+    def check_width(self, logits: torch.Tensor) -> None:
+        if self.mode == "rows" and (self.a.constrained or self.a.ngram) and logits.shape[1] != self.V:
+            raise RuntimeError(f"generate: the allow masks were built for V = {self.V}, the logits have {logits.shape[1]} columns")
+
+    def pick(self, step: int, logits: torch.Tensor) -> torch.Tensor:
+        a = self.a
+        if self.mode == "argmax":
+            return ops.argmax(logits)
+        if self.mode == "top_p":   # device-side temperature / top-k / top-p sampler (no host sync, counter-based RNG)
+            return ops.sample_top_p(logits, a.temperature, a.top_p if a.top_p else 1.0, a.sample_seed, step, top_k=int(a.top_k or 0))
+        if self.ban_rows is not None:            # the rows' masks for this pick, from their histories: one launch, nothing uploaded
+            ops.ban_rows(self.ban_rows[step], self.B, logits.shape[1])
+            ptrs = self.ban_ptrs
+        else:
+            ptrs = None if self.allow_ptrs is None else self.allow_ptrs[step]
+        nxt = ops.sample_rows(logits, self.rows[step], return_logprob=bool(a.return_logprobs), _allow_ptrs=ptrs)
+        if a.return_logprobs:
+            nxt, lp = nxt
+            self._lp.append(lp)
+        if self.hist is not None:
+            self.hist.append(nxt)
+        if self.ban_rows is not None:
+            self.ban_hist.append(nxt)
+        return nxt
+
+    def logprobs(self, n: int) -> torch.Tensor:
+        """fp32 [B, n]: the log-probabilities collected by the first n picks."""
+        if not self._lp:
+            return torch.empty((self.B, 0), dtype=torch.float32, device=self.device)
+        return torch.stack(self._lp, 1)[:, :n]

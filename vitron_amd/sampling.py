@@ -13,6 +13,7 @@ seen so far, so their mask is built on the DEVICE (struct vt_ban_row, `pack_ban_
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import numbers
 from dataclasses import dataclass
@@ -59,7 +60,7 @@ class SamplingParams:
     """How ONE request picks its tokens. temperature 0 is greedy; top_k None means config.top_k (default 50, as in `generate`);
     `seed` with the number of tokens generated so far is the whole state of the request's random stream, so its draws do not depend on
     what else is in the batch. logprobs=True collects the chosen token's log-probability per step (ServingEngine.logprobs).
-    Two more constraints are keyword arguments of the constructor: no_repeat_ngram_size (int >= 0, 0 is off: no n-gram of
+    The last two fields are history-dependent bans: no_repeat_ngram_size (int >= 0, 0 is off: no n-gram of
     that size occurs twice in prompt + reply, NoRepeatNGramLogitsProcessor) and bad_words (non-empty id sequences, one or several tokens:
     the last id of a sequence is banned while the ids before it are the end of prompt + reply, NoBadWordsLogitsProcessor). Their masks
     depend on the history and are built on the device, never read back: a step at which they leave nothing to emit cannot raise; the
@@ -76,23 +77,9 @@ class SamplingParams:
     min_new_tokens: int = 0                                  # the request's EOS ids are banned while it has generated fewer tokens
     choices: Optional[Tuple[Tuple[int, ...], ...]] = None    # the reply is exactly one of these id sequences, followed by EOS
     allowed_tokens_fn: Optional[Callable] = None             # generated ids -> iterable of allowed ids, or None (PrefixConstrained)
-    # ---- history-dependent bans. They come after the fields above in the constructor, are frozen, and take part in ==, hash, repr and
-    # replace() -- but they are plain attributes, NOT dataclass fields: the field list above is pinned as it is
-    # (tests/test_allow_ref_host.py), so the generated __init__ / __eq__ / __hash__ / __repr__ are replaced by the ones below, and
-    # dataclasses.replace() would drop the two: use SamplingParams.replace().
-    _EXTRA = (("no_repeat_ngram_size", 0), ("bad_words", None))
-
-    def __init__(self, temperature: float = 0.0, top_p: float = 1.0, top_k: Optional[int] = None, seed: int = 0,
-                 repetition_penalty: float = 1.0, logprobs: bool = False, allowed_token_ids=None, banned_token_ids=None,
-                 min_new_tokens: int = 0, choices=None, allowed_tokens_fn: Optional[Callable] = None,
-                 no_repeat_ngram_size: int = 0, bad_words=None):
-        for name, value in (("temperature", temperature), ("top_p", top_p), ("top_k", top_k), ("seed", seed),
-                            ("repetition_penalty", repetition_penalty), ("logprobs", logprobs), ("allowed_token_ids", allowed_token_ids),
-                            ("banned_token_ids", banned_token_ids), ("min_new_tokens", min_new_tokens), ("choices", choices),
-                            ("allowed_tokens_fn", allowed_tokens_fn), ("no_repeat_ngram_size", no_repeat_ngram_size),
-                            ("bad_words", bad_words)):
-            object.__setattr__(self, name, value)
-        self.__post_init__()
+    # ---- history-dependent bans: their masks are built on the device from the request's history ----
+    no_repeat_ngram_size: int = 0                            # no n-gram of this size occurs twice in prompt + reply (0 is off)
+    bad_words: Optional[Tuple[Tuple[int, ...], ...]] = None  # id sequences whose last id is banned while the ids before it end the history
 
     def __post_init__(self):
         def ids(x, what):
@@ -111,24 +98,9 @@ class SamplingParams:
                 object.__setattr__(self, name, tuple(ids(c, name) for c in seqs))
         self.validate()
 
-    def _key(self) -> tuple:
-        return tuple(getattr(self, n) for n in self.__dataclass_fields__) + tuple(getattr(self, n) for n, _ in self._EXTRA)
-
-    def __eq__(self, other):
-        return self._key() == other._key() if other.__class__ is self.__class__ else NotImplemented
-
-    def __hash__(self):
-        return hash(self._key())
-
-    def __repr__(self):
-        names = list(self.__dataclass_fields__) + [n for n, _ in self._EXTRA]
-        return "SamplingParams(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in names) + ")"
-
     def replace(self, **changes) -> "SamplingParams":
-        """A copy with some arguments changed (dataclasses.replace knows only the dataclass fields)."""
-        kw = {n: getattr(self, n) for n in list(self.__dataclass_fields__) + [n for n, _ in self._EXTRA]}
-        kw.update(changes)
-        return SamplingParams(**kw)
+        """A copy with some fields changed (dataclasses.replace)."""
+        return dataclasses.replace(self, **changes)
 
     def validate(self) -> None:
         check_sampling_values(self.temperature, self.top_p, self.top_k, self.repetition_penalty, "SamplingParams")

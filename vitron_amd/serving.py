@@ -35,6 +35,7 @@ import torch
 
 from . import ops
 from .engine import PagedKVCache, SequenceState, llama_forward, pair_lo, parse_kv_cache_dtype
+from .picker import device_history
 from .sampling import SamplingParams, check_constraints, flatten_ban_seqs, mask_words, pack_ban_rows, pack_sample_rows, step_allow_mask
 
 
@@ -197,12 +198,8 @@ class ServingEngine:
                 rows.append((self.temperature if self.do_sample else 0.0, 0, self.top_p, 1.0, self.seed, self._step, i, 0, 0))
                 continue
             if (sp.repetition_penalty != 1.0 or sp.device_bans) and r.hist is None:
-                keep = r.input_ids[0].to(torch.int32)
-                if not sp.device_bans:
-                    keep = keep[keep >= 0]                                          # (the image / region sentinels are negative)
-                r.hist = torch.empty((keep.numel() + r.max_new_tokens,), dtype=torch.int32, device=keep.device)
-                r.hist[:keep.numel()] = keep
-                r.hist_len = int(keep.numel())
+                buf, lens = device_history(r.input_ids, r.max_new_tokens, nonneg=not sp.device_bans)
+                r.hist, r.hist_len = buf[0], lens[0]
             rows.append((sp.temperature, sp.resolved_top_k(self.model.config), sp.top_p, sp.repetition_penalty, sp.seed, len(r.tokens), 0,
                          *((r.hist.data_ptr(), r.hist_len) if sp.repetition_penalty != 1.0 else (0, 0))))
         want_lp = any(r.sampling is not None and r.sampling.logprobs for r in reqs)
