@@ -92,6 +92,8 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
 /* 114 also carries vt_beam_step, vt_beam_step_scratch_bytes and vt_kv_copy_pages WITHOUT a bump: three new symbols, no struct and no
  * existing signature changes. */
 /* 114 also carries vt_ban_rows and struct vt_ban_row WITHOUT a bump: one new symbol and one new struct; the samplers do not change. */
+/* 114 also carries vt_bias_rows, struct vt_bias_row and vt_sample_rows_adj WITHOUT a bump: two new symbols and one new struct; struct
+ * vt_sample_row, vt_sample_rows and vt_sample_rows_allow do not change. */
 #define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
@@ -435,6 +437,68 @@ typedef struct vt_ban_row {
   int32_t seqs_len;
 } vt_ban_row;
 int vt_ban_rows(const vt_ban_row* rows /* DEVICE */, int n_rows, int V, void* stream);
+
+/* ADDITIVE ADJUSTMENTS: logit_bias / single-token sequence_bias and the presence / frequency penalties (the role of
+ * transformers' SequenceBiasLogitsProcessor and of the OpenAI / vLLM penalties). A row's adjustment `adj` is V pairs (pre, post) of fp32:
+ * adj[2t] = pre[t], adj[2t + 1] = post[t]. The value the sampler uses for token t, every arithmetic step rounded to fp32 separately (no
+ * fused multiply-add anywhere):
+ *     x = raw[t];  if the allow bit of t is clear: x = -inf                       (vt_sample_rows_allow)
+ *     x = x + pre[t]                                                              (logit_bias / sequence_bias)
+ *     if t is in the penalty history and penalty != 1: x = x < 0 ? x * penalty : x / penalty     (vt_sample_rows step 1, bit for bit)
+ *     x = x + post[t]                                                             (presence / frequency)
+ * -- transformers runs SequenceBiasLogitsProcessor in front of RepetitionPenaltyLogitsProcessor; vLLM applies logit_bias, then the
+ * repetition penalty, then frequency and presence. Everything after that (greedy pick, temperature, top-k, top-p, the draw, kept_count)
+ * is vt_sample_rows_allow's arithmetic on x. logprob stays raw[id] - logsumexp(raw) over the RAW row.
+ *
+ * vt_bias_rows builds the adjustments on the device, nothing is read on the host. rows: DEVICE array of n_rows vt_bias_row (48 bytes
+ * each, 8-byte aligned; the offsets are part of the ABI):
+ *   @0  const int32_t* history      DEVICE ids the counts are taken over: the tokens the row has GENERATED so far (not the prompt); may be NULL
+ *   @8  const int32_t* bias_ids     DEVICE, n_bias distinct ids; may be NULL
+ *   @16 const float*   bias_vals    DEVICE, n_bias values
+ *   @24 float*         out          DEVICE fp32 [V][2] to write; NULL = this row is skipped entirely
+ *   @32 int32_t        history_len  <= 0: empty history
+ *   @36 int32_t        n_bias       <= 0: none (also when bias_ids or bias_vals is NULL)
+ *   @40 float          presence
+ *   @44 float          frequency
+ * Per row:
+ *   - pre[t] = bias_vals[j] if bias_ids[j] == t for some j < n_bias, else 0.0f. Ids outside [0, V) are skipped and index nothing. The
+ *     caller guarantees distinct ids; with a duplicate one of its values lands and nothing else is affected.
+ *   - post[t], with c = the number of i < history_len with history[i] == t:  c == 0 ? 0.0f : -(frequency * (float)c + presence), the
+ *     product and the sum rounded separately. History ids outside [0, V) are skipped. Counting is over generated tokens only (OpenAI's
+ *     and vLLM's definition); the repetition penalty keeps its own prompt + reply history in vt_sample_row.
+ *   - counts are 16-bit integers in LDS: a row with history_len > 65535 counts its LAST 65535 entries only. Integer counts make the
+ *     result independent of the order of the atomics: it is deterministic.
+ * The kernel is total: no field value leads to an access outside history[0 .. history_len), bias_ids / bias_vals[0 .. n_bias) or the
+ * 2 * V floats of out (the inputs must be readable for those lengths when set); floats of a larger buffer behind out are not touched.
+ * out must NOT alias another row's out. An out that is 8-byte aligned is written with 8-byte stores.
+ * Refused with VT_STATUS_ARG and a message before any launch: V <= 0, V > VT_BIAS_ROWS_MAX_V, n_rows < 0, rows == NULL with n_rows > 0.
+ * n_rows == 0 is a success that launches nothing. One launch, one 1024-thread block per row: the counts live in dynamic LDS sized by V
+ * (two 16-bit counters per word, 128 KiB at the limit, plus V bits).
+ * 114 carries these entry points WITHOUT a bump: two new symbols and one new struct, nothing existing changes (see the note at VT_ABI_VERSION). */
+#define VT_BIAS_ROWS_MAX_V 65536
+typedef struct vt_bias_row {
+  const int32_t* history;
+  const int32_t* bias_ids;
+  const float* bias_vals;
+  float* out;
+  int32_t history_len;
+  int32_t n_bias;
+  float presence;
+  float frequency;
+} vt_bias_row;
+int vt_bias_rows(const vt_bias_row* rows /* DEVICE */, int n_rows, int V, void* stream);
+
+/* vt_sample_rows_allow with a PER-ROW ADJUSTMENT, applied as stated above.
+ * adjust: DEVICE array of `rows` device pointers (8-byte aligned); adjust[r] points to fp32 [V][2] (8-byte aligned, what vt_bias_rows
+ *   writes), or is NULL: no adjustment for that row. No float outside the 2 * V of a row's adjustment is read.
+ * adjust == NULL is the vt_sample_rows_allow launch itself (and with allow == NULL too, vt_sample_rows'). allow may be NULL with adjust
+ * set. out_ids and kept_count are bit-equal to what vt_sample_rows_allow returns, with repetition_penalty 1, on a copy of the logits
+ * holding the values x above. Both forms (row in registers; streaming), the argument checks and VT_SAMPLE_ROWS_MAX_V are
+ * vt_sample_rows's; the adjustment stays in global memory in both forms. */
+int vt_sample_rows_adj(const float* logits, int rows, int V, int ldl, const vt_sample_row* params,
+                       const uint32_t* const* allow /* DEVICE array of `rows` device pointers, entries and the array may be NULL */,
+                       const float* const* adjust /* DEVICE array of `rows` device pointers to fp32 [V][2], entries and the array may be NULL */,
+                       int* out_ids, int* kept_count, float* logprob, void* stream);
 
 /* BEAM SEARCH (the role of transformers' GenerationMixin beam search: log_softmax + running scores + torch.topk over
  * num_beams * vocab, and the cache reorder behind it).

@@ -110,10 +110,12 @@ SIGNATURES = {
     "vt_sample_top_p": (_i, [vp, _i, _i, _i, _f, _i, _f, C.c_uint64, C.c_uint64, vp, vp, vp]),
     "vt_sample_rows": (_i, [vp, _i, _i, _i, vp, vp, vp, vp, vp]),
     "vt_sample_rows_allow": (_i, [vp, _i, _i, _i, vp, vp, vp, vp, vp, vp]),
+    "vt_sample_rows_adj": (_i, [vp, _i, _i, _i, vp, vp, vp, vp, vp, vp, vp]),
     "vt_beam_step_scratch_bytes": (_sz, [_i, _i, _i]),
     "vt_beam_step": (_i, [vp, _i, _i, _i, _i, vp, _i, vp, vp, vp, vp, _sz, vp]),
     "vt_kv_copy_pages": (_i, [vp, vp, _i, _i, _sz, vp, vp, _i, vp]),
     "vt_ban_rows": (_i, [vp, _i, _i, vp]),
+    "vt_bias_rows": (_i, [vp, _i, _i, vp]),
     "vt_projector_workspace_bytes": (_sz, [_i, _i]),
     "vt_projector_forward": (_i, [vp, _i, _i, vp, vp, _i, vp, vp, _i, vp, vp, _sz, vp]),
     "vt_projector_precise_workspace_bytes": (_sz, [_i, _i, _i]),

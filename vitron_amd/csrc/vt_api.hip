@@ -457,6 +457,11 @@ int vt_sample_rows_allow(const float* logits, int rows, int V, int ldl, const vt
   return vt_sample_rows_launch(logits, rows, V, ldl, params, allow, out_ids, kept_count, logprob, S(stream));
 }
 
+int vt_sample_rows_adj(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, const uint32_t* const* allow,
+                       const float* const* adjust, int* out_ids, int* kept_count, float* logprob, void* stream) {
+  return vt_sample_rows_launch(logits, rows, V, ldl, params, allow, out_ids, kept_count, logprob, S(stream), adjust);
+}
+
 // ---- beam search (vt_beam.hip) ----------------------------------------------------------------------------------------
 size_t vt_beam_step_scratch_bytes(int groups, int beams_in, int n_out) { return vt_beam_step_scratch_bytes_impl(groups, beams_in, n_out); }
 
@@ -473,6 +478,7 @@ int vt_kv_copy_pages(void* k, void* vt, int num_layers, int num_pages, size_t pa
 
 // ---- history-dependent bans (vt_ban.hip) ------------------------------------------------------------------------------
 int vt_ban_rows(const vt_ban_row* rows, int n_rows, int V, void* stream) { return vt_ban_rows_launch(rows, n_rows, V, S(stream)); }
+int vt_bias_rows(const vt_bias_row* rows, int n_rows, int V, void* stream) { return vt_bias_rows_launch(rows, n_rows, V, S(stream)); }
 
 // ---- mm_projector ---------------------------------------------------------------------------------------------------
 size_t vt_projector_workspace_bytes(int M, int Dh) { return align_up((size_t)M * Dh * 2, 256) + 256; }

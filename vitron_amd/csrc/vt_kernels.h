@@ -263,7 +263,8 @@ int vt_cross_entropy_launch(const float* logits, int rows, int V, int ldl, const
 int vt_sample_top_p_launch(const float* logits, int rows, int V, int ldl, float temperature, int top_k, float top_p, uint64_t seed,
                            uint64_t step, int* out_ids, int* kept_count, hipStream_t s);
 int vt_sample_rows_launch(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, const uint32_t* const* allow,
-                          int* out_ids, int* kept_count, float* logprob, hipStream_t s);   // allow == NULL: vt_sample_rows
+                          int* out_ids, int* kept_count, float* logprob, hipStream_t s,    // allow == NULL: vt_sample_rows
+                          const float* const* adjust = nullptr);                           // adjust != NULL: vt_sample_rows_adj
 
 // ---- vt_beam.hip ----------------------------------------------------------------------------------
 size_t vt_beam_step_scratch_bytes_impl(int groups, int beams_in, int n_out);
@@ -274,6 +275,9 @@ int vt_kv_copy_pages_launch(void* k, void* vt, int num_layers, int num_pages, si
 
 // ---- vt_ban.hip -----------------------------------------------------------------------------------
 int vt_ban_rows_launch(const vt_ban_row* rows, int n_rows, int V, hipStream_t s);
+
+// ---- vt_bias.hip ----------------------------------------------------------------------------------
+int vt_bias_rows_launch(const vt_bias_row* rows, int n_rows, int V, hipStream_t s);
 
 // ---- vt_preproc.hip -------------------------------------------------------------------------------
 int vt_preprocess_launch(const void* src, int src_u8, int hwc, int F, int H, int W, int bicubic, int S, const float* mean,

@@ -192,6 +192,12 @@ __device__ __forceinline__ float sample_uniform24(const SampleArgs& a) {   // (0
 // RepetitionPenaltyLogitsProcessor on one logit (transformers 4.31: torch.where(score < 0, score * penalty, score / penalty)), fp32 with
 // the correctly rounded divide: torch's fp32 result bit for bit
 __device__ __forceinline__ float penalise(float x, float penalty) { return x < 0.f ? x * penalty : __fdiv_rn(x, penalty); }
+// One addition of the additive adjustment (kAdj), rounded on its own: hipcc contracts a * b + c into an fma by default
+// (__fadd_rn is a plain + to it), which would fuse penalise()'s product with the post term.
+__device__ __forceinline__ float add_rounded(float x, float y) {
+#pragma clang fp contract(off)
+  return x + y;
+}
 
 // V-bit "seen" mask of the row's history in LDS: bit id is set for every history id in [0, V). Ids outside that range (the negative
 // image / region sentinels of a multimodal prompt, anything >= V) are skipped and index nothing. Returns whether a penalty applies.
@@ -217,10 +223,12 @@ __device__ __forceinline__ bool fill_seen_mask(uint32_t* seen, int V, const Samp
 // kAllow (vt_sample_rows_allow): `allow` is the row's V-bit allow mask in GLOBAL memory (ceil(V/32) words, NULL = all
 // allowed). val(i) reads word i >> 5 for i < V only -- always inside the mask -- and a token whose bit is clear is -inf BEFORE the penalty,
 // i.e. exactly a row with -inf written there. The raw log-sum-exp does not go through val(): logprob stays over the RAW row.
-template <bool kRows, bool kAllow = false>
+// kAdj (vt_sample_rows_adj): `adj` is the row's additive adjustment in GLOBAL memory, fp32 [V][2] = (pre, post) per token,
+// 8-byte aligned, NULL = none. val(i) reads pair i for i < V only; pre is added after the mask and before the penalty, post after it.
+template <bool kRows, bool kAllow = false, bool kAdj = false>
 __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row, int V, const SampleArgs& a, uint32_t* seen,
                                                    int* __restrict__ out_id, int* __restrict__ kept_out, float* __restrict__ logprob,
-                                                   const uint32_t* __restrict__ allow = nullptr) {
+                                                   const uint32_t* __restrict__ allow = nullptr, const float* __restrict__ adj = nullptr) {
   __shared__ float sh[16];
   __shared__ float sh_scan[16];
   __shared__ int chosen;
@@ -245,8 +253,18 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
     float x = row[i];
     if constexpr (kAllow)
       if (allow && !((allow[i >> 5] >> (i & 31)) & 1u)) x = -INFINITY;
+    float post = 0.f;
+    if constexpr (kAdj) {
+      if (adj) {         // block-uniform
+        const float2 pq = *(const float2*)(adj + 2 * (size_t)i);
+        x = add_rounded(x, pq.x);
+        post = pq.y;
+      }
+    }
     if constexpr (kRows)
       if (pen && ((seen[i >> 5] >> (i & 31)) & 1u)) x = penalise(x, a.penalty);
+    if constexpr (kAdj)
+      if (adj) x = add_rounded(x, post);
     return x;
   };
   if constexpr (kRows) {
@@ -374,10 +392,13 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
 // kAllow: word t of the row's allow mask is read straight from global memory (threads past ceil(V/32) read nothing: their slots are
 // -inf already) and applied under the same static unroll, after the raw log-sum-exp and before the penalty. Bits >= V of the last
 // word meet slots that are -inf whatever the bit says.
-template <bool kRows, bool kAllow = false>
+// kAdj: the thread's 32 (pre, post) pairs are 256 contiguous bytes of the row's adjustment in global memory, read once -- 16 bytes (two
+// pairs) at a time where the adjustment is 16-byte aligned, else 8: pre is added after the mask, then the penalty, then post, slot by
+// slot. Slots past V read nothing and stay -inf.
+template <bool kRows, bool kAllow = false, bool kAdj = false>
 __device__ __forceinline__ void sample_reg_body(const float* __restrict__ row, int V, const SampleArgs& a, uint32_t* seen,
                                                 int* __restrict__ out_id, int* __restrict__ kept_out, float* __restrict__ logprob,
-                                                const uint32_t* __restrict__ allow = nullptr) {
+                                                const uint32_t* __restrict__ allow = nullptr, const float* __restrict__ adj = nullptr) {
   constexpr int NPT = 32;
   __shared__ float sh[2][16];
   __shared__ float sh_scan[16];
@@ -442,7 +463,42 @@ __device__ __forceinline__ void sample_reg_body(const float* __restrict__ row, i
           if (!((ok >> j) & 1u)) p[j] = -INFINITY;
       }
     }
-    if (fill_seen_mask(seen, V, a)) {
+    const bool pen = fill_seen_mask(seen, V, a);
+    bool adjusted = false;
+    if constexpr (kAdj) {
+      if (adj) {         // block-uniform: pre, the penalty and post in one pass over the thread's 32 pairs
+        adjusted = true;
+        const uint32_t word = pen ? seen[tid] : 0u;
+        auto apply = [&](float x, float pre, float post, int j) -> float {
+          x = add_rounded(x, pre);
+          if ((word >> j) & 1u) x = penalise(x, a.penalty);
+          return add_rounded(x, post);
+        };
+        const float* __restrict__ mine = adj + 2 * i0;
+        if (((uintptr_t)adj % 16) == 0) {      // block-uniform: two pairs per 16-byte load, half the (lane-strided) load instructions
+#pragma unroll
+          for (int j = 0; j < NPT; j += 2) {
+            if (i0 + j + 1 < V) {
+              const f32x4 q = *(const f32x4*)(mine + 2 * j);
+              p[j] = apply(p[j], q[0], q[1], j);
+              p[j + 1] = apply(p[j + 1], q[2], q[3], j + 1);
+            } else if (i0 + j < V) {
+              const float2 q = *(const float2*)(mine + 2 * j);
+              p[j] = apply(p[j], q.x, q.y, j);
+            }
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < NPT; ++j) {
+            if (i0 + j < V) {
+              const float2 q = *(const float2*)(mine + 2 * j);
+              p[j] = apply(p[j], q.x, q.y, j);
+            }
+          }
+        }
+      }
+    }
+    if (pen && !adjusted) {
       const uint32_t word = seen[tid];
 #pragma unroll
       for (int j = 0; j < NPT; ++j)
@@ -634,6 +690,27 @@ __global__ __launch_bounds__(1024) void sample_rows_allow_kernel(const float* __
     sample_stream_body<true, true>(row, V, a, seen, out_ids + r, kept_count ? kept_count + r : nullptr, logprob ? logprob + r : nullptr,
                                    mask);
 }
+// vt_sample_rows_adj: the allow launch with row r's additive adjustment adjust[r] (a device pointer to fp32 [V][2], or NULL: none). A
+// kernel of its own again, so that the two above stay the code they were. Here the allow ARRAY may be NULL too (adjustments without masks).
+template <bool kReg>
+__global__ __launch_bounds__(1024) void sample_rows_adj_kernel(const float* __restrict__ logits, int V, int ldl,
+                                                               const vt_sample_row* __restrict__ params,
+                                                               const uint32_t* const* __restrict__ allow,
+                                                               const float* const* __restrict__ adjust, int* __restrict__ out_ids,
+                                                               int* __restrict__ kept_count, float* __restrict__ logprob) {
+  __shared__ uint32_t seen[(kReg ? 32 * 1024 : kSampleRowsMaxV) / 32];
+  const int r = blockIdx.x;
+  const SampleArgs a = row_args(params[r]);
+  const float* row = logits + (size_t)r * ldl;
+  const uint32_t* mask = allow ? allow[r] : nullptr;
+  const float* adj = adjust[r];
+  if constexpr (kReg)
+    sample_reg_body<true, true, true>(row, V, a, seen, out_ids + r, kept_count ? kept_count + r : nullptr, logprob ? logprob + r : nullptr,
+                                      mask, adj);
+  else
+    sample_stream_body<true, true, true>(row, V, a, seen, out_ids + r, kept_count ? kept_count + r : nullptr,
+                                         logprob ? logprob + r : nullptr, mask, adj);
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Shifted-token cross entropy of LlamaForCausalLM.forward(labels=...) (ignore_index rows skipped, mean over the rest):
@@ -699,13 +776,17 @@ int vt_sample_top_p_launch(const float* logits, int rows, int V, int ldl, float 
 }
 
 int vt_sample_rows_launch(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, const uint32_t* const* allow,
-                          int* out_ids, int* kept_count, float* logprob, hipStream_t s) {
+                          int* out_ids, int* kept_count, float* logprob, hipStream_t s, const float* const* adjust) {
   VT_REQUIRE(logits && params && out_ids, "vt_sample_rows: null pointer (logits, params and out_ids are required)");
   VT_REQUIRE(rows > 0 && V > 0 && ldl >= V, "vt_sample_rows: rows=%d V=%d ldl=%d (rows, V > 0 and ldl >= V)", rows, V, ldl);
   VT_REQUIRE(((uintptr_t)params % 8) == 0, "vt_sample_rows: params must be 8-byte aligned");
   VT_REQUIRE(((uintptr_t)allow % 8) == 0, "vt_sample_rows_allow: the allow pointer array must be 8-byte aligned");
+  VT_REQUIRE(((uintptr_t)adjust % 8) == 0, "vt_sample_rows_adj: the adjust pointer array must be 8-byte aligned");
   if (V <= 32 * 1024 && (ldl % 4) == 0 && ((uintptr_t)logits % 16) == 0) {
-    if (allow)
+    if (adjust)
+      hipLaunchKernelGGL(sample_rows_adj_kernel<true>, dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, allow, adjust, out_ids,
+                         kept_count, logprob);
+    else if (allow)
       hipLaunchKernelGGL(sample_rows_allow_kernel<true>, dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, allow, out_ids,
                          kept_count, logprob);
     else
@@ -713,7 +794,10 @@ int vt_sample_rows_launch(const float* logits, int rows, int V, int ldl, const v
   } else {
     VT_REQUIRE(V <= VT_SAMPLE_ROWS_MAX_V, "vt_sample_rows: V=%d is beyond the history mask of the streaming form (V <= %d)", V,
                VT_SAMPLE_ROWS_MAX_V);
-    if (allow)
+    if (adjust)
+      hipLaunchKernelGGL(sample_rows_adj_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, allow, adjust, out_ids,
+                         kept_count, logprob);
+    else if (allow)
       hipLaunchKernelGGL(sample_rows_allow_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, allow, out_ids,
                          kept_count, logprob);
     else

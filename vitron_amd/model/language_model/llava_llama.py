@@ -468,7 +468,8 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                  stopping_criteria=None, eos_token_id=None, pad_token_id=None, num_beams=1, seed=None,
                  return_logits=False, padded_batch=False, repetition_penalty=1.0, return_logprobs=False, suppress_tokens=None,
                  begin_suppress_tokens=None, min_new_tokens=None, bad_words_ids=None, allowed_token_ids=None, num_return_sequences=1,
-                 length_penalty=1.0, early_stopping=False, no_repeat_ngram_size=None, **kwargs):
+                 length_penalty=1.0, early_stopping=False, no_repeat_ngram_size=None, sequence_bias=None, presence_penalty=0.0,
+                 frequency_penalty=0.0, **kwargs):
         """repetition_penalty (RepetitionPenaltyLogitsProcessor; 1.0 is off) and return_logprobs: with both at their defaults a step
         launches what it always did (vt_argmax / vt_sample_top_p). Otherwise every step is ONE vt_sample_rows launch (row b: stream = b,
         counter = step -- today's draws) whose penalty history -- the sample's non-negative prompt ids plus what it has generated -- lives
@@ -488,6 +489,13 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         those masks. Every step's vt_ban_row array is uploaded once before the loop: no host wait, no per-step upload. The device-built
         mask is never read back, so a row it leaves nothing for cannot raise: it gets what vt_sample_rows_allow defines for a row with
         nothing allowed (the static constraints keep their host checks). Refused with NotImplementedError: num_beams > 1, padded_batch.
+        Additive adjustments: sequence_bias (transformers' dict {tuple of ids: float}, SequenceBiasLogitsProcessor; a bare
+        int is a one-token key; a key of several tokens raises NotImplementedError) is added to the logits BEFORE the repetition penalty;
+        presence_penalty and frequency_penalty (OpenAI's / vLLM's; any finite float) take presence + frequency * count off every id the
+        sample has GENERATED so far, AFTER it. Each sample owns a [V][2] adjustment on the device that vt_bias_rows rebuilds before every
+        pick from the sample's generated ids (once, before the prefill, with sequence_bias alone) and vt_sample_rows_adj reads; nothing
+        is uploaded or waited for in the loop. return_logits and return_logprobs stay RAW. ValueError: an id outside [0, vocab_size), a
+        value that is not finite, an id given twice. Refused with NotImplementedError: num_beams > 1, padded_batch.
         padded_batch=True (B > 1, right padding): reproduce what the REFERENCE's batched generate() returns -- transformers 4.31 reads the
         first token of every sample from the last COLUMN of the padded logits (a pad row for the shorter samples) and the decode-step
         fix-up (llava_arch.py:196-205) attends the pad rows of the spliced batch while masking the rows that share an index with the
@@ -511,7 +519,8 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
             repetition_penalty=repetition_penalty, return_logprobs=return_logprobs, suppress_tokens=suppress_tokens,
             begin_suppress_tokens=begin_suppress_tokens, min_new_tokens=min_new_tokens, bad_words_ids=bad_words_ids,
             allowed_token_ids=allowed_token_ids, num_return_sequences=num_return_sequences, length_penalty=length_penalty,
-            early_stopping=early_stopping, no_repeat_ngram_size=no_repeat_ngram_size)
+            early_stopping=early_stopping, no_repeat_ngram_size=no_repeat_ngram_size, sequence_bias=sequence_bias,
+            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty)
         dev = self.device
         input_ids = input_ids.to(dev)
         B, L0 = input_ids.shape

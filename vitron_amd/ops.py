@@ -529,15 +529,37 @@ def allow_pointers(allow, rows: int, V: int, device) -> torch.Tensor:
     return torch.tensor(ptrs, dtype=torch.int64).to(device)
 
 
+def adjust_pointers(adjust, rows: int, V: int, device) -> torch.Tensor:
+    """The device pointer array vt_sample_rows_adj reads (int64 [rows]) from one entry per row: None (NULL: no adjustment) or a
+    contiguous fp32 device tensor of 2 * V elements, the (pre, post) pairs ops.bias_rows writes. The caller keeps the buffers alive until
+    the launch has run. One small host -> device copy."""
+    if isinstance(adjust, torch.Tensor) or not hasattr(adjust, "__len__") or len(adjust) != rows:
+        raise _lib.VitronHipError(f"sample_rows.adjust: expected a sequence of {rows} entries (one per row), each None or an fp32 tensor")
+    ptrs = []
+    for i, m in enumerate(adjust):
+        if m is None:
+            ptrs.append(0)
+            continue
+        if not isinstance(m, torch.Tensor) or m.device != device or m.dtype != torch.float32 or not m.is_contiguous() \
+                or m.numel() != 2 * V or m.data_ptr() % 8:
+            raise _lib.VitronHipError(f"sample_rows.adjust[{i}]: expected None or a contiguous, 8-byte aligned fp32 tensor of {2 * V} "
+                                      f"elements ([V][2], V = {V}) on the logits' device")
+        ptrs.append(m.data_ptr())
+    return torch.tensor(ptrs, dtype=torch.int64).to(device)
+
+
 def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = False, return_logprob: bool = False, allow=None,
-                _allow_ptrs: Optional[torch.Tensor] = None):
+                _allow_ptrs: Optional[torch.Tensor] = None, adjust=None, _adjust_ptrs: Optional[torch.Tensor] = None):
     """One token id per row (int32, on device) with PER-ROW parameters: greedy and sampled rows, penalties and the chosen token's
     log-probability in one launch; see vt_sample_rows in include/vitron_hip.h. `params`: the device array of vt_sample_row that
     sampling.pack_sample_rows builds (uint8 [rows, 48]). Returns ids, or (ids[, kept_count][, logprob]) when either is asked for.
     allow: per-row allow masks (vt_sample_rows_allow) -- a sequence of `rows` entries, each None or a device tensor of ceil(V / 32)
     mask words; each is checked and the pointer array is built here. None: today's vt_sample_rows call.
     _allow_ptrs (private; generate's single upload, tools/sampler_bench.py): a pointer array that allow_pointers -- or its caller, from
-    masks it has checked itself -- built earlier, int64 [rows]; its values are dereferenced on the device as they are."""
+    masks it has checked itself -- built earlier, int64 [rows]; its values are dereferenced on the device as they are.
+    adjust: per-row additive adjustments (vt_sample_rows_adj) -- a sequence of `rows` entries, each None or a device fp32 tensor of
+    2 * V elements, the (pre, post) pairs of ops.bias_rows; pre is added before the repetition penalty, post after it. _adjust_ptrs is
+    its private pointer-array form, like _allow_ptrs. With neither, the launches are the ones above."""
     from .sampling import ROW_BYTES
     lib = _lib.load_any()
     _chk_rows(logits, torch.float32, "sample_rows.logits")
@@ -551,15 +573,29 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = 
     lp = torch.empty((rows,), device=logits.device, dtype=torch.float32) if return_logprob else None
     if allow is not None and _allow_ptrs is not None:
         raise _lib.VitronHipError("sample_rows: pass allow or _allow_ptrs, not both")
-    if allow is None and _allow_ptrs is None:
+    if adjust is not None and _adjust_ptrs is not None:
+        raise _lib.VitronHipError("sample_rows: pass adjust or _adjust_ptrs, not both")
+
+    def given_ptrs(ptrs, what):
+        if not isinstance(ptrs, torch.Tensor) or ptrs.dtype != torch.int64 or ptrs.device != logits.device or not ptrs.is_contiguous() \
+                or ptrs.numel() != rows:
+            raise _lib.VitronHipError(f"sample_rows.{what}: expected a contiguous int64 [{rows}] tensor on the logits' device")
+        return ptrs
+    if adjust is not None or _adjust_ptrs is not None:
+        aptrs = None
+        if _allow_ptrs is not None:
+            aptrs = given_ptrs(_allow_ptrs, "_allow_ptrs")
+        elif allow is not None:
+            aptrs = allow_pointers(allow, rows, V, logits.device)
+        jptrs = given_ptrs(_adjust_ptrs, "_adjust_ptrs") if _adjust_ptrs is not None else adjust_pointers(adjust, rows, V, logits.device)
+        _lib.check(lib.vt_sample_rows_adj(_p(logits), rows, V, logits.stride(0), _p(params), _p(aptrs), _p(jptrs), _p(out), _p(kept),
+                                          _p(lp), _stream()), "vt_sample_rows_adj", lib)
+    elif allow is None and _allow_ptrs is None:
         _lib.check(lib.vt_sample_rows(_p(logits), rows, V, logits.stride(0), _p(params), _p(out), _p(kept), _p(lp), _stream()),
                    "vt_sample_rows", lib)
     else:
         if _allow_ptrs is not None:
-            ptrs = _allow_ptrs
-            if not isinstance(ptrs, torch.Tensor) or ptrs.dtype != torch.int64 or ptrs.device != logits.device or not ptrs.is_contiguous() \
-                    or ptrs.numel() != rows:
-                raise _lib.VitronHipError(f"sample_rows._allow_ptrs: expected a contiguous int64 [{rows}] tensor on the logits' device")
+            ptrs = given_ptrs(_allow_ptrs, "_allow_ptrs")
         else:
             ptrs = allow_pointers(allow, rows, V, logits.device)
         _lib.check(lib.vt_sample_rows_allow(_p(logits), rows, V, logits.stride(0), _p(params), _p(ptrs), _p(out), _p(kept), _p(lp),
@@ -582,6 +618,22 @@ def ban_rows(rows_dev: torch.Tensor, n_rows: int, V: int) -> None:
             raise _lib.VitronHipError(f"ban_rows.rows_dev: expected {n_rows} x {BAN_ROW_BYTES} bytes (sampling.pack_ban_rows), got "
                                       f"{rows_dev.numel()}")
     _lib.check(lib.vt_ban_rows(_p(rows_dev) if n_rows > 0 else None, n_rows, int(V), _stream()), "vt_ban_rows", lib)
+
+
+def bias_rows(rows_dev: torch.Tensor, n_rows: int, V: int) -> None:
+    """Build the additive adjustments of n_rows rows on the device (logit bias, presence and frequency penalties over the generated
+    ids); see vt_bias_rows in include/vitron_hip.h. rows_dev: the device array of vt_bias_row that sampling.pack_bias_rows builds
+    (contiguous uint8, n_rows x 48 bytes). Every pointer inside it is dereferenced on the device as it is: the caller keeps the
+    buffers alive until the launch has run, sizes every `out` for 2 * V floats and lets no `out` alias another."""
+    from .sampling import BIAS_ROW_BYTES
+    lib = _lib.load_any()
+    n_rows = int(n_rows)
+    if n_rows > 0:
+        _chk(rows_dev, torch.uint8, "bias_rows.rows_dev")
+        if rows_dev.numel() != n_rows * BIAS_ROW_BYTES:
+            raise _lib.VitronHipError(f"bias_rows.rows_dev: expected {n_rows} x {BIAS_ROW_BYTES} bytes (sampling.pack_bias_rows), got "
+                                      f"{rows_dev.numel()}")
+    _lib.check(lib.vt_bias_rows(_p(rows_dev) if n_rows > 0 else None, n_rows, int(V), _stream()), "vt_bias_rows", lib)
 
 
 def beam_step(logits: torch.Tensor, beam_scores: torch.Tensor, groups: int, beams_in: int, n_out: int, packed: bool = False):

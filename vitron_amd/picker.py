@@ -2,9 +2,10 @@
 
 `resolve_generate_args` turns generate()'s keyword arguments into one frozen `GenerateArgs` and raises every refusal that needs no device
 work, in a fixed order. `StepPicker` is built from that record once, before the prefill: it uploads everything the picks of ALL steps
-need (the static allow masks and every step's pointer array, every step's vt_sample_row / vt_ban_row array, the device histories) and
+need (the static allow masks and every step's pointer array, every step's vt_sample_row / vt_ban_row / vt_bias_row array, the device
+histories, the adjustment buffers) and
 then serves `pick(step, logits) -> ids` without an upload or a host wait. `device_history` is the one builder of a penalty / ban
-history; ServingEngine fills a request's `hist` with it too. (DESIGN.md 9.3 - 9.6.)
+history; ServingEngine fills a request's `hist` with it too. (DESIGN.md 9.3 - 9.8.)
 """
 from __future__ import annotations
 
@@ -17,7 +18,8 @@ import torch
 
 from . import ops
 from .engine import parse_kv_cache_dtype
-from .sampling import BAN_ROW_BYTES, ROW_BYTES, allow_mask, check_sampling_values, mask_words, pack_ban_rows, pack_sample_rows
+from .sampling import (BAN_ROW_BYTES, BIAS_ROW_BYTES, BIAS_ROWS_MAX_V, ROW_BYTES, allow_mask, check_penalties, check_sampling_values,
+                       mask_words, normalise_bias, pack_ban_rows, pack_bias_rows, pack_sample_rows)
 
 
 @dataclass(frozen=True, eq=False)
@@ -47,15 +49,28 @@ class GenerateArgs:
     allowed_ids: Optional[Tuple[int, ...]] = None
     masks: Optional[np.ndarray] = None           # uint32 [n_masks, ceil(V / 32)]: the distinct static allow masks, or None (unconstrained)
     step_mask: Tuple[int, ...] = ()              # per step: the row of `masks` in force, -1 for none
+    bias: Tuple[Tuple[int, float], ...] = ()     # sequence_bias, normalised: (id, value) sorted by id, single-token keys only
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
 
     @property
     def constrained(self) -> bool:
         return self.masks is not None
 
     @property
+    def count_penalties(self) -> bool:
+        """Does the adjustment depend on what a row has generated (a vt_bias_rows launch before every pick)?"""
+        return float(self.presence_penalty) != 0.0 or float(self.frequency_penalty) != 0.0
+
+    @property
+    def adjusted(self) -> bool:
+        return bool(self.bias) or self.count_penalties
+
+    @property
     def per_row(self) -> bool:
         """Does a step need the per-row sampler (vt_sample_rows) instead of vt_argmax / vt_sample_top_p?"""
-        return float(self.repetition_penalty) != 1.0 or bool(self.return_logprobs) or self.constrained or self.ngram > 0
+        return (float(self.repetition_penalty) != 1.0 or bool(self.return_logprobs) or self.constrained or self.ngram > 0
+                or self.adjusted)
 
 
 def static_mask_schedule(V: int, steps: int, banned_always, banned_begin, min_new: int, eos, allowed_ids):
@@ -83,10 +98,12 @@ def static_mask_schedule(V: int, steps: int, banned_always, banned_begin, min_ne
 def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top_p, top_k, max_new_tokens, max_length, stopping_criteria,
                           eos_token_id, pad_token_id, num_beams, seed, return_logits, padded_batch, repetition_penalty, return_logprobs,
                           suppress_tokens, begin_suppress_tokens, min_new_tokens, bad_words_ids, allowed_token_ids, num_return_sequences,
-                          length_penalty, early_stopping, no_repeat_ngram_size) -> GenerateArgs:
+                          length_penalty, early_stopping, no_repeat_ngram_size, sequence_bias=None, presence_penalty=0.0,
+                          frequency_penalty=0.0) -> GenerateArgs:
     """generate()'s keyword arguments as a GenerateArgs. Raises, in this order and before any device work: the argument errors of
     num_beams / no_repeat_ngram_size, everything a beam call refuses, the padded_batch refusals that depend on arguments alone, the
-    sampling values, the constraint arguments, a step the constraints leave no token for, constraints with padded_batch. The sample seed
+    sampling values, the constraint arguments, a step the constraints leave no token for, constraints with padded_batch, the values of
+    sequence_bias / presence_penalty / frequency_penalty, those three with padded_batch. The sample seed
     is drawn from torch's global CPU generator (so torch.manual_seed makes sampling reproducible, as with GenerationMixin.sample) and
     only when sampling without `seed`, after the beam refusals: greedy and refused calls leave the RNG state alone."""
     num_beams = int(num_beams)
@@ -112,7 +129,9 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
         pad=pad_token_id if pad_token_id is not None else (config.pad_token_id if config.pad_token_id is not None else 0),
         max_new_tokens=max_new_tokens, ngram=int(no_repeat_ngram_size),
         given=tuple(f"{name}=..." for name, value in optional if value)
-        + tuple(f"{name}=True" for name, value in (("return_logits", return_logits), ("return_logprobs", return_logprobs)) if value))
+        + tuple(f"{name}=True" for name, value in (("return_logits", return_logits), ("return_logprobs", return_logprobs)) if value)
+        + tuple(f"{name}=..." for name, value in (("sequence_bias", sequence_bias), ("presence_penalty", presence_penalty),
+                                                  ("frequency_penalty", frequency_penalty)) if value))
     if num_beams > 1:
         check_beam_arguments(a, int(config.vocab_size))
     elif a.num_return_sequences != 1:
@@ -144,8 +163,19 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
     if masks is not None and padded_batch:
         raise NotImplementedError("generate(padded_batch=True) does not take suppress_tokens / begin_suppress_tokens / min_new_tokens / "
                                   "bad_words_ids / allowed_token_ids; use the default packed batch")
-    return dataclasses.replace(a, sample_seed=sample_seed, banned_always=tuple(banned_always), banned_begin=tuple(banned_begin),
-                               min_new=min_new, allowed_ids=allowed_ids, masks=masks, step_mask=step_mask)
+    V = int(config.vocab_size)
+    bias = normalise_bias(sequence_bias, V, "generate(sequence_bias=...)", tuple_keys=True)
+    check_penalties(presence_penalty, frequency_penalty, "generate")
+    a = dataclasses.replace(a, sample_seed=sample_seed, banned_always=tuple(banned_always), banned_begin=tuple(banned_begin),
+                            min_new=min_new, allowed_ids=allowed_ids, masks=masks, step_mask=step_mask, bias=bias,
+                            presence_penalty=float(presence_penalty), frequency_penalty=float(frequency_penalty))
+    if a.adjusted and padded_batch:
+        raise NotImplementedError("generate(padded_batch=True) does not take sequence_bias / presence_penalty / frequency_penalty; use "
+                                  "the default packed batch")
+    if a.adjusted and V > BIAS_ROWS_MAX_V:
+        raise NotImplementedError(f"generate(sequence_bias / presence_penalty / frequency_penalty): vocab_size={V} is beyond vt_bias_rows' "
+                                  f"{BIAS_ROWS_MAX_V}")
+    return a
 
 
 def check_beam_arguments(a: GenerateArgs, V: int) -> None:
@@ -213,8 +243,13 @@ class StepPicker:
       - the penalty history (the non-negative prompt ids, then the picks) -- with a repetition penalty;
       - with no_repeat_ngram_size: the ban history (the ids where attention_mask is 1, sentinels included, then the picks), the [steps, B]
         vt_ban_row array (history_len = prompt ids + step, base = the step's static mask or NULL) and the B working masks vt_ban_rows
-        writes, which are what the sampler's allow pointers name then -- the same B addresses at every step.
-    Both histories grow on the device. The device-built masks are never read back."""
+        writes, which are what the sampler's allow pointers name then -- the same B addresses at every step;
+      - with sequence_bias / presence_penalty / frequency_penalty: B adjustment buffers [V][2] and their B addresses (the
+        sampler's adjust pointers, the same at every step), the bias ids / values, and the ids every row has GENERATED -- the tail of
+        the penalty history where there is one, else a history of its own. With a penalty != 0 the [steps, B] vt_bias_row array
+        (history_len = step) is uploaded too and every pick is preceded by ONE ops.bias_rows launch; with sequence_bias alone the
+        buffers never change and are built by ONE launch here, before the prefill.
+    The histories grow on the device. The device-built masks and adjustments are never read back."""
 
     def __init__(self, a: GenerateArgs, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], V: int):
         self.a = a
@@ -246,10 +281,31 @@ class StepPicker:
             self.ban_rows = pack_ban_rows([(h.row_ptr(b), h.lens[b] + st, step_base[st], work_ptr[b], a.ngram, 0, 0, 0)
                                            for st in range(steps) for b in range(B)], dev).view(steps, B, BAN_ROW_BYTES)
             self.ban_ptrs = torch.tensor(work_ptr, dtype=torch.int64).to(dev)
+        self.adj_ptrs = self.bias_rows = self.gen_hist = None
+        if a.adjusted and steps > 0:
+            self.adj = adj = torch.zeros((B, self.V, 2), dtype=torch.float32, device=dev)
+            adj_ptr = [adj.data_ptr() + 4 * b * adj.stride(0) for b in range(B)]
+            self.adj_ptrs = torch.tensor(adj_ptr, dtype=torch.int64).to(dev)
+            self.bias_ids = torch.tensor([t for t, _ in a.bias], dtype=torch.int32).to(dev)
+            self.bias_vals = torch.tensor([v for _, v in a.bias], dtype=torch.float32).to(dev)
+            ids_ptr, vals_ptr = (self.bias_ids.data_ptr(), self.bias_vals.data_ptr()) if a.bias else (0, 0)
+            if not a.count_penalties:            # the rows never change: one launch, here
+                ops.bias_rows(pack_bias_rows([(0, 0, ids_ptr, vals_ptr, len(a.bias), adj_ptr[b], 0.0, 0.0) for b in range(B)], dev), B, self.V)
+            else:
+                if self.hist is not None:        # the generated ids are the tail of the penalty history
+                    gen_ptr = [self.hist.row_ptr(b) + 4 * self.hist.lens[b] for b in range(B)]
+                else:
+                    self.gen_hist = _History(input_ids[:, :0], steps)
+                    gen_ptr = [self.gen_hist.row_ptr(b) for b in range(B)]
+                self.bias_rows = pack_bias_rows(
+                    [(gen_ptr[b] if st else 0, st, ids_ptr, vals_ptr, len(a.bias), adj_ptr[b], a.presence_penalty, a.frequency_penalty)
+                     for st in range(steps) for b in range(B)], dev).view(steps, B, BIAS_ROW_BYTES)
 
     def check_width(self, logits: torch.Tensor) -> None:
         if self.mode == "rows" and (self.a.constrained or self.a.ngram) and logits.shape[1] != self.V:
             raise RuntimeError(f"generate: the allow masks were built for V = {self.V}, the logits have {logits.shape[1]} columns")
+        if self.mode == "rows" and self.a.adjusted and logits.shape[1] != self.V:
+            raise RuntimeError(f"generate: the logit adjustments were built for V = {self.V}, the logits have {logits.shape[1]} columns")
 
     def pick(self, step: int, logits: torch.Tensor) -> torch.Tensor:
         a = self.a
@@ -262,7 +318,9 @@ class StepPicker:
             ptrs = self.ban_ptrs
         else:
             ptrs = None if self.allow_ptrs is None else self.allow_ptrs[step]
-        nxt = ops.sample_rows(logits, self.rows[step], return_logprob=bool(a.return_logprobs), _allow_ptrs=ptrs)
+        if self.bias_rows is not None:           # the rows' adjustments for this pick, from what they have generated: one launch
+            ops.bias_rows(self.bias_rows[step], self.B, self.V)
+        nxt = ops.sample_rows(logits, self.rows[step], return_logprob=bool(a.return_logprobs), _allow_ptrs=ptrs, _adjust_ptrs=self.adj_ptrs)
         if a.return_logprobs:
             nxt, lp = nxt
             self._lp.append(lp)
@@ -270,6 +328,8 @@ class StepPicker:
             self.hist.append(nxt)
         if self.ban_rows is not None:
             self.ban_hist.append(nxt)
+        if self.gen_hist is not None:
+            self.gen_hist.append(nxt)
         return nxt
 
     def logprobs(self, n: int) -> torch.Tensor:

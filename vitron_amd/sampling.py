@@ -10,6 +10,11 @@ tokens generated so far into the mask of the next pick.
 History-dependent bans: `no_repeat_ngram_size` and multi-token `bad_words` forbid ids that depend on what the request has
 seen so far, so their mask is built on the DEVICE (struct vt_ban_row, `pack_ban_rows`, ops.ban_rows) from a device-resident history;
 `history_bans` is the host statement of that contract.
+
+Additive adjustments: a logit bias and the presence / frequency penalties add to a logit instead of forbidding it. A
+row's adjustment is V pairs (pre, post) of fp32 built on the DEVICE (struct vt_bias_row, `pack_bias_rows`, ops.bias_rows) and read by
+vt_sample_rows_adj; `LogitAdjust` is what a caller hands to `ServingEngine.submit(..., adjust=)`, `logit_adjust` the host statement of
+the contract.
 """
 from __future__ import annotations
 
@@ -38,6 +43,15 @@ BAN_ROW_DTYPE = np.dtype({
     "itemsize": 48,
 })
 BAN_ROW_BYTES = BAN_ROW_DTYPE.itemsize
+# struct vt_bias_row: the offsets are part of the ABI (tests/test_bias_ref_host.py checks them against the header's table)
+BIAS_ROW_DTYPE = np.dtype({
+    "names": ["history", "bias_ids", "bias_vals", "out", "history_len", "n_bias", "presence", "frequency"],
+    "formats": ["<u8", "<u8", "<u8", "<u8", "<i4", "<i4", "<f4", "<f4"],
+    "offsets": [0, 8, 16, 24, 32, 36, 40, 44],
+    "itemsize": 48,
+})
+BIAS_ROW_BYTES = BIAS_ROW_DTYPE.itemsize
+BIAS_ROWS_MAX_V = 65536            # VT_BIAS_ROWS_MAX_V
 
 
 def check_sampling_values(temperature, top_p, top_k, repetition_penalty, what: str = "sampling") -> None:
@@ -338,3 +352,115 @@ def pack_ban_rows(rows: Sequence[tuple], device):
     import torch
     arr = ban_rows_array(rows)
     return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), BAN_ROW_BYTES)).to(device)
+
+
+# ---- additive adjustments: struct vt_bias_row and the host statement of vt_bias_rows' contract --------------------------------------
+def _finite(x) -> bool:
+    return isinstance(x, numbers.Real) and not isinstance(x, bool) and math.isfinite(x)
+
+
+def normalise_bias(bias, V: Optional[int], what: str, tuple_keys: bool) -> Tuple[Tuple[int, float], ...]:
+    """((id, value), ...) sorted by id from a mapping. tuple_keys: transformers' sequence_bias form, keys are tuples of ids (a bare int
+    is a one-token key) and a key of more than one token is a NotImplementedError; otherwise keys are ids (logit_bias). ValueError: a key
+    that is no id, an id outside [0, V) (when V is given), a value that is not a finite number, the same id twice."""
+    if bias is None:
+        return ()
+    if not hasattr(bias, "items"):
+        raise ValueError(f"{what} must be a mapping, got {bias!r}")
+    out = {}
+    for key, value in bias.items():
+        if tuple_keys and isinstance(key, (tuple, list)):
+            if len(key) == 0:
+                raise ValueError(f"{what}: an empty key")
+            if len(key) > 1:
+                raise NotImplementedError(f"{what}: the multi-token key {tuple(key)!r} is not implemented (single-token keys only: its "
+                                          "bias depends on the history)")
+            key = key[0]
+        if not isinstance(key, numbers.Integral) or isinstance(key, bool):
+            raise ValueError(f"{what}: the key {key!r} is not a token id")
+        t = int(key)
+        if t < 0 or (V is not None and t >= int(V)):
+            raise ValueError(f"{what}: the id {t} is outside [0, {'vocab_size' if V is None else int(V)})")
+        if not _finite(value):
+            raise ValueError(f"{what}: the bias of id {t} must be a finite number, got {value!r}")
+        if t in out:
+            raise ValueError(f"{what}: the id {t} is given twice")
+        out[t] = float(value)
+    return tuple(sorted(out.items()))
+
+
+def check_penalties(presence, frequency, what: str) -> None:
+    if not _finite(presence):
+        raise ValueError(f"{what}: presence_penalty must be a finite number, got {presence!r}")
+    if not _finite(frequency):
+        raise ValueError(f"{what}: frequency_penalty must be a finite number, got {frequency!r}")
+
+
+@dataclass(frozen=True)
+class LogitAdjust:
+    """What ONE request adds to its logits (ServingEngine.submit(..., adjust=)): logit_bias maps a token id to a finite float added
+    BEFORE the repetition penalty (OpenAI's / vLLM's logit_bias, transformers' single-token sequence_bias); presence_penalty and
+    frequency_penalty take presence + frequency * count off every token the request has GENERATED so far, AFTER the repetition penalty
+    (any finite float; OpenAI's [-2, 2] is not enforced). `bias` is the normalised form: ((id, value), ...) sorted by id."""
+    logit_bias: Optional[Dict[int, float]] = None
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+
+    def __post_init__(self):
+        object.__setattr__(self, "bias", normalise_bias(self.logit_bias, None, "LogitAdjust: logit_bias", tuple_keys=False))
+        check_penalties(self.presence_penalty, self.frequency_penalty, "LogitAdjust")
+
+    def __hash__(self):
+        return hash((self.bias, float(self.presence_penalty), float(self.frequency_penalty)))
+
+    @property
+    def penalties(self) -> bool:
+        """Does the adjustment depend on what the request has generated (a rebuild before every pick)?"""
+        return float(self.presence_penalty) != 0.0 or float(self.frequency_penalty) != 0.0
+
+    @property
+    def active(self) -> bool:
+        return bool(self.bias) or self.penalties
+
+    def check_vocab(self, V: int) -> None:
+        for t, _ in self.bias:
+            if t >= int(V):
+                raise ValueError(f"LogitAdjust: logit_bias: the id {t} is outside [0, {int(V)})")
+
+
+def logit_adjust(V: int, generated: Sequence[int], bias=None, presence: float = 0.0, frequency: float = 0.0):
+    """(pre, post), fp32 [V] each: what vt_bias_rows writes for a row that has generated `generated`, with the logit bias `bias` (a mapping
+    id -> value or pairs (id, value), distinct ids) and the two penalties (include/vitron_hip.h):
+    pre[t] = the bias of t, else 0; post[t] = 0 where t was not generated, else -(frequency * count(t) + presence) with the product and
+    the sum rounded to fp32 separately. Ids outside [0, V) are skipped; only the last 65535 generated ids are counted."""
+    V = int(V)
+    pre = np.zeros((V,), dtype=np.float32)
+    for t, v in (bias.items() if hasattr(bias, "items") else (bias or ())):
+        if 0 <= int(t) < V:
+            pre[int(t)] = np.float32(v)
+    g = np.asarray(list(generated), dtype=np.int64).reshape(-1)[-65535:]
+    g = g[(g >= 0) & (g < V)]
+    c = np.bincount(g, minlength=V).astype(np.float32)
+    prod = (np.float32(frequency) * c).astype(np.float32)
+    post = np.where(c > 0, -(prod + np.float32(presence)).astype(np.float32), np.float32(0.0)).astype(np.float32)
+    return pre, post
+
+
+def bias_rows_array(rows: Sequence[tuple]) -> np.ndarray:
+    """Host array of vt_bias_row from one tuple per row:
+        (history_ptr, history_len, bias_ids_ptr, bias_vals_ptr, n_bias, out_ptr, presence, frequency)
+    The pointers are DEVICE addresses (tensor.data_ptr(), 0 for NULL) whose owners the caller keeps alive until the launch has run."""
+    arr = np.zeros((len(rows),), dtype=BIAS_ROW_DTYPE)
+    for i, (hist_ptr, hist_len, ids_ptr, vals_ptr, n_bias, out_ptr, presence, frequency) in enumerate(rows):
+        if min(int(hist_ptr), int(ids_ptr), int(vals_ptr), int(out_ptr)) < 0 or (int(hist_len) > 0 and not hist_ptr) \
+                or (int(n_bias) > 0 and not (ids_ptr and vals_ptr)):
+            raise ValueError(f"bias row {i}: a negative address, or a length without its buffer")
+        arr[i] = (int(hist_ptr), int(ids_ptr), int(vals_ptr), int(out_ptr), int(hist_len), int(n_bias), float(presence), float(frequency))
+    return arr
+
+
+def pack_bias_rows(rows: Sequence[tuple], device):
+    """Device form of `bias_rows_array(rows)`: a uint8 tensor [len(rows), 48] for ops.bias_rows."""
+    import torch
+    arr = bias_rows_array(rows)
+    return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), BIAS_ROW_BYTES)).to(device)

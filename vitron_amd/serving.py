@@ -36,7 +36,8 @@ import torch
 from . import ops
 from .engine import PagedKVCache, SequenceState, llama_forward, pair_lo, parse_kv_cache_dtype
 from .picker import device_history
-from .sampling import SamplingParams, check_constraints, flatten_ban_seqs, mask_words, pack_ban_rows, pack_sample_rows, step_allow_mask
+from .sampling import (BIAS_ROWS_MAX_V, LogitAdjust, SamplingParams, check_constraints, flatten_ban_seqs, mask_words, pack_ban_rows,
+                       pack_bias_rows, pack_sample_rows, step_allow_mask)
 
 
 @dataclass
@@ -69,6 +70,12 @@ class _Request:
     mask_uploads: int = 0                            # host -> device mask copies this request has cost
     ban_mask: Optional[torch.Tensor] = None          # device int32 [ceil(V / 32)]: the working mask vt_ban_rows writes before every pick
     ban_seqs: Optional[torch.Tensor] = None          # device int32: sampling.bad_words flattened ({L, ids} repeated), uploaded once
+    adjust: Optional[LogitAdjust] = None             # additive adjustment; None: none. What follows is released with hist
+    adj_buf: Optional[torch.Tensor] = None           # device fp32 [V, 2]: the (pre, post) pairs vt_bias_rows writes, vt_sample_rows_adj reads
+    adj_ids: Optional[torch.Tensor] = None           # device int32 / fp32: the logit bias, uploaded once
+    adj_vals: Optional[torch.Tensor] = None
+    gen: Optional[torch.Tensor] = None               # device int32 [max_new_tokens]: the tokens fed back (what the penalties count over)
+    gen_len: int = 0
 
 
 class ServingEngine:
@@ -100,11 +107,15 @@ class ServingEngine:
 
     # ---- queue ----------------------------------------------------------------------------------------------------------
     def submit(self, input_ids: torch.Tensor, images=None, regions=None, max_new_tokens: int = 256,
-               eos_token_id=None, sampling: Optional[SamplingParams] = None) -> int:
+               eos_token_id=None, sampling: Optional[SamplingParams] = None, adjust: Optional[LogitAdjust] = None) -> int:
         """sampling: this request's own SamplingParams. It then draws with (seed = sampling.seed, counter = tokens it has generated so
         far, stream = 0) -- what generate() uses for a batch of one -- so its tokens equal
         generate(do_sample=temperature > 0, temperature, top_p, top_k, seed, repetition_penalty) for the request alone, whatever else is in
-        the batch. Without it the request follows the engine-wide setting exactly as before."""
+        the batch. Without it the request follows the engine-wide setting exactly as before.
+        adjust: this request's own LogitAdjust: a logit bias added before the repetition penalty, presence / frequency
+        penalties over the tokens it has generated after it. Its tokens equal generate(sequence_bias=..., presence_penalty=...,
+        frequency_penalty=...) for the request alone, whatever else is in the batch; a request with `adjust` and without `sampling` keeps
+        its legacy row parameters."""
         ids = input_ids if input_ids.dim() == 2 else input_ids.unsqueeze(0)
         if ids.shape[0] != 1:
             raise ValueError("submit() takes one sequence per request")
@@ -116,7 +127,17 @@ class ServingEngine:
         eos_set = frozenset(eos) if isinstance(eos, (list, tuple, set, frozenset)) else (frozenset([eos]) if eos is not None else frozenset())
         if sampling is not None and sampling.constrained:
             check_constraints(sampling, eos_set, int(self.model.config.vocab_size))     # ValueError: nothing is queued
-        r = _Request(self._next_id, ids.to(self.model.device), images, regions, int(max_new_tokens), eos_set, sampling=sampling)
+        if adjust is not None:                   # rejected here too
+            if not isinstance(adjust, LogitAdjust):
+                raise TypeError(f"submit(adjust=...) takes a LogitAdjust, got {type(adjust).__name__}")
+            V = int(self.model.config.vocab_size)
+            adjust.check_vocab(V)
+            if adjust.active and V > BIAS_ROWS_MAX_V:
+                raise ValueError(f"submit(adjust=...): vocab_size={V} is beyond vt_bias_rows' {BIAS_ROWS_MAX_V}")
+            if not adjust.active:
+                adjust = None
+        r = _Request(self._next_id, ids.to(self.model.device), images, regions, int(max_new_tokens), eos_set, sampling=sampling,
+                     adjust=adjust)
         self._next_id += 1
         self.waiting.append(r)
         return r.rid
@@ -152,6 +173,7 @@ class ServingEngine:
     def _drop_masks(r: _Request) -> None:
         r.allow_dev, r.allow_host, r.allow_cur, r.allow_at = {}, {}, None, -1
         r.ban_mask = r.ban_seqs = None
+        r.adj_buf = r.adj_ids = r.adj_vals = r.gen = None
 
     def _prepare_allow(self, r: _Request) -> None:
         """The allow mask of r's next pick: a pure host function of (r.sampling, r.tokens, r.eos) -- the host has read back
@@ -186,8 +208,12 @@ class ServingEngine:
         vt_ban_rows launch in front of the sampler turns (the mask above as base, or NULL; the history; the rules) into the working masks
         of all such rows, and those rows' allow pointers name their working masks. Nothing is uploaded per step but the 48-byte rows, and
         the masks are never read back: a row they leave nothing for returns what vt_sample_rows_allow defines for it instead of failing.
-        While no active request carries such a ban the launches are exactly the ones above."""
-        if reqs is None or all(r.sampling is None for r in reqs):
+        While no active request carries such a ban the launches are exactly the ones above.
+        A request with `adjust` owns a [V][2] adjustment, its bias and its generated tokens on the device: ONE
+        vt_bias_rows launch serves every row that needs a rebuild (a row with penalties at every pick, a bias-only row at its first pick
+        only), the launch is vt_sample_rows_adj and the row's adjust pointer names its buffer; all other rows pass NULL. While no
+        active request carries `adjust` the launches are exactly the ones above."""
+        if reqs is None or all(r.sampling is None and r.adjust is None for r in reqs):
             if self.do_sample:
                 return ops.sample_top_p(logits, self.temperature, self.top_p, self.seed, self._step)
             return ops.argmax(logits)
@@ -228,7 +254,32 @@ class ServingEngine:
                 allow = [r.ban_mask if (r.sampling is not None and r.sampling.device_bans) else a for r, a in zip(reqs, allow)]
             if all(a is None for a in allow):
                 allow = None
-        res = ops.sample_rows(logits, pack_sample_rows(rows, logits.device), return_logprob=want_lp, allow=allow)
+        adj = None
+        if any(r.adjust is not None for r in reqs):
+            V, dev = int(logits.shape[1]), logits.device
+            bias_rows = []
+            for r in reqs:
+                if r.adjust is None:
+                    continue
+                first = r.adj_buf is None
+                if first:
+                    r.adj_buf = torch.zeros((V, 2), dtype=torch.float32, device=dev)
+                    if r.adjust.bias:
+                        r.adj_ids = torch.tensor([t for t, _ in r.adjust.bias], dtype=torch.int32).to(dev)
+                        r.adj_vals = torch.tensor([v for _, v in r.adjust.bias], dtype=torch.float32).to(dev)
+                    if r.adjust.penalties:
+                        r.gen = torch.zeros((max(r.max_new_tokens, 1),), dtype=torch.int32, device=dev)
+                elif r.adj_buf.numel() != 2 * V:                  # (the buffer is read for 2 * V floats)
+                    raise ValueError(f"request {r.rid}: its adjustment was built for V = {r.adj_buf.numel() // 2}, the logits have {V} columns")
+                if first or r.adjust.penalties:
+                    n_gen = min(r.gen_len, int(r.gen.numel())) if r.gen is not None else 0
+                    bias_rows.append((r.gen.data_ptr() if n_gen else 0, n_gen, 0 if r.adj_ids is None else r.adj_ids.data_ptr(),
+                                      0 if r.adj_vals is None else r.adj_vals.data_ptr(), len(r.adjust.bias), r.adj_buf.data_ptr(),
+                                      r.adjust.presence_penalty, r.adjust.frequency_penalty))
+            if bias_rows:
+                ops.bias_rows(pack_bias_rows(bias_rows, dev), len(bias_rows), V)
+            adj = [r.adj_buf for r in reqs]
+        res = ops.sample_rows(logits, pack_sample_rows(rows, logits.device), return_logprob=want_lp, allow=allow, adjust=adj)
         ids, lp = res if want_lp else (res, None)
         for i, r in enumerate(reqs):
             if r.sampling is not None and r.sampling.logprobs:
@@ -420,6 +471,9 @@ class ServingEngine:
                 if r.hist is not None:
                     r.hist[r.hist_len:r.hist_len + 1].copy_(r.last)
                     r.hist_len += 1
+                if r.gen is not None and r.gen_len < int(r.gen.numel()):
+                    r.gen[r.gen_len:r.gen_len + 1].copy_(r.last)
+                    r.gen_len += 1
             nxt = self._pick(logits, self.active)
             for i, r in enumerate(self.active):
                 r.last = nxt[i:i + 1]
