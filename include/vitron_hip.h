@@ -94,6 +94,8 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
 /* 114 also carries vt_ban_rows and struct vt_ban_row WITHOUT a bump: one new symbol and one new struct; the samplers do not change. */
 /* 114 also carries vt_bias_rows, struct vt_bias_row and vt_sample_rows_adj WITHOUT a bump: two new symbols and one new struct; struct
  * vt_sample_row, vt_sample_rows and vt_sample_rows_allow do not change. */
+/* 114 also carries the tower unit entry points vt_vit_embed, vt_region_pool and vt_attn_temporal_f32 WITHOUT a bump: three new symbols
+ * that forward to launches vt_vit_forward and vt_region_forward already make; no struct and no existing signature changes. */
 #define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
@@ -291,6 +293,16 @@ int vt_attn_tail_desc(const int* seq_desc, int nseq, const int* logit_rows, int 
 /* temporal attention of the video tower: qkv bf16 [B*T*N][3*heads*64] (row (b*T+t)*N+n, q pre-scaled) ->
  * out bf16 [B*T*N][heads*64]; attends over the T frames at each (b, n). Reference modeling_video.py:105-127. */
 int vt_attn_temporal(const uint16_t* qkv, uint16_t* out, int B, int T, int N, int heads, void* stream);
+/* The same attention on fp32 q | k | v (the pair projection of vt_vit_model.precise >= 2; vt_vit_forward's own launch, exported for unit
+ * tests): qkv fp32 [B*T*N][ld], ld >= 3*heads*64, columns q | k | v; everything in fp32; the output as an operand pair: out = the
+ * 16-bit rounding of o, out_lo = the 16-bit rounding of o - out, both [B*T*N][heads*64]. T in 1..8. */
+int vt_attn_temporal_f32(const float* qkv, int ld, uint16_t* out, uint16_t* out_lo, int B, int T, int N, int heads, void* stream);
+
+/* CLIPVisionEmbeddings assembly + pre_layrnorm (vt_vit_forward's own launch, exported for unit tests): with R = G2 + 1 rows per frame,
+ * x[f*R] = LN(cls + pos[0]) and x[f*R + 1 + p] = LN(patch_out[f*G2 + p] + pos[1 + p]), LN over D with gamma g, beta b and eps. All fp32:
+ * patch_out [F*G2][D], cls [D], pos [R][D], g / b [D], x [F*R][D]. D % 4 == 0, D <= 4096; rows 16-byte aligned. */
+int vt_vit_embed(const float* patch_out, const float* cls, const float* pos, const float* g, const float* b, float* x, int F, int G2,
+                 int D, float eps, void* stream);
 
 /* CLIPVisionEmbeddings patch gather: pixels ([F][3][H][W] or, video_layout=1, [B][3][T][H][W]; bf16 or fp32) ->
  * patches bf16 [B*T*(H/P)*(W/P)][k_pad], K order (c,py,px), zero padded. */
@@ -571,6 +583,16 @@ size_t vt_region_workspace_bytes(int B, int in_dim, int out_dim);
 int vt_region_forward(const vt_region_weights* w, const uint16_t* feats, const int* slices, const float* coords,
                       int B, int G, int image_size, uint16_t* out, int* cell_mask, int* cell_count, void* workspace,
                       size_t workspace_bytes, void* stream);
+/* The first launch of vt_region_forward on its own (exported for unit tests; any B >= 1: the 16-box limit belongs to the GEMMs that
+ * follow): feats / slices / coords as above with D = in_dim (D % 64 == 0), G <= 64, image_size >= G.
+ *   pooled     16-bit [B][D]       masked mean of the box's cells, sum_cells x * fl32(1 / count) in fp32; an empty box gives zeros
+ *   cell_mask  int32 [B][G*G], cell_count int32 [B]: optional (may be NULL), bit-exact
+ *   loc_out    16-bit [B][ld_loc]  optional: columns 0 .. loc_n - 1 of row b = relu(coords[b] . loc_w0[n][0..3] + loc_b0[n]) with
+ *                                  loc_w0 16-bit [loc_n][8] and loc_b0 fp32 [loc_n]; the D / 64 channel slabs of a box share the
+ *                                  loc_n outputs, ceil(loc_n / slabs) each. NULL skips the layer (coords / loc_w0 / loc_b0 unused). */
+int vt_region_pool(const uint16_t* feats, const int* slices, int B, int G, int image_size, int D, uint16_t* pooled, int* cell_mask,
+                   int* cell_count, const float* coords, const uint16_t* loc_w0, const float* loc_b0, int loc_n, uint16_t* loc_out,
+                   int ld_loc, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * LanguageBind ViT tower (CLIP ViT + optional per-layer temporal attention)

@@ -411,6 +411,24 @@ def test_cabi_argument_validation_without_a_gpu():
     bad(lib.vt_decode_feed(P, 64, 100, None, P, None, 0, 0, P, P, P, P, 2, None), "null")
     bad(lib.vt_flash_attn(P, 384, P, P, P, P, 1, 16, P, 128, 2, 48, 0, 1.0, None))                     # head_dim 48
     bad(lib.vt_attn_temporal(P, P, 1, 8, 16, 0, None))
+    # the tower unit entry points: the launchers' own checks, reached before anything is launched
+    bad(lib.vt_attn_temporal_f32(None, 200, P, P, 1, 4, 5, 1, None), "vt_attn_temporal_f32", "null")
+    bad(lib.vt_attn_temporal_f32(P, 200, P, None, 1, 4, 5, 1, None), "vt_attn_temporal_f32", "null")        # the pair needs both halves
+    bad(lib.vt_attn_temporal_f32(P, 200, P, P, 1, 9, 5, 1, None), "vt_attn_temporal_f32", "T=9")
+    bad(lib.vt_attn_temporal_f32(P, 191, P, P, 1, 4, 5, 1, None), "vt_attn_temporal_f32", "ld 191")          # ld < 3 D = 192
+    bad(lib.vt_attn_temporal(P, P, 1, 9, 5, 1, None), "T=9")
+    bad(lib.vt_vit_embed(P, P, P, P, P, None, 3, 5, 64, 1e-5, None), "vt_vit_embed", "null")
+    bad(lib.vt_vit_embed(P, None, P, P, P, P, 3, 5, 64, 1e-5, None), "vt_vit_embed", "null")
+    bad(lib.vt_vit_embed(P, P, P, P, P, P, 3, 5, 66, 1e-5, None), "vt_vit_embed", "D=66")                    # D % 4
+    bad(lib.vt_vit_embed(P, P, P, P, P, P, 3, 5, 4100, 1e-5, None), "vt_vit_embed", "D=4100")                # above the widest instantiation
+    bad(lib.vt_region_pool(None, P, 4, 24, 224, 128, P, None, None, None, None, None, 0, None, 0, None), "vt_region_pool", "null")
+    bad(lib.vt_region_pool(P, P, 4, 24, 224, 128, None, None, None, None, None, None, 0, None, 0, None), "vt_region_pool", "null")
+    bad(lib.vt_region_pool(P, P, 4, 65, 224, 128, P, None, None, None, None, None, 0, None, 0, None), "vt_region_pool", "G=65")
+    bad(lib.vt_region_pool(P, P, 4, 24, 224, 96, P, None, None, None, None, None, 0, None, 0, None), "vt_region_pool", "D=96")   # D % 64
+    bad(lib.vt_region_pool(P, P, 4, 24, 16, 128, P, None, None, None, None, None, 0, None, 0, None), "vt_region_pool", "image=16")   # canvas below the grid
+    bad(lib.vt_region_pool(P, P, 0, 24, 224, 128, P, None, None, None, None, None, 0, None, 0, None), "vt_region_pool", "B=0")
+    bad(lib.vt_region_pool(P, P, 4, 24, 224, 128, P, None, None, None, None, None, 8, P, 16, None), "vt_region_pool", "location-encoder")   # loc_out without its inputs
+    bad(lib.vt_region_pool(P, P, 4, 24, 224, 128, P, None, None, P, P, P, 0, P, 16, None), "vt_region_pool", "location-encoder")           # ... or without a width
     bad(lib.vt_sample_top_p(P, 2, 100, 100, 0.0, 0, 0.9, 0, 0, P, None, None))                         # temperature 0
     bad(lib.vt_sample_top_p(P, 2, 100, 100, 1.0, -3, 0.9, 0, 0, P, None, None), "top_k")
     rw = _lib.VtRegionWeights()

@@ -100,6 +100,9 @@ SIGNATURES = {
     "vt_kv_tiles": (_i, [vp, _i, _i, _i, _i, vp, vp, vp, vp, _i, _i, _i, _i, vp, vp, vp, vp]),
     "vt_attn_tail_desc": (_i, [vp, _i, vp, _i, vp, vp]),
     "vt_attn_temporal": (_i, [vp, vp, _i, _i, _i, _i, vp]),
+    "vt_attn_temporal_f32": (_i, [vp, _i, vp, vp, _i, _i, _i, _i, vp]),
+    "vt_vit_embed": (_i, [vp, vp, vp, vp, vp, vp, _i, _i, _i, _f, vp]),
+    "vt_region_pool": (_i, [vp, vp, _i, _i, _i, _i, vp, vp, vp, vp, vp, vp, _i, vp, _i, vp]),
     "vt_im2col": (_i, [vp, _i, vp, _i, _i, _i, _i, _i, _i, _i, vp]),
     "vt_preprocess": (_i, [vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _i, vp, _i, C.c_long,
                            C.c_long, vp]),

@@ -411,6 +411,22 @@ int vt_attn_temporal(const uint16_t* qkv, uint16_t* out, int B, int T, int N, in
   return vt_attn_temporal_launch(qkv, out, B, T, N, heads, S(stream));
 }
 
+int vt_attn_temporal_f32(const float* qkv, int ld, uint16_t* out, uint16_t* out_lo, int B, int T, int N, int heads, void* stream) {
+  return vt_attn_temporal_f32_launch(qkv, ld, out, out_lo, B, T, N, heads, S(stream));
+}
+
+int vt_vit_embed(const float* patch_out, const float* cls, const float* pos, const float* g, const float* b, float* x, int F, int G2,
+                 int D, float eps, void* stream) {
+  return vt_vit_embed_launch(patch_out, cls, pos, g, b, x, F, G2, D, eps, S(stream));
+}
+
+int vt_region_pool(const uint16_t* feats, const int* slices, int B, int G, int image_size, int D, uint16_t* pooled, int* cell_mask,
+                   int* cell_count, const float* coords, const uint16_t* loc_w0, const float* loc_b0, int loc_n, uint16_t* loc_out,
+                   int ld_loc, void* stream) {
+  return vt_region_pool_launch(feats, slices, B, G, image_size, D, pooled, cell_mask, cell_count, coords, loc_w0, loc_b0, loc_n, loc_out,
+                               ld_loc, S(stream));
+}
+
 int vt_im2col(const void* pixels, int pix_dtype, uint16_t* patches, int B, int T, int H, int W, int P, int k_pad,
               int video_layout, void* stream) {
   return vt_im2col_launch(pixels, pix_dtype, patches, B, T, H, W, P, k_pad, video_layout, S(stream));

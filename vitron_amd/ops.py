@@ -416,12 +416,103 @@ def attn_decode_fused_kv8(qkv: torch.Tensor, q_col0: int, k_col0: int, v_col0: i
     return out
 
 
-def attn_temporal(qkv: torch.Tensor, B: int, T: int, N: int, heads: int) -> torch.Tensor:
+def attn_temporal(qkv: torch.Tensor, B: int, T: int, N: int, heads: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     lib, dt = _op16(qkv, "attn_temporal.qkv")
     _chk(qkv, dt, "attn_temporal.qkv")
-    out = torch.empty((qkv.shape[0], heads * 64), device=qkv.device, dtype=dt)
+    if out is None:
+        out = torch.empty((qkv.shape[0], heads * 64), device=qkv.device, dtype=dt)
+    _chk(out, dt, "attn_temporal.out")
+    if qkv.numel() < B * T * N * 3 * heads * 64 or out.numel() < B * T * N * heads * 64:
+        raise _lib.VitronHipError(f"attn_temporal: qkv {tuple(qkv.shape)} / out {tuple(out.shape)} too small for {B * T * N} rows of {heads} heads")
     _lib.check(lib.vt_attn_temporal(_p(qkv), _p(out), B, T, N, heads, _stream()), "vt_attn_temporal", lib)
     return out
+
+
+def attn_temporal_f32(qkv: torch.Tensor, B: int, T: int, N: int, heads: int, dtype=None, out: Optional[torch.Tensor] = None,
+                      out_lo: Optional[torch.Tensor] = None):
+    """Temporal attention on fp32 q | k | v rows (a row-strided view: its row stride travels as ld) -> (hi, lo), the output as an operand
+    pair in `dtype` (default: the dtype of `out`, else the default operand)."""
+    if dtype is None:
+        dtype = out.dtype if out is not None else _lib.torch_dtype()
+    lib = _lib.lib_for(dtype)
+    _chk_view(qkv, torch.float32, "attn_temporal_f32.qkv")
+    if qkv.dim() != 2 or qkv.shape[0] != B * T * N or qkv.shape[1] != 3 * heads * 64:
+        raise _lib.VitronHipError(f"attn_temporal_f32: qkv is {tuple(qkv.shape)}, expected {(B * T * N, 3 * heads * 64)}")
+    if out is None:
+        out = torch.empty((qkv.shape[0], heads * 64), device=qkv.device, dtype=dtype)
+    if out_lo is None:
+        out_lo = torch.empty((qkv.shape[0], heads * 64), device=qkv.device, dtype=dtype)
+    for name, t in (("out", out), ("out_lo", out_lo)):
+        _chk(t, dtype, "attn_temporal_f32." + name)
+        if t.numel() < B * T * N * heads * 64:
+            raise _lib.VitronHipError(f"attn_temporal_f32.{name}: {t.numel()} elements for {B * T * N} rows of {heads * 64}")
+    _lib.check(lib.vt_attn_temporal_f32(_p(qkv), qkv.stride(0), _p(out), _p(out_lo), B, T, N, heads, _stream()), "vt_attn_temporal_f32", lib)
+    return out, out_lo
+
+
+def vit_embed(patch_out: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, g: torch.Tensor, b: torch.Tensor, F: int, G2: int,
+              eps: float, out: Optional[torch.Tensor] = None, lib=None) -> torch.Tensor:
+    """x fp32 [F * (G2 + 1)][D]: CLS / position add + pre-LayerNorm of the ViT front end (all fp32; `lib`: the build to run, default the
+    default operand's -- the kernel has no 16-bit argument)."""
+    lib = _lib.load() if lib is None else lib
+    D = pos.shape[-1]
+    for name, t, n in (("patch_out", patch_out, F * G2 * D), ("cls", cls, D), ("pos", pos, (G2 + 1) * D), ("g", g, D), ("b", b, D)):
+        _chk(t, torch.float32, "vit_embed." + name)
+        if t.numel() != n:
+            raise _lib.VitronHipError(f"vit_embed.{name}: {t.numel()} elements, expected {n}")
+    if out is None:
+        out = torch.empty((F * (G2 + 1), D), device=pos.device, dtype=torch.float32)
+    _chk(out, torch.float32, "vit_embed.out")
+    if out.numel() < F * (G2 + 1) * D:
+        raise _lib.VitronHipError(f"vit_embed.out: {out.numel()} elements for {F * (G2 + 1)} rows of {D}")
+    _lib.check(lib.vt_vit_embed(_p(patch_out), _p(cls), _p(pos), _p(g), _p(b), _p(out), F, G2, D, float(eps), _stream()), "vt_vit_embed", lib)
+    return out
+
+
+def region_pool(feats: torch.Tensor, slices: torch.Tensor, G: int, image_size: int, pooled: Optional[torch.Tensor] = None,
+                want_mask: bool = True, coords: Optional[torch.Tensor] = None, loc_w0: Optional[torch.Tensor] = None,
+                loc_b0: Optional[torch.Tensor] = None, loc_out: Optional[torch.Tensor] = None,
+                cell_mask: Optional[torch.Tensor] = None, cell_count: Optional[torch.Tensor] = None):
+    """The pooling launch of the region extractor: feats 16-bit [B][G*G][D], slices int32 [B][4] -> (pooled [B][D], cell_mask int32
+    [B][G*G] | None, cell_count int32 [B] | None, loc_out); want_mask=False passes NULL for the two optional outputs. With loc_out (a 16-bit [B][>= loc_n] tensor or row-strided view, loc_n =
+    loc_w0.shape[0]) LocationEncoder layer 0 is evaluated into its first loc_n columns from coords fp32 [B][4], loc_w0 16-bit [loc_n][8]
+    and loc_b0 fp32 [loc_n]."""
+    lib, dt = _op16(feats, "region_pool.feats")
+    _chk(feats, dt, "region_pool.feats")
+    _chk(slices, torch.int32, "region_pool.slices")
+    B = slices.shape[0]
+    if feats.dim() != 3 or feats.shape[0] != B or feats.shape[1] != G * G or slices.numel() != B * 4:
+        raise _lib.VitronHipError(f"region_pool: feats {tuple(feats.shape)} / slices {tuple(slices.shape)} do not describe {B} boxes on a {G}x{G} grid")
+    D = feats.shape[2]
+    if pooled is None:
+        pooled = torch.empty((B, D), device=feats.device, dtype=dt)
+    _chk(pooled, dt, "region_pool.pooled")
+    if pooled.numel() < B * D:
+        raise _lib.VitronHipError(f"region_pool.pooled: {pooled.numel()} elements for {B} rows of {D}")
+    mask, count = cell_mask, cell_count
+    if mask is None and want_mask:
+        mask = torch.empty((B, G * G), device=feats.device, dtype=torch.int32)
+    if count is None and want_mask:
+        count = torch.empty((B,), device=feats.device, dtype=torch.int32)
+    for name, t, n in (("cell_mask", mask, B * G * G), ("cell_count", count, B)):
+        if t is not None:
+            _chk(t, torch.int32, "region_pool." + name)
+            if t.numel() < n:
+                raise _lib.VitronHipError(f"region_pool.{name}: {t.numel()} elements, expected {n}")
+    loc_n = ld_loc = 0
+    if loc_out is not None:
+        _chk_view(loc_out, dt, "region_pool.loc_out")
+        _chk(coords, torch.float32, "region_pool.coords")
+        _chk(loc_w0, dt, "region_pool.loc_w0")
+        _chk(loc_b0, torch.float32, "region_pool.loc_b0")
+        loc_n = loc_b0.numel()
+        if loc_w0.numel() != loc_n * 8 or coords.numel() != B * 4 or loc_out.dim() != 2 or loc_out.shape[0] != B or loc_out.shape[1] < loc_n:
+            raise _lib.VitronHipError(f"region_pool: loc_w0 {tuple(loc_w0.shape)} / coords {tuple(coords.shape)} / loc_out "
+                                      f"{tuple(loc_out.shape)} do not describe {loc_n} outputs for {B} boxes")
+        ld_loc = loc_out.stride(0)
+    _lib.check(lib.vt_region_pool(_p(feats), _p(slices), B, G, image_size, D, _p(pooled), _p(mask), _p(count), _p(coords), _p(loc_w0),
+                                  _p(loc_b0), loc_n, _p(loc_out), ld_loc, _stream()), "vt_region_pool", lib)
+    return pooled, mask, count, loc_out
 
 
 def im2col(pixels: torch.Tensor, patch: int, k_pad: int, dtype=None) -> torch.Tensor:
