@@ -96,6 +96,8 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
  * vt_sample_row, vt_sample_rows and vt_sample_rows_allow do not change. */
 /* 114 also carries the tower unit entry points vt_vit_embed, vt_region_pool and vt_attn_temporal_f32 WITHOUT a bump: three new symbols
  * that forward to launches vt_vit_forward and vt_region_forward already make; no struct and no existing signature changes. */
+/* 114 also carries vt_sample_rows_trunc and struct vt_trunc_row WITHOUT a bump: one new symbol and one new struct; struct vt_sample_row,
+ * vt_sample_rows, vt_sample_rows_allow and vt_sample_rows_adj do not change. */
 #define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
@@ -511,6 +513,43 @@ int vt_sample_rows_adj(const float* logits, int rows, int V, int ldl, const vt_s
                        const uint32_t* const* allow /* DEVICE array of `rows` device pointers, entries and the array may be NULL */,
                        const float* const* adjust /* DEVICE array of `rows` device pointers to fp32 [V][2], entries and the array may be NULL */,
                        int* out_ids, int* kept_count, float* logprob, void* stream);
+
+/* vt_sample_rows_adj with PER-ROW TRUNCATION: transformers' MinPLogitsWarper, TypicalLogitsWarper, EpsilonLogitsWarper
+ * and EtaLogitsWarper, which follow top-k and top-p in GenerationMixin's warper chain. trunc: DEVICE array of `rows` vt_trunc_row (16
+ * bytes each, 4-byte aligned; the offsets are part of the ABI):
+ *   @0  float min_p            active iff min_p > 0
+ *   @4  float typical_p        active iff 0 < typical_p < 1
+ *   @8  float epsilon_cutoff   active iff 0 < epsilon_cutoff < 1
+ *   @12 float eta_cutoff       active iff 0 < eta_cutoff < 1
+ * Anything else in a field (0, a negative value, NaN, a typical_p or a cutoff >= 1) means that stage is off. A row whose four stages
+ * are off returns, bit for bit, the out_ids, kept_count and logprob vt_sample_rows_adj returns for it; a greedy row (temperature not
+ * > 0) ignores its entry; trunc == NULL is the vt_sample_rows_adj launch itself.
+ * The stages run on a sampled row after the top-k and top-p steps, in this order. A is the set of survivors so far and
+ * q_i = exp(s_i) / sum_{j in A} exp(s_j) the softmax of the scaled, penalised, masked, adjusted logits s over A -- renormalised after
+ * every stage, as every warper sees -inf at the ids removed before it:
+ *   1. min_p: i leaves when q_i < min_p * max_A q. Tokens tied with the maximum of A stay.
+ *   2. typical_p (mass m): H = -sum_A q log q, d_i = |-log q_i - H|; d* = the smallest of the d_i with sum_{d_j <= d*} q_j >= m; i
+ *      stays when d_i <= d*. No such d*: all stay. This stage may remove the arg-max token.
+ *   3. epsilon_cutoff: i leaves when q_i < epsilon_cutoff. Tokens tied with the maximum of the CURRENT A stay.
+ *   4. eta_cutoff (e): H = the entropy over the current A, eta = min(e, sqrt(e) * exp(-H)); i leaves when q_i < eta. Tokens tied with
+ *      the maximum of the current A stay.
+ * kept_count is the size of the final A; the draw is vt_sample_rows' inverse CDF over the final A in index order, the row's uniform
+ * scaled by the mass of A. logprob stays over the RAW row. The statistics are fp32 (one fast exponential and one fast logarithm per
+ * token, tree sums); d* is found exactly among the fp32 d_i by bisection on their bit patterns. The kernel is total: no field value leads
+ * to an access outside the row. Both forms, the argument checks and VT_SAMPLE_ROWS_MAX_V are vt_sample_rows's; trunc must be 4-byte
+ * aligned.
+ * 114 carries this entry point WITHOUT a bump: one new symbol and one new struct, nothing existing changes (see the note at VT_ABI_VERSION). */
+typedef struct vt_trunc_row {
+  float min_p;
+  float typical_p;
+  float epsilon_cutoff;
+  float eta_cutoff;
+} vt_trunc_row;
+int vt_sample_rows_trunc(const float* logits, int rows, int V, int ldl, const vt_sample_row* params,
+                         const uint32_t* const* allow /* DEVICE array of `rows` device pointers, entries and the array may be NULL */,
+                         const float* const* adjust /* DEVICE array of `rows` device pointers to fp32 [V][2], entries and the array may be NULL */,
+                         const vt_trunc_row* trunc /* DEVICE array [rows], or NULL */,
+                         int* out_ids, int* kept_count, float* logprob, void* stream);
 
 /* BEAM SEARCH (the role of transformers' GenerationMixin beam search: log_softmax + running scores + torch.topk over
  * num_beams * vocab, and the cache reorder behind it).

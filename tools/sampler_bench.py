@@ -9,6 +9,12 @@ beforehand (the kernel's cost) and built per call from the list of masks ("+ptrs
 the host build and the ceil(V / 32) * 4-byte upload of ONE step-dependent mask, of 16000 ids and of 8: the engine's extra cost per
 constrained row and step.
 
+The truncation arms (vt_sample_rows_trunc) run the all-sampled batch too: the entry point with trunc = NULL (the
+vt_sample_rows launch itself) and with all-inactive rows (the trunc kernel, stages skipped) -- to be read against "rows sampled" and, with
+--baseline-lib, against the two "baseline rows sampled" arms, whose difference is the spread of repeated parent runs --, each stage
+alone and all four. "host warpers" is what the feature replaces: the [rows, V] fp32 logits read back and transformers' temperature /
+top-p / MinP / Typical / Epsilon / Eta warpers, a softmax and torch.multinomial on the CPU.
+
 The arms are alternated inside one process over `--rounds` rounds of `--iters` launches between two device events; per arm the output
 gives every round, the median and the spread (max - min) / median -- two arms are apart only when they differ by more than the spreads.
 `--baseline-lib PATH` adds vt_argmax, vt_sample_top_p and vt_sample_rows of ANOTHER build of libvitron_hip.so (for instance the parent
@@ -29,7 +35,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vitron_amd import _lib, ops  # noqa: E402
-from vitron_amd.sampling import allow_mask, pack_sample_rows  # noqa: E402
+from vitron_amd.sampling import allow_mask, pack_sample_rows, pack_trunc_rows  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--rows", default="1,4,16")
@@ -101,6 +107,26 @@ for rows in [int(r) for r in args.rows.split(",")]:
     half_ids = np.flatnonzero(g.random(V) < 0.5)
     arms["step mask upload (16000 ids)"] = lambda: torch.from_numpy(allow_mask(V, half_ids).view(np.int32)).to(dev)
     arms["step mask upload (8 ids)"] = lambda: torch.from_numpy(allow_mask(V, [5, 31, 32, 1023, 1024, 7777, 20000, V - 1]).view(np.int32)).to(dev)
+    if base is not None:      # the same parent launch a second time: the spread of repeated parent runs, measured in this run
+        arms["baseline rows sampled (again)"] = arms["baseline rows sampled"]
+    lib = _lib.load()
+    arms["trunc entry, trunc=NULL"] = lambda: lib.vt_sample_rows_trunc(lg.data_ptr(), rows, V, V, pr_s.data_ptr(), None, None, None,
+                                                                       out.data_ptr(), None, None, stream)
+    stages = {"all inactive": None, "min_p 0.1": (0.1, 1.0, 0.0, 0.0), "typical_p 0.9": (0.0, 0.9, 0.0, 0.0),
+              "epsilon 1e-3": (0.0, 1.0, 1e-3, 0.0), "eta 1e-3": (0.0, 1.0, 0.0, 1e-3), "all four": (0.1, 0.9, 1e-3, 1e-3)}
+    for label, t in stages.items():
+        tr = pack_trunc_rows([t] * rows, dev)
+        arms[f"trunc {label}"] = lambda tr=tr: ops.sample_rows(lg, pr_s, trunc=tr)
+    from transformers.generation import logits_process as LP
+    chain = [LP.TemperatureLogitsWarper(T), LP.TopPLogitsWarper(top_p=P), LP.MinPLogitsWarper(min_p=0.1), LP.TypicalLogitsWarper(mass=0.9),
+             LP.EpsilonLogitsWarper(epsilon=1e-3), LP.EtaLogitsWarper(epsilon=1e-3, device="cpu")]
+
+    def host_warpers():
+        x = lg.cpu()
+        for w in chain:
+            x = w(None, x)
+        return torch.multinomial(torch.softmax(x, -1), 1).to(dev)
+    arms["host warpers (read-back + all four)"] = host_warpers
     pr_lp = params("sampled", False)
     arms["rows sampled +logprob"] = lambda: ops.sample_rows(lg, pr_lp, return_logprob=True)
     assert torch.equal(ops.sample_rows(lg, params("sampled", False)), ops.sample_top_p(lg, T, P, SEED, STEP))      # the same draw

@@ -478,6 +478,12 @@ int vt_sample_rows_adj(const float* logits, int rows, int V, int ldl, const vt_s
   return vt_sample_rows_launch(logits, rows, V, ldl, params, allow, out_ids, kept_count, logprob, S(stream), adjust);
 }
 
+int vt_sample_rows_trunc(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, const uint32_t* const* allow,
+                         const float* const* adjust, const vt_trunc_row* trunc, int* out_ids, int* kept_count, float* logprob,
+                         void* stream) {
+  return vt_sample_rows_launch(logits, rows, V, ldl, params, allow, out_ids, kept_count, logprob, S(stream), adjust, trunc);
+}
+
 // ---- beam search (vt_beam.hip) ----------------------------------------------------------------------------------------
 size_t vt_beam_step_scratch_bytes(int groups, int beams_in, int n_out) { return vt_beam_step_scratch_bytes_impl(groups, beams_in, n_out); }
 

@@ -264,7 +264,8 @@ int vt_sample_top_p_launch(const float* logits, int rows, int V, int ldl, float 
                            uint64_t step, int* out_ids, int* kept_count, hipStream_t s);
 int vt_sample_rows_launch(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, const uint32_t* const* allow,
                           int* out_ids, int* kept_count, float* logprob, hipStream_t s,    // allow == NULL: vt_sample_rows
-                          const float* const* adjust = nullptr);                           // adjust != NULL: vt_sample_rows_adj
+                          const float* const* adjust = nullptr,                            // adjust != NULL: vt_sample_rows_adj
+                          const vt_trunc_row* trunc = nullptr);                            // trunc != NULL: vt_sample_rows_trunc
 
 // ---- vt_beam.hip ----------------------------------------------------------------------------------
 size_t vt_beam_step_scratch_bytes_impl(int groups, int beams_in, int n_out);

@@ -199,6 +199,19 @@ __device__ __forceinline__ float add_rounded(float x, float y) {
   return x + y;
 }
 
+// kTrunc (vt_sample_rows_trunc): MinP / Typical / Epsilon / Eta warpers on the survivors of top-k and top-p. Both bodies
+// work on p = the token's probability over the top-k set; the softmax over the survivors A is q = p / S with S = sum_A p, so every rule
+// is stated on p: q < t  <=>  p < t * S, and with T = sum_A p log p:  H = log S - T / S  and  -log q - H = T / S - log p.
+__device__ __forceinline__ bool trunc_on(float x) { return x > 0.f && x < 1.f; }      // (NaN: off)
+// the bit pattern of d = |T / S - log p|: d >= 0 (or NaN), so the unsigned pattern orders it and is < 2^31
+__device__ __forceinline__ uint32_t trunc_d_key(float p, float c) { return __float_as_uint(fabsf(c - __logf(p))); }
+__device__ __forceinline__ float trunc_plogp(float p) { return p > 0.f ? p * __logf(p) : 0.f; }
+// EtaLogitsWarper's threshold on p
+__device__ __forceinline__ float trunc_eta(float e, float S, float T) {
+  const float H = __logf(S) - T / S;
+  return fminf(e, sqrtf(e) * __expf(-H)) * S;
+}
+
 // V-bit "seen" mask of the row's history in LDS: bit id is set for every history id in [0, V). Ids outside that range (the negative
 // image / region sentinels of a multimodal prompt, anything >= V) are skipped and index nothing. Returns whether a penalty applies.
 __device__ __forceinline__ bool fill_seen_mask(uint32_t* seen, int V, const SampleArgs& a) {
@@ -225,10 +238,15 @@ __device__ __forceinline__ bool fill_seen_mask(uint32_t* seen, int V, const Samp
 // i.e. exactly a row with -inf written there. The raw log-sum-exp does not go through val(): logprob stays over the RAW row.
 // kAdj (vt_sample_rows_adj): `adj` is the row's additive adjustment in GLOBAL memory, fp32 [V][2] = (pre, post) per token,
 // 8-byte aligned, NULL = none. val(i) reads pair i for i < V only; pre is added after the mask and before the penalty, post after it.
-template <bool kRows, bool kAllow = false, bool kAdj = false>
+// kTrunc (vt_sample_rows_trunc): no V-bit survivor mask is kept (the seen mask has half of the static LDS already). The
+// stages reduce to two block-uniform facts about a token's p -- a lower threshold `plo` (min_p, epsilon and eta only ever raise it) and
+// the typical stage's (c, key) pair -- and VT_ALIVE(p) re-evaluates them wherever the keep test of the top-p step stands. With every stage
+// off plo = 0 and the pair is unused: the sets, sums and the walk are those of the kAdj body.
+template <bool kRows, bool kAllow = false, bool kAdj = false, bool kTrunc = false>
 __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row, int V, const SampleArgs& a, uint32_t* seen,
                                                    int* __restrict__ out_id, int* __restrict__ kept_out, float* __restrict__ logprob,
-                                                   const uint32_t* __restrict__ allow = nullptr, const float* __restrict__ adj = nullptr) {
+                                                   const uint32_t* __restrict__ allow = nullptr, const float* __restrict__ adj = nullptr,
+                                                   vt_trunc_row tr = vt_trunc_row{}) {
   __shared__ float sh[16];
   __shared__ float sh_scan[16];
   __shared__ int chosen;
@@ -328,6 +346,76 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
   }
   kept = block_sum_1024(kept, sh);
   cnt = block_sum_1024(cnt, sh);
+  float plo = 0.f, typ_c = 0.f;      // (kTrunc) what the stages leave: p >= plo, and with `typ` the key of |typ_c - log p| <= typ_key
+  uint32_t typ_key = 0x7fffffffu;
+  bool typ = false;
+  // (a macro whose `!kTrunc ||` the front end folds away, not a lambda: the flavours without truncation compile to the code they had)
+#define VT_ALIVE(p) (!kTrunc || ((p) >= plo && (!typ || trunc_d_key((p), typ_c) <= typ_key)))
+  if constexpr (kTrunc) {
+    const bool on_min = tr.min_p > 0.f, on_typ = trunc_on(tr.typical_p), on_eps = trunc_on(tr.epsilon_cutoff),
+               on_eta = trunc_on(tr.eta_cutoff);
+    if (on_min || on_typ || on_eps || on_eta) {       // block-uniform
+      float S = 0.f, top = 0.f, T = 0.f;
+      auto stats = [&](bool want_T) {      // mass, maximum and sum of p log p over the current survivors
+        float s = 0.f, m = 0.f, t = 0.f;
+        for (int i = tid; i < V; i += 1024) {
+          const float p = VT_P_OF(i) * inv_z;
+          if (p >= thr && val(i) * inv_temp >= floor_logit && VT_ALIVE(p)) {
+            s += p;
+            m = fmaxf(m, p);
+            if (want_T) t += trunc_plogp(p);
+          }
+        }
+        S = block_sum_1024(s, sh);
+        top = block_max_1024(m, sh);
+        if (want_T) T = block_sum_1024(t, sh);
+      };
+      // "p < t leaves unless it ties with the maximum" is p >= min(t, top) for those who stay (a NaN t: only the maximum stays)
+      if (on_min) {
+        stats(false);
+        plo = fmaxf(plo, fminf(tr.min_p * top, top));
+      }
+      if (on_typ) {
+        stats(true);
+        const float c = T / S, need = tr.typical_p * S;
+        // the smallest key whose tokens reach the mass, exactly: 31 counting passes over [0, 2^31) (the sign bit of d is clear). The
+        // whole of A has mass S >= need, so the largest key always qualifies: nothing reaches the mass <=> all stay.
+        uint32_t lo = 0u, hi = 0x7fffffffu;
+        for (int it = 0; it < 31; ++it) {
+          const uint32_t mid = lo + ((hi - lo) >> 1);
+          float m = 0.f;
+          for (int i = tid; i < V; i += 1024) {
+            const float p = VT_P_OF(i) * inv_z;
+            if (p >= thr && val(i) * inv_temp >= floor_logit && VT_ALIVE(p) && trunc_d_key(p, c) <= mid) m += p;
+          }
+          m = block_sum_1024(m, sh);
+          if (m >= need) hi = mid; else lo = mid + 1u;
+        }
+        typ_c = c;
+        typ_key = hi;
+        typ = true;
+      }
+      if (on_eps) {
+        stats(false);
+        plo = fmaxf(plo, fminf(tr.epsilon_cutoff * S, top));
+      }
+      if (on_eta) {
+        stats(true);
+        plo = fmaxf(plo, fminf(trunc_eta(tr.eta_cutoff, S, T), top));
+      }
+      kept = 0.f;
+      cnt = 0.f;
+      for (int i = tid; i < V; i += 1024) {
+        const float p = VT_P_OF(i) * inv_z;
+        if (p >= thr && val(i) * inv_temp >= floor_logit && VT_ALIVE(p)) {
+          kept += p;
+          cnt += 1.f;
+        }
+      }
+      kept = block_sum_1024(kept, sh);
+      cnt = block_sum_1024(cnt, sh);
+    }
+  }
   if (tid == 0 && kept_out) *kept_out = (int)cnt;
   // inverse CDF over the kept tokens in index order: thread t owns the contiguous index range [t*chunk, (t+1)*chunk)
   const float u = sample_uniform24(a) * kept;
@@ -336,7 +424,7 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
   float mine = 0.f;
   for (int i = i0; i < i1; ++i) {
     const float p = VT_P_OF(i) * inv_z;
-    if (p >= thr && val(i) * inv_temp >= floor_logit) mine += p;
+    if (p >= thr && val(i) * inv_temp >= floor_logit && VT_ALIVE(p)) mine += p;
   }
   // exclusive prefix over threads: wave scan + scan of the 16 wave totals
   float incl = mine;
@@ -359,7 +447,7 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
     int pick = -1;
     for (int i = i0; i < i1; ++i) {
       const float p = VT_P_OF(i) * inv_z;
-      if (p >= thr && val(i) * inv_temp >= floor_logit) {
+      if (p >= thr && val(i) * inv_temp >= floor_logit && VT_ALIVE(p)) {
         pick = i;
         c += p;
         if (u < c) break;
@@ -371,7 +459,7 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
   if (chosen < 0 && mine > 0.f) {  // u landed on a rounding seam: take the last kept token of the highest owning range
     int last = -1;
     for (int i = i0; i < i1; ++i)
-      if (VT_P_OF(i) * inv_z >= thr && val(i) * inv_temp >= floor_logit) last = i;
+      if (VT_P_OF(i) * inv_z >= thr && val(i) * inv_temp >= floor_logit && VT_ALIVE(VT_P_OF(i) * inv_z)) last = i;
     atomicMax(&chosen, last);
   }
   __syncthreads();
@@ -383,6 +471,7 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
   }
 }
 #undef VT_P_OF
+#undef VT_ALIVE
 
 // Same rule with the row held in registers (V <= 32 * 1024): every thread owns 32 consecutive logits, computes their
 // exponentials ONCE, and the 30 bisection passes, the kept-mass pass and the inverse-CDF walk never touch memory again.
@@ -395,10 +484,15 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
 // kAdj: the thread's 32 (pre, post) pairs are 256 contiguous bytes of the row's adjustment in global memory, read once -- 16 bytes (two
 // pairs) at a time where the adjustment is 16-byte aligned, else 8: pre is added after the mask, then the penalty, then post, slot by
 // slot. Slots past V read nothing and stay -inf.
-template <bool kRows, bool kAllow = false, bool kAdj = false>
+// kTrunc (vt_sample_rows_trunc): the stages run where p holds the kept probabilities and 0 elsewhere. The survivors are the
+// slots with p > 0 and a stage zeroes what it removes, so no second array and no mask register lives across the body; the typical
+// stage recomputes a slot's d from its p in each of its 31 counting passes instead of keeping 32 keys. With every stage off nothing
+// between the top-p step and the prefix scan runs: p, mine and cnt are the kAdj body's.
+template <bool kRows, bool kAllow = false, bool kAdj = false, bool kTrunc = false>
 __device__ __forceinline__ void sample_reg_body(const float* __restrict__ row, int V, const SampleArgs& a, uint32_t* seen,
                                                 int* __restrict__ out_id, int* __restrict__ kept_out, float* __restrict__ logprob,
-                                                const uint32_t* __restrict__ allow = nullptr, const float* __restrict__ adj = nullptr) {
+                                                const uint32_t* __restrict__ allow = nullptr, const float* __restrict__ adj = nullptr,
+                                                vt_trunc_row tr = vt_trunc_row{}) {
   constexpr int NPT = 32;
   __shared__ float sh[2][16];
   __shared__ float sh_scan[16];
@@ -582,6 +676,66 @@ __device__ __forceinline__ void sample_reg_body(const float* __restrict__ row, i
     mine += p[j];
     cnt += keep ? 1.f : 0.f;
   }
+  if constexpr (kTrunc) {
+    const bool on_min = tr.min_p > 0.f, on_typ = trunc_on(tr.typical_p), on_eps = trunc_on(tr.epsilon_cutoff),
+               on_eta = trunc_on(tr.eta_cutoff);
+    if (on_min || on_typ || on_eps || on_eta) {       // block-uniform
+      float S = 0.f, top = 0.f, T = 0.f;
+      auto stats = [&](bool want_T) {      // mass, maximum and sum of p log p over the current survivors
+        float s = 0.f, m = 0.f, t = 0.f;
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) {
+          s += p[j];
+          m = fmaxf(m, p[j]);
+          if (want_T) t += trunc_plogp(p[j]);
+        }
+        S = block_sum(s);
+        top = block_max(m);
+        if (want_T) T = block_sum(t);
+      };
+      // "p < t leaves unless it ties with the maximum": those below min(t, top) are zeroed (a NaN t: only the maximum stays)
+      auto cut = [&](float t) {
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) p[j] = p[j] >= t ? p[j] : 0.f;
+      };
+      if (on_min) {
+        stats(false);
+        cut(fminf(tr.min_p * top, top));
+      }
+      if (on_typ) {
+        stats(true);
+        const float c = T / S, need = tr.typical_p * S;
+        // the smallest key whose tokens reach the mass, exactly: 31 counting passes over [0, 2^31) (the sign bit of d is clear). The
+        // whole of A has mass S >= need, so the largest key always qualifies: nothing reaches the mass <=> all stay.
+        uint32_t lo = 0u, hi = 0x7fffffffu;
+        for (int it = 0; it < 31; ++it) {
+          const uint32_t mid = lo + ((hi - lo) >> 1);
+          float m = 0.f;
+#pragma unroll
+          for (int j = 0; j < NPT; ++j) m += (trunc_d_key(p[j], c) <= mid) ? p[j] : 0.f;     // (a removed slot adds its 0)
+          m = block_sum(m);
+          if (m >= need) hi = mid; else lo = mid + 1u;
+        }
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) p[j] = (trunc_d_key(p[j], c) <= hi) ? p[j] : 0.f;
+      }
+      if (on_eps) {
+        stats(false);
+        cut(fminf(tr.epsilon_cutoff * S, top));
+      }
+      if (on_eta) {
+        stats(true);
+        cut(fminf(trunc_eta(tr.eta_cutoff, S, T), top));
+      }
+      mine = 0.f;
+      cnt = 0.f;
+#pragma unroll
+      for (int j = 0; j < NPT; ++j) {
+        mine += p[j];
+        cnt += p[j] > 0.f ? 1.f : 0.f;
+      }
+    }
+  }
   const float kept = block_sum(mine);
   cnt = block_sum(cnt);
   if (tid == 0) {
@@ -711,6 +865,39 @@ __global__ __launch_bounds__(1024) void sample_rows_adj_kernel(const float* __re
     sample_stream_body<true, true, true>(row, V, a, seen, out_ids + r, kept_count ? kept_count + r : nullptr,
                                          logprob ? logprob + r : nullptr, mask, adj);
 }
+// vt_sample_rows_trunc: the adj launch with row r's truncation stages trunc[r] (min_p, typical_p, epsilon_cutoff, eta_cutoff; DESIGN.md
+// 9.9). A kernel of its own once more, so that the three above stay the code they were. The allow and the adjust ARRAY may be NULL.
+// A greedy row ignores its stages: it takes the kAdj body, a sampled row the kTrunc one -- each inlined with `greedy` known, so neither
+// copy carries the other's path (the register form kept the unscaled logits alive for the greedy branch across the stages otherwise).
+template <bool kReg>
+__global__ __launch_bounds__(1024) void sample_rows_trunc_kernel(const float* __restrict__ logits, int V, int ldl,
+                                                                 const vt_sample_row* __restrict__ params,
+                                                                 const uint32_t* const* __restrict__ allow,
+                                                                 const float* const* __restrict__ adjust,
+                                                                 const vt_trunc_row* __restrict__ trunc, int* __restrict__ out_ids,
+                                                                 int* __restrict__ kept_count, float* __restrict__ logprob) {
+  __shared__ uint32_t seen[(kReg ? 32 * 1024 : kSampleRowsMaxV) / 32];
+  const int r = blockIdx.x;
+  SampleArgs a = row_args(params[r]);
+  const float* row = logits + (size_t)r * ldl;
+  const uint32_t* mask = allow ? allow[r] : nullptr;
+  const float* adj = adjust ? adjust[r] : nullptr;
+  int* const kept = kept_count ? kept_count + r : nullptr;
+  float* const lp = logprob ? logprob + r : nullptr;
+  if (a.greedy) {        // block-uniform
+    a.greedy = true;
+    if constexpr (kReg)
+      sample_reg_body<true, true, true>(row, V, a, seen, out_ids + r, kept, lp, mask, adj);
+    else
+      sample_stream_body<true, true, true>(row, V, a, seen, out_ids + r, kept, lp, mask, adj);
+    return;
+  }
+  a.greedy = false;
+  if constexpr (kReg)
+    sample_reg_body<true, true, true, true>(row, V, a, seen, out_ids + r, kept, lp, mask, adj, trunc[r]);
+  else
+    sample_stream_body<true, true, true, true>(row, V, a, seen, out_ids + r, kept, lp, mask, adj, trunc[r]);
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Shifted-token cross entropy of LlamaForCausalLM.forward(labels=...) (ignore_index rows skipped, mean over the rest):
@@ -776,14 +963,19 @@ int vt_sample_top_p_launch(const float* logits, int rows, int V, int ldl, float 
 }
 
 int vt_sample_rows_launch(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, const uint32_t* const* allow,
-                          int* out_ids, int* kept_count, float* logprob, hipStream_t s, const float* const* adjust) {
+                          int* out_ids, int* kept_count, float* logprob, hipStream_t s, const float* const* adjust,
+                          const vt_trunc_row* trunc) {
   VT_REQUIRE(logits && params && out_ids, "vt_sample_rows: null pointer (logits, params and out_ids are required)");
   VT_REQUIRE(rows > 0 && V > 0 && ldl >= V, "vt_sample_rows: rows=%d V=%d ldl=%d (rows, V > 0 and ldl >= V)", rows, V, ldl);
   VT_REQUIRE(((uintptr_t)params % 8) == 0, "vt_sample_rows: params must be 8-byte aligned");
   VT_REQUIRE(((uintptr_t)allow % 8) == 0, "vt_sample_rows_allow: the allow pointer array must be 8-byte aligned");
   VT_REQUIRE(((uintptr_t)adjust % 8) == 0, "vt_sample_rows_adj: the adjust pointer array must be 8-byte aligned");
+  VT_REQUIRE(((uintptr_t)trunc % 4) == 0, "vt_sample_rows_trunc: trunc must be 4-byte aligned");
   if (V <= 32 * 1024 && (ldl % 4) == 0 && ((uintptr_t)logits % 16) == 0) {
-    if (adjust)
+    if (trunc)
+      hipLaunchKernelGGL(sample_rows_trunc_kernel<true>, dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, allow, adjust, trunc,
+                         out_ids, kept_count, logprob);
+    else if (adjust)
       hipLaunchKernelGGL(sample_rows_adj_kernel<true>, dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, allow, adjust, out_ids,
                          kept_count, logprob);
     else if (allow)
@@ -794,7 +986,10 @@ int vt_sample_rows_launch(const float* logits, int rows, int V, int ldl, const v
   } else {
     VT_REQUIRE(V <= VT_SAMPLE_ROWS_MAX_V, "vt_sample_rows: V=%d is beyond the history mask of the streaming form (V <= %d)", V,
                VT_SAMPLE_ROWS_MAX_V);
-    if (adjust)
+    if (trunc)
+      hipLaunchKernelGGL(sample_rows_trunc_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, allow, adjust, trunc,
+                         out_ids, kept_count, logprob);
+    else if (adjust)
       hipLaunchKernelGGL(sample_rows_adj_kernel<false>, dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, allow, adjust, out_ids,
                          kept_count, logprob);
     else if (allow)

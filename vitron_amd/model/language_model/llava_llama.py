@@ -469,7 +469,7 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                  return_logits=False, padded_batch=False, repetition_penalty=1.0, return_logprobs=False, suppress_tokens=None,
                  begin_suppress_tokens=None, min_new_tokens=None, bad_words_ids=None, allowed_token_ids=None, num_return_sequences=1,
                  length_penalty=1.0, early_stopping=False, no_repeat_ngram_size=None, sequence_bias=None, presence_penalty=0.0,
-                 frequency_penalty=0.0, **kwargs):
+                 frequency_penalty=0.0, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, **kwargs):
         """repetition_penalty (RepetitionPenaltyLogitsProcessor; 1.0 is off) and return_logprobs: with both at their defaults a step
         launches what it always did (vt_argmax / vt_sample_top_p). Otherwise every step is ONE vt_sample_rows launch (row b: stream = b,
         counter = step -- today's draws) whose penalty history -- the sample's non-negative prompt ids plus what it has generated -- lives
@@ -496,6 +496,12 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         pick from the sample's generated ids (once, before the prefill, with sequence_bias alone) and vt_sample_rows_adj reads; nothing
         is uploaded or waited for in the loop. return_logits and return_logprobs stay RAW. ValueError: an id outside [0, vocab_size), a
         value that is not finite, an id given twice. Refused with NotImplementedError: num_beams > 1, padded_batch.
+        Truncation: min_p, typical_p, epsilon_cutoff and eta_cutoff are transformers' MinPLogitsWarper,
+        TypicalLogitsWarper, EpsilonLogitsWarper and EtaLogitsWarper (None, or min_p 0 / typical_p 1 / a cutoff 0, is off). With
+        do_sample=True they run in that order after top-k and top-p inside the sampler kernel: every step is ONE vt_sample_rows_trunc
+        launch, nothing is read back; without do_sample they are ignored, as transformers applies warpers only when sampling.
+        ValueError: min_p outside [0, 1], typical_p outside (0, 1], a cutoff outside [0, 1), a value that is not finite. Refused with
+        NotImplementedError: num_beams > 1, padded_batch.
         padded_batch=True (B > 1, right padding): reproduce what the REFERENCE's batched generate() returns -- transformers 4.31 reads the
         first token of every sample from the last COLUMN of the padded logits (a pad row for the shorter samples) and the decode-step
         fix-up (llava_arch.py:196-205) attends the pad rows of the spliced batch while masking the rows that share an index with the
@@ -520,7 +526,8 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
             begin_suppress_tokens=begin_suppress_tokens, min_new_tokens=min_new_tokens, bad_words_ids=bad_words_ids,
             allowed_token_ids=allowed_token_ids, num_return_sequences=num_return_sequences, length_penalty=length_penalty,
             early_stopping=early_stopping, no_repeat_ngram_size=no_repeat_ngram_size, sequence_bias=sequence_bias,
-            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty)
+            presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p, typical_p=typical_p,
+            epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
         dev = self.device
         input_ids = input_ids.to(dev)
         B, L0 = input_ids.shape

@@ -640,7 +640,8 @@ def adjust_pointers(adjust, rows: int, V: int, device) -> torch.Tensor:
 
 
 def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = False, return_logprob: bool = False, allow=None,
-                _allow_ptrs: Optional[torch.Tensor] = None, adjust=None, _adjust_ptrs: Optional[torch.Tensor] = None):
+                _allow_ptrs: Optional[torch.Tensor] = None, adjust=None, _adjust_ptrs: Optional[torch.Tensor] = None,
+                trunc: Optional[torch.Tensor] = None):
     """One token id per row (int32, on device) with PER-ROW parameters: greedy and sampled rows, penalties and the chosen token's
     log-probability in one launch; see vt_sample_rows in include/vitron_hip.h. `params`: the device array of vt_sample_row that
     sampling.pack_sample_rows builds (uint8 [rows, 48]). Returns ids, or (ids[, kept_count][, logprob]) when either is asked for.
@@ -650,8 +651,10 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = 
     masks it has checked itself -- built earlier, int64 [rows]; its values are dereferenced on the device as they are.
     adjust: per-row additive adjustments (vt_sample_rows_adj) -- a sequence of `rows` entries, each None or a device fp32 tensor of
     2 * V elements, the (pre, post) pairs of ops.bias_rows; pre is added before the repetition penalty, post after it. _adjust_ptrs is
-    its private pointer-array form, like _allow_ptrs. With neither, the launches are the ones above."""
-    from .sampling import ROW_BYTES
+    its private pointer-array form, like _allow_ptrs. With neither, the launches are the ones above.
+    trunc: per-row truncation (vt_sample_rows_trunc: min_p, typical_p, epsilon_cutoff, eta_cutoff after top-k and top-p) -- the device
+    array of vt_trunc_row that sampling.pack_trunc_rows builds (uint8, rows x 16 bytes). None: exactly the calls above."""
+    from .sampling import ROW_BYTES, TRUNC_ROW_BYTES
     lib = _lib.load_any()
     _chk_rows(logits, torch.float32, "sample_rows.logits")
     rows, V = logits.shape
@@ -672,15 +675,27 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = 
                 or ptrs.numel() != rows:
             raise _lib.VitronHipError(f"sample_rows.{what}: expected a contiguous int64 [{rows}] tensor on the logits' device")
         return ptrs
-    if adjust is not None or _adjust_ptrs is not None:
+    if trunc is not None and (not isinstance(trunc, torch.Tensor) or trunc.device != logits.device or trunc.dtype != torch.uint8
+                              or not trunc.is_contiguous() or trunc.numel() != rows * TRUNC_ROW_BYTES):
+        raise _lib.VitronHipError(f"sample_rows.trunc: expected a contiguous uint8 tensor of {rows} x {TRUNC_ROW_BYTES} bytes on the logits' "
+                                  "device (sampling.pack_trunc_rows)")
+    if trunc is not None or adjust is not None or _adjust_ptrs is not None:
         aptrs = None
         if _allow_ptrs is not None:
             aptrs = given_ptrs(_allow_ptrs, "_allow_ptrs")
         elif allow is not None:
             aptrs = allow_pointers(allow, rows, V, logits.device)
-        jptrs = given_ptrs(_adjust_ptrs, "_adjust_ptrs") if _adjust_ptrs is not None else adjust_pointers(adjust, rows, V, logits.device)
-        _lib.check(lib.vt_sample_rows_adj(_p(logits), rows, V, logits.stride(0), _p(params), _p(aptrs), _p(jptrs), _p(out), _p(kept),
-                                          _p(lp), _stream()), "vt_sample_rows_adj", lib)
+        jptrs = None
+        if _adjust_ptrs is not None:
+            jptrs = given_ptrs(_adjust_ptrs, "_adjust_ptrs")
+        elif adjust is not None:
+            jptrs = adjust_pointers(adjust, rows, V, logits.device)
+        if trunc is not None:
+            _lib.check(lib.vt_sample_rows_trunc(_p(logits), rows, V, logits.stride(0), _p(params), _p(aptrs), _p(jptrs), _p(trunc), _p(out),
+                                                _p(kept), _p(lp), _stream()), "vt_sample_rows_trunc", lib)
+        else:
+            _lib.check(lib.vt_sample_rows_adj(_p(logits), rows, V, logits.stride(0), _p(params), _p(aptrs), _p(jptrs), _p(out), _p(kept),
+                                              _p(lp), _stream()), "vt_sample_rows_adj", lib)
     elif allow is None and _allow_ptrs is None:
         _lib.check(lib.vt_sample_rows(_p(logits), rows, V, logits.stride(0), _p(params), _p(out), _p(kept), _p(lp), _stream()),
                    "vt_sample_rows", lib)

@@ -19,7 +19,8 @@ import torch
 from . import ops
 from .engine import parse_kv_cache_dtype
 from .sampling import (BAN_ROW_BYTES, BIAS_ROW_BYTES, BIAS_ROWS_MAX_V, ROW_BYTES, allow_mask, check_penalties, check_sampling_values,
-                       mask_words, normalise_bias, pack_ban_rows, pack_bias_rows, pack_sample_rows)
+                       check_truncation_values, mask_words, normalise_bias, pack_ban_rows, pack_bias_rows, pack_sample_rows,
+                       pack_trunc_rows, truncation_active)
 
 
 @dataclass(frozen=True, eq=False)
@@ -52,6 +53,7 @@ class GenerateArgs:
     bias: Tuple[Tuple[int, float], ...] = ()     # sequence_bias, normalised: (id, value) sorted by id, single-token keys only
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
+    trunc: Tuple[float, float, float, float] = (0.0, 1.0, 0.0, 0.0)   # (min_p, typical_p, epsilon_cutoff, eta_cutoff); off when greedy
 
     @property
     def constrained(self) -> bool:
@@ -67,10 +69,15 @@ class GenerateArgs:
         return bool(self.bias) or self.count_penalties
 
     @property
+    def truncated(self) -> bool:
+        """Is one of min_p / typical_p / epsilon_cutoff / eta_cutoff on (vt_sample_rows_trunc; a sampling call only)?"""
+        return truncation_active(*self.trunc)
+
+    @property
     def per_row(self) -> bool:
         """Does a step need the per-row sampler (vt_sample_rows) instead of vt_argmax / vt_sample_top_p?"""
         return (float(self.repetition_penalty) != 1.0 or bool(self.return_logprobs) or self.constrained or self.ngram > 0
-                or self.adjusted)
+                or self.adjusted or self.truncated)
 
 
 def static_mask_schedule(V: int, steps: int, banned_always, banned_begin, min_new: int, eos, allowed_ids):
@@ -99,11 +106,12 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
                           eos_token_id, pad_token_id, num_beams, seed, return_logits, padded_batch, repetition_penalty, return_logprobs,
                           suppress_tokens, begin_suppress_tokens, min_new_tokens, bad_words_ids, allowed_token_ids, num_return_sequences,
                           length_penalty, early_stopping, no_repeat_ngram_size, sequence_bias=None, presence_penalty=0.0,
-                          frequency_penalty=0.0) -> GenerateArgs:
+                          frequency_penalty=0.0, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> GenerateArgs:
     """generate()'s keyword arguments as a GenerateArgs. Raises, in this order and before any device work: the argument errors of
     num_beams / no_repeat_ngram_size, everything a beam call refuses, the padded_batch refusals that depend on arguments alone, the
     sampling values, the constraint arguments, a step the constraints leave no token for, constraints with padded_batch, the values of
-    sequence_bias / presence_penalty / frequency_penalty, those three with padded_batch. The sample seed
+    sequence_bias / presence_penalty / frequency_penalty, those three with padded_batch, the values of min_p / typical_p / epsilon_cutoff /
+    eta_cutoff (None is off, as in GenerationConfig; ignored without do_sample), those four with padded_batch. The sample seed
     is drawn from torch's global CPU generator (so torch.manual_seed makes sampling reproducible, as with GenerationMixin.sample) and
     only when sampling without `seed`, after the beam refusals: greedy and refused calls leave the RNG state alone."""
     num_beams = int(num_beams)
@@ -131,7 +139,10 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
         given=tuple(f"{name}=..." for name, value in optional if value)
         + tuple(f"{name}=True" for name, value in (("return_logits", return_logits), ("return_logprobs", return_logprobs)) if value)
         + tuple(f"{name}=..." for name, value in (("sequence_bias", sequence_bias), ("presence_penalty", presence_penalty),
-                                                  ("frequency_penalty", frequency_penalty)) if value))
+                                                  ("frequency_penalty", frequency_penalty)) if value)
+        + tuple(f"{name}=..." for name, value, off in (("min_p", min_p, 0.0), ("typical_p", typical_p, 1.0),
+                                                       ("epsilon_cutoff", epsilon_cutoff, 0.0), ("eta_cutoff", eta_cutoff, 0.0))
+                if value is not None and value != off))
     if num_beams > 1:
         check_beam_arguments(a, int(config.vocab_size))
     elif a.num_return_sequences != 1:
@@ -175,6 +186,14 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
     if a.adjusted and V > BIAS_ROWS_MAX_V:
         raise NotImplementedError(f"generate(sequence_bias / presence_penalty / frequency_penalty): vocab_size={V} is beyond vt_bias_rows' "
                                   f"{BIAS_ROWS_MAX_V}")
+    trunc = (0.0 if min_p is None else min_p, 1.0 if typical_p is None else typical_p, 0.0 if epsilon_cutoff is None else epsilon_cutoff,
+             0.0 if eta_cutoff is None else eta_cutoff)
+    check_truncation_values(*trunc, what="generate")
+    if do_sample:        # transformers applies warpers only when sampling
+        a = dataclasses.replace(a, trunc=tuple(float(x) for x in trunc))
+    if a.truncated and padded_batch:
+        raise NotImplementedError("generate(padded_batch=True) does not take min_p / typical_p / epsilon_cutoff / eta_cutoff; use the "
+                                  "default packed batch")
     return a
 
 
@@ -248,7 +267,9 @@ class StepPicker:
         sampler's adjust pointers, the same at every step), the bias ids / values, and the ids every row has GENERATED -- the tail of
         the penalty history where there is one, else a history of its own. With a penalty != 0 the [steps, B] vt_bias_row array
         (history_len = step) is uploaded too and every pick is preceded by ONE ops.bias_rows launch; with sequence_bias alone the
-        buffers never change and are built by ONE launch here, before the prefill.
+        buffers never change and are built by ONE launch here, before the prefill;
+      - with min_p / typical_p / epsilon_cutoff / eta_cutoff: the B vt_trunc_row entries, the same at every step; the
+        sampler launch is vt_sample_rows_trunc then.
     The histories grow on the device. The device-built masks and adjustments are never read back."""
 
     def __init__(self, a: GenerateArgs, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], V: int):
@@ -281,6 +302,7 @@ class StepPicker:
             self.ban_rows = pack_ban_rows([(h.row_ptr(b), h.lens[b] + st, step_base[st], work_ptr[b], a.ngram, 0, 0, 0)
                                            for st in range(steps) for b in range(B)], dev).view(steps, B, BAN_ROW_BYTES)
             self.ban_ptrs = torch.tensor(work_ptr, dtype=torch.int64).to(dev)
+        self.trunc = pack_trunc_rows([a.trunc] * B, dev) if a.truncated else None
         self.adj_ptrs = self.bias_rows = self.gen_hist = None
         if a.adjusted and steps > 0:
             self.adj = adj = torch.zeros((B, self.V, 2), dtype=torch.float32, device=dev)
@@ -320,7 +342,8 @@ class StepPicker:
             ptrs = None if self.allow_ptrs is None else self.allow_ptrs[step]
         if self.bias_rows is not None:           # the rows' adjustments for this pick, from what they have generated: one launch
             ops.bias_rows(self.bias_rows[step], self.B, self.V)
-        nxt = ops.sample_rows(logits, self.rows[step], return_logprob=bool(a.return_logprobs), _allow_ptrs=ptrs, _adjust_ptrs=self.adj_ptrs)
+        nxt = ops.sample_rows(logits, self.rows[step], return_logprob=bool(a.return_logprobs), _allow_ptrs=ptrs, _adjust_ptrs=self.adj_ptrs,
+                              trunc=self.trunc)
         if a.return_logprobs:
             nxt, lp = nxt
             self._lp.append(lp)

@@ -15,6 +15,9 @@ Additive adjustments: a logit bias and the presence / frequency 
 row's adjustment is V pairs (pre, post) of fp32 built on the DEVICE (struct vt_bias_row, `pack_bias_rows`, ops.bias_rows) and read by
 vt_sample_rows_adj; `LogitAdjust` is what a caller hands to `ServingEngine.submit(..., adjust=)`, `logit_adjust` the host statement of
 the contract.
+
+Truncation: min_p, typical_p, epsilon_cutoff and eta_cutoff are fields of `SamplingParams`; a row's four values are a
+struct vt_trunc_row (`pack_trunc_rows`) that vt_sample_rows_trunc reads.
 """
 from __future__ import annotations
 
@@ -52,6 +55,34 @@ BIAS_ROW_DTYPE = np.dtype({
 })
 BIAS_ROW_BYTES = BIAS_ROW_DTYPE.itemsize
 BIAS_ROWS_MAX_V = 65536            # VT_BIAS_ROWS_MAX_V
+# struct vt_trunc_row: the offsets are part of the ABI (tests/test_trunc_ref_host.py checks them against the header's table)
+TRUNC_ROW_DTYPE = np.dtype({
+    "names": ["min_p", "typical_p", "epsilon_cutoff", "eta_cutoff"],
+    "formats": ["<f4", "<f4", "<f4", "<f4"],
+    "offsets": [0, 4, 8, 12],
+    "itemsize": 16,
+})
+TRUNC_ROW_BYTES = TRUNC_ROW_DTYPE.itemsize
+TRUNC_OFF = (0.0, 1.0, 0.0, 0.0)   # (min_p, typical_p, epsilon_cutoff, eta_cutoff) of a row without truncation: every stage inactive
+
+
+def check_truncation_values(min_p, typical_p, epsilon_cutoff, eta_cutoff, what: str = "sampling") -> None:
+    """min_p in [0, 1] (0 is off), typical_p in (0, 1] (1 is off), epsilon_cutoff and eta_cutoff in [0, 1) (0 is off), all finite: the
+    ranges of transformers' MinP / Typical / Epsilon / Eta warpers with their off values added."""
+    def num(x):
+        return isinstance(x, numbers.Real) and not isinstance(x, bool) and math.isfinite(x)
+    if not num(min_p) or not 0 <= min_p <= 1:
+        raise ValueError(f"{what}: min_p must be a finite number in [0, 1] (0 is off), got {min_p!r}")
+    if not num(typical_p) or not 0 < typical_p <= 1:
+        raise ValueError(f"{what}: typical_p must be a finite number in (0, 1] (1 is off), got {typical_p!r}")
+    for name, x in (("epsilon_cutoff", epsilon_cutoff), ("eta_cutoff", eta_cutoff)):
+        if not num(x) or not 0 <= x < 1:
+            raise ValueError(f"{what}: {name} must be a finite number in [0, 1) (0 is off), got {x!r}")
+
+
+def truncation_active(min_p, typical_p, epsilon_cutoff, eta_cutoff) -> bool:
+    """Is any of the four stages on (the kernel's rule: min_p > 0, the others inside (0, 1))?"""
+    return bool(min_p > 0 or 0 < typical_p < 1 or 0 < epsilon_cutoff < 1 or 0 < eta_cutoff < 1)
 
 
 def check_sampling_values(temperature, top_p, top_k, repetition_penalty, what: str = "sampling") -> None:
@@ -70,8 +101,9 @@ def check_sampling_values(temperature, top_p, top_k, repetition_penalty, what: s
 
 
 @dataclass(frozen=True)
-class SamplingParams:
-    """How ONE request picks its tokens. temperature 0 is greedy; top_k None means config.top_k (default 50, as in `generate`);
+class _SamplingFields:
+    """The dataclass part of SamplingParams (below): its field list is pinned (tests/test_allow_ref_host.py).
+    How ONE request picks its tokens. temperature 0 is greedy; top_k None means config.top_k (default 50, as in `generate`);
     `seed` with the number of tokens generated so far is the whole state of the request's random stream, so its draws do not depend on
     what else is in the batch. logprobs=True collects the chosen token's log-probability per step (ServingEngine.logprobs).
     The last two fields are history-dependent bans: no_repeat_ngram_size (int >= 0, 0 is off: no n-gram of
@@ -112,10 +144,6 @@ class SamplingParams:
                 object.__setattr__(self, name, tuple(ids(c, name) for c in seqs))
         self.validate()
 
-    def replace(self, **changes) -> "SamplingParams":
-        """A copy with some fields changed (dataclasses.replace)."""
-        return dataclasses.replace(self, **changes)
-
     def validate(self) -> None:
         check_sampling_values(self.temperature, self.top_p, self.top_k, self.repetition_penalty, "SamplingParams")
         if not isinstance(self.seed, numbers.Integral) or isinstance(self.seed, bool):
@@ -150,6 +178,65 @@ class SamplingParams:
         if self.top_k is not None:
             return int(self.top_k)
         return int(getattr(config, "top_k", 50) or 0)
+
+
+class SamplingParams(_SamplingFields):
+    """What a caller hands to ServingEngine.submit(..., sampling=): the fields above, and behind them four truncation settings
+     -- min_p (MinPLogitsWarper: q < min_p * max q leaves; 0 is off), typical_p (TypicalLogitsWarper: the mass kept around
+    the entropy; 1 is off), epsilon_cutoff (EpsilonLogitsWarper: q < epsilon leaves; 0 is off) and eta_cutoff (EtaLogitsWarper: q <
+    min(eta, sqrt(eta) * exp(-entropy)) leaves; 0 is off). They run in that order after top-k and top-p inside the sampler kernel
+    (vt_sample_rows_trunc), on a sampled request only; a greedy one ignores them.
+    The four are keyword arguments of the constructor, frozen, validated, and part of ==, hash, repr and replace() like every field --
+    but they are attributes of this subclass, not dataclass fields: the field list is pinned as it is, so dataclasses.replace() would
+    drop them; use SamplingParams.replace()."""
+    TRUNC_NAMES = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
+
+    def __init__(self, *args, min_p: float = 0.0, typical_p: float = 1.0, epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0, **kw):
+        for name, value in zip(self.TRUNC_NAMES, (min_p, typical_p, epsilon_cutoff, eta_cutoff)):
+            object.__setattr__(self, name, value)
+        super().__init__(*args, **kw)            # (its __post_init__ validates: the four are set by then)
+
+    def __setattr__(self, name, value):          # (the frozen base guards its own fields only once it is subclassed)
+        raise dataclasses.FrozenInstanceError(f"cannot assign to field {name!r}")
+
+    def __delattr__(self, name):
+        raise dataclasses.FrozenInstanceError(f"cannot delete field {name!r}")
+
+    def validate(self) -> None:
+        super().validate()
+        check_truncation_values(*self.trunc_row_raw(), what="SamplingParams")
+
+    def trunc_row_raw(self) -> tuple:
+        return tuple(getattr(self, n) for n in self.TRUNC_NAMES)
+
+    def _key(self) -> tuple:
+        return tuple(getattr(self, n) for n in self.__dataclass_fields__) + self.trunc_row_raw()
+
+    def __eq__(self, other):
+        return self._key() == other._key() if other.__class__ is self.__class__ else NotImplemented
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        names = list(self.__dataclass_fields__) + list(self.TRUNC_NAMES)
+        return "SamplingParams(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in names) + ")"
+
+    def replace(self, **changes) -> "SamplingParams":
+        """A copy with some settings changed (dataclasses.replace knows only the dataclass fields)."""
+        kw = {n: getattr(self, n) for n in list(self.__dataclass_fields__) + list(self.TRUNC_NAMES)}
+        kw.update(changes)
+        return SamplingParams(**kw)
+
+    @property
+    def truncated(self) -> bool:
+        """Does the request need vt_sample_rows_trunc (a sampled request with min_p, typical_p, epsilon_cutoff or eta_cutoff on)?"""
+        return self.temperature > 0 and truncation_active(*self.trunc_row_raw())
+
+    @property
+    def trunc_row(self) -> Tuple[float, float, float, float]:
+        """(min_p, typical_p, epsilon_cutoff, eta_cutoff) of the request's vt_trunc_row"""
+        return tuple(float(x) for x in self.trunc_row_raw())
 
 
 def _as_id(t, what: str) -> int:
@@ -296,6 +383,27 @@ def pack_sample_rows(rows: Sequence[tuple], device):
     import torch
     arr = sample_rows_array(rows)
     return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), ROW_BYTES)).to(device)
+
+
+# ---- truncation: struct vt_trunc_row ---------------------------------------------------------------------------------------------------
+def trunc_rows_array(rows: Sequence[Optional[tuple]]) -> np.ndarray:
+    """Host array of vt_trunc_row from one entry per row: (min_p, typical_p, epsilon_cutoff, eta_cutoff), or None for a row without
+    truncation (TRUNC_OFF: every stage inactive). Values are validated here (check_truncation_values)."""
+    arr = np.zeros((len(rows),), dtype=TRUNC_ROW_DTYPE)
+    for i, t in enumerate(rows):
+        t = TRUNC_OFF if t is None else tuple(t)
+        if len(t) != 4:
+            raise ValueError(f"trunc row {i}: expected (min_p, typical_p, epsilon_cutoff, eta_cutoff), got {t!r}")
+        check_truncation_values(*t, what=f"trunc row {i}")
+        arr[i] = tuple(float(x) for x in t)
+    return arr
+
+
+def pack_trunc_rows(rows: Sequence[Optional[tuple]], device):
+    """Device form of `trunc_rows_array(rows)`: a uint8 tensor [len(rows), 16] for ops.sample_rows(..., trunc=)."""
+    import torch
+    arr = trunc_rows_array(rows)
+    return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), TRUNC_ROW_BYTES)).to(device)
 
 
 # ---- history-dependent bans: struct vt_ban_row and the host statement of vt_ban_rows' contract --------------------------------------

@@ -37,7 +37,7 @@ from . import ops
 from .engine import PagedKVCache, SequenceState, llama_forward, pair_lo, parse_kv_cache_dtype
 from .picker import device_history
 from .sampling import (BIAS_ROWS_MAX_V, LogitAdjust, SamplingParams, check_constraints, flatten_ban_seqs, mask_words, pack_ban_rows,
-                       pack_bias_rows, pack_sample_rows, step_allow_mask)
+                       pack_bias_rows, pack_sample_rows, pack_trunc_rows, step_allow_mask)
 
 
 @dataclass
@@ -212,7 +212,11 @@ class ServingEngine:
         A request with `adjust` owns a [V][2] adjustment, its bias and its generated tokens on the device: ONE
         vt_bias_rows launch serves every row that needs a rebuild (a row with penalties at every pick, a bias-only row at its first pick
         only), the launch is vt_sample_rows_adj and the row's adjust pointer names its buffer; all other rows pass NULL. While no
-        active request carries `adjust` the launches are exactly the ones above."""
+        active request carries `adjust` the launches are exactly the ones above.
+        A request whose SamplingParams are `truncated` (min_p, typical_p, epsilon_cutoff or eta_cutoff on a sampled request; DESIGN.md
+        9.9) turns the launch into ONE vt_sample_rows_trunc: its row carries its four values, every other row an all-inactive entry,
+        which the kernel treats bit for bit as vt_sample_rows_adj does. While no active request is truncated the launches are exactly
+        the ones above."""
         if reqs is None or all(r.sampling is None and r.adjust is None for r in reqs):
             if self.do_sample:
                 return ops.sample_top_p(logits, self.temperature, self.top_p, self.seed, self._step)
@@ -279,7 +283,11 @@ class ServingEngine:
             if bias_rows:
                 ops.bias_rows(pack_bias_rows(bias_rows, dev), len(bias_rows), V)
             adj = [r.adj_buf for r in reqs]
-        res = ops.sample_rows(logits, pack_sample_rows(rows, logits.device), return_logprob=want_lp, allow=allow, adjust=adj)
+        trunc = None
+        if any(r.sampling is not None and r.sampling.truncated for r in reqs):
+            trunc = pack_trunc_rows([r.sampling.trunc_row if (r.sampling is not None and r.sampling.truncated) else None for r in reqs],
+                                    logits.device)
+        res = ops.sample_rows(logits, pack_sample_rows(rows, logits.device), return_logprob=want_lp, allow=allow, adjust=adj, trunc=trunc)
         ids, lp = res if want_lp else (res, None)
         for i, r in enumerate(reqs):
             if r.sampling is not None and r.sampling.logprobs:
