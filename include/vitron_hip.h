@@ -98,6 +98,8 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
  * that forward to launches vt_vit_forward and vt_region_forward already make; no struct and no existing signature changes. */
 /* 114 also carries vt_sample_rows_trunc and struct vt_trunc_row WITHOUT a bump: one new symbol and one new struct; struct vt_sample_row,
  * vt_sample_rows, vt_sample_rows_allow and vt_sample_rows_adj do not change. */
+/* 114 also carries vt_logprob_rows WITHOUT a bump: one new symbol, no struct and no existing signature changes; the samplers and
+ * vt_beam_step do not change. */
 #define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
@@ -569,6 +571,41 @@ size_t vt_beam_step_scratch_bytes(int groups, int beams_in, int n_out);
 int vt_beam_step(const float* logits, int ldl, int V, int groups, int beams_in, const float* beam_scores /* [groups*beams_in] */,
                  int n_out, float* out_scores, int* out_tokens, int* out_beams /* each [groups][n_out] */,
                  void* scratch, size_t scratch_bytes, void* stream);
+
+/* LOG-PROBABILITIES OF LOGIT ROWS (the role of torch.log_softmax + torch.topk + a gather on rows read back to the host).
+ *
+ * vt_logprob_rows: per row r of `logits` (fp32, row stride ldl >= V), over the RAW row -- no penalty, temperature or mask, as the samplers'
+ * logprob output -- in one launch of one 1024-thread block per row; `logits` is only read:
+ *     lse[r]         = m + logf(sum_i expf(x_i - m)),   m = max_i x_i,   all in fp32  (vt_sample_rows' expression; the summation order may
+ *                      differ from the sampler's, so the two agree within their two bounds, not bit for bit)
+ *     a token's log-probability is  x_t - lse[r]
+ *     ORDER            a larger RAW logit comes first, exact ties go to the lower index. Selection compares x, never x - lse: it is exact.
+ *     top_ids[r][p]  = the p-th token in that order, p < n_top;   top_lp[r][p] = its log-probability
+ *     target_lp[r]   = the log-probability of target[r];   target_rank[r] = 1 + the number of tokens strictly ahead of target[r] in the
+ *                      order (exact integer arithmetic; the best token has rank 1)
+ * target == NULL, or target[r] outside [0, V): target_lp[r] = NaN, target_rank[r] = 0, and row[target[r]] is not read; when neither the
+ * top lists (n_top == 0) nor lse are asked for either, the row is not read at all.
+ * Edge rules:
+ *   * a NaN logit is never taken and never counted as ahead. A row that holds one has lse = NaN, hence NaN log-probabilities everywhere; its
+ *     top_ids still follow the order over the values that are not NaN. A target whose own logit is NaN stands behind every value that is not
+ *     a NaN: its rank is 1 + their number.
+ *   * -inf logits are ordinary candidates with log-probability -inf (+inf likewise: the row's lse is then +inf or NaN as IEEE gives it).
+ *   * fewer than n_top takeable values (V < n_top, or NaNs): the remaining slots hold id -1 and a NaN log-probability.
+ *   * total: no input value reaches an index unchecked, and nothing but the outputs named here is written.
+ * lse, target_lp, target_rank may each be NULL (not written); top_ids / top_lp are [rows][n_top] and may be NULL when n_top == 0.
+ * Refused with VT_STATUS_ARG and a message before any launch: logits == NULL, rows <= 0, V <= 0, V > VT_LOGPROB_MAX_V, ldl < V, n_top outside
+ * [0, VT_LOGPROB_MAX_TOP], n_top > 0 with top_ids or top_lp NULL, n_top == 0 with lse, target_lp and target_rank all NULL, a pointer that is
+ * not 4-byte aligned.
+ * Two forms, chosen by the launcher: V <= 32 * 1024 with a 16-byte aligned base and ldl % 4 == 0 -- the row is read once, 32 values per
+ * thread, and everything runs over registers; any other V or alignment -- a thread re-reads its part of the row (L2) for the sum, the count
+ * and whenever it looks for its next candidate. No scratch memory and no workspace in either form.
+ * 114 carries this entry point WITHOUT a bump: one new symbol, nothing existing changes (see the note at VT_ABI_VERSION). */
+#define VT_LOGPROB_MAX_TOP 20
+#define VT_LOGPROB_MAX_V (1 << 30)
+int vt_logprob_rows(const float* logits, int rows, int V, int ldl,
+                    const int* target /* DEVICE int32 [rows], or NULL */, int n_top /* 0 .. VT_LOGPROB_MAX_TOP */,
+                    float* lse /* [rows] or NULL */, float* target_lp /* [rows] or NULL */, int* target_rank /* [rows] or NULL */,
+                    int* top_ids /* [rows][n_top] */, float* top_lp /* [rows][n_top] */, void* stream);
 
 /* vt_kv_copy_pages: for every layer and every i < n, page src_pages[i] is copied onto page dst_pages[i] in both the K pool and the V^T
  * pool (k / vt: [num_layers][num_pages][page_bytes] each). It counts in bytes -- page_bytes = heads * 64 * head_dim * element size, a

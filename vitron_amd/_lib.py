@@ -118,6 +118,7 @@ SIGNATURES = {
     "vt_beam_step_scratch_bytes": (_sz, [_i, _i, _i]),
     "vt_beam_step": (_i, [vp, _i, _i, _i, _i, vp, _i, vp, vp, vp, vp, _sz, vp]),
     "vt_kv_copy_pages": (_i, [vp, vp, _i, _i, _sz, vp, vp, _i, vp]),
+    "vt_logprob_rows": (_i, [vp, _i, _i, _i, vp, _i, vp, vp, vp, vp, vp, vp]),
     "vt_ban_rows": (_i, [vp, _i, _i, vp]),
     "vt_bias_rows": (_i, [vp, _i, _i, vp]),
     "vt_projector_workspace_bytes": (_sz, [_i, _i]),

@@ -493,6 +493,12 @@ int vt_beam_step(const float* logits, int ldl, int V, int groups, int beams_in, 
                              scratch_bytes, S(stream));
 }
 
+// ---- log-probabilities of logit rows (vt_logprob.hip) -----------------------------------------------------------------
+int vt_logprob_rows(const float* logits, int rows, int V, int ldl, const int* target, int n_top, float* lse, float* target_lp,
+                    int* target_rank, int* top_ids, float* top_lp, void* stream) {
+  return vt_logprob_rows_launch(logits, rows, V, ldl, target, n_top, lse, target_lp, target_rank, top_ids, top_lp, S(stream));
+}
+
 int vt_kv_copy_pages(void* k, void* vt, int num_layers, int num_pages, size_t page_bytes, const int* src_pages, const int* dst_pages,
                      int n, void* stream) {
   return vt_kv_copy_pages_launch(k, vt, num_layers, num_pages, page_bytes, src_pages, dst_pages, n, S(stream));

@@ -274,6 +274,10 @@ int vt_beam_step_launch(const float* logits, int ldl, int V, int groups, int bea
 int vt_kv_copy_pages_launch(void* k, void* vt, int num_layers, int num_pages, size_t page_bytes, const int* src_pages,
                             const int* dst_pages, int n, hipStream_t s);
 
+// ---- vt_logprob.hip ------------------------------------------------------------------------------
+int vt_logprob_rows_launch(const float* logits, int rows, int V, int ldl, const int* target, int n_top, float* lse, float* target_lp,
+                           int* target_rank, int* top_ids, float* top_lp, hipStream_t s);
+
 // ---- vt_ban.hip -----------------------------------------------------------------------------------
 int vt_ban_rows_launch(const vt_ban_row* rows, int n_rows, int V, hipStream_t s);
 

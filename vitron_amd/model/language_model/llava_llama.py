@@ -469,7 +469,7 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                  return_logits=False, padded_batch=False, repetition_penalty=1.0, return_logprobs=False, suppress_tokens=None,
                  begin_suppress_tokens=None, min_new_tokens=None, bad_words_ids=None, allowed_token_ids=None, num_return_sequences=1,
                  length_penalty=1.0, early_stopping=False, no_repeat_ngram_size=None, sequence_bias=None, presence_penalty=0.0,
-                 frequency_penalty=0.0, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, **kwargs):
+                 frequency_penalty=0.0, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, top_logprobs=0, **kwargs):
         """repetition_penalty (RepetitionPenaltyLogitsProcessor; 1.0 is off) and return_logprobs: with both at their defaults a step
         launches what it always did (vt_argmax / vt_sample_top_p). Otherwise every step is ONE vt_sample_rows launch (row b: stream = b,
         counter = step -- today's draws) whose penalty history -- the sample's non-negative prompt ids plus what it has generated -- lives
@@ -516,7 +516,13 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         prefix. Refused with NotImplementedError before any page is taken: do_sample, padded_batch, repetition_penalty != 1, every
         constraint argument above (no_repeat_ngram_size included), stopping_criteria, return_logits / return_logprobs, num_beams > 16, and a candidate list
         (max(2, 1 + number of EOS ids) * num_beams per step, as in transformers) beyond the vocabulary or beyond vt_beam_step's 32.
-        num_beams = 1 runs the code it always ran."""
+        num_beams = 1 runs the code it always ran.
+        top_logprobs = N in [1, 20] (0 is off): after the other outputs a dict is returned -- top_ids int32 [B, n_new, N]
+        and top_logprobs fp32 [B, n_new, N], every step's N most likely tokens of the RAW distribution (larger logit first, ties by the
+        lower id) with their log-probabilities, and rank int32 [B, n_new], the emitted id's rank in that order (1 is the most likely).
+        Every pick is followed by ONE vt_logprob_rows launch that writes into buffers allocated before the loop; the pick itself, the
+        ids and return_logprobs are what they are without it. For a row that has finished the values are those of the id it would have
+        emitted, as with return_logprobs. Refused with NotImplementedError: num_beams > 1, padded_batch; ValueError outside [0, 20]."""
         from ...picker import StepPicker, resolve_generate_args
         a = resolve_generate_args(
             self.config, input_ids.shape[1], do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k,
@@ -527,7 +533,7 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
             allowed_token_ids=allowed_token_ids, num_return_sequences=num_return_sequences, length_penalty=length_penalty,
             early_stopping=early_stopping, no_repeat_ngram_size=no_repeat_ngram_size, sequence_bias=sequence_bias,
             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p, typical_p=typical_p,
-            epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff)
+            epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, top_logprobs=top_logprobs)
         dev = self.device
         input_ids = input_ids.to(dev)
         B, L0 = input_ids.shape
@@ -594,12 +600,155 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         finally:
             self._leave_prefix(sig, seqs, out_host[0, L0:n_out])
         out = out_host[:, :n_out].to(dev)
-        if a.return_logprobs:
-            lps = picker.logprobs(n_out - L0)
-            return (out, all_logits, lps) if a.return_logits else (out, lps)
-        if a.return_logits:
-            return out, all_logits
-        return out
+        res = (out,) + ((all_logits,) if a.return_logits else ()) + ((picker.logprobs(n_out - L0),) if a.return_logprobs else ()) \
+            + ((picker.top(n_out - L0),) if a.top_logprobs else ())
+        return res if len(res) > 1 else out
+
+    # ---- log-probabilities of GIVEN tokens -----------------------------------------------------------
+    @torch.no_grad()
+    def score(self, input_ids, images=None, regions=None, top_logprobs=0, return_logits=False, attention_mask=None,
+              packed_prefill=False):
+        """The log-probability and the rank of every token of `input_ids` given what stands before it -- prompt scoring.
+        input_ids: LongTensor [B, L] (or [L]) with the <image> / <objs> sentinels as generate() takes them, right-padded where
+        attention_mask is 0; or a list of B 1-D id tensors of any lengths (padded here). images / regions: as for generate().
+        Towers, splice and decoder prefill run as generate()'s prefill does (through the encoded-image cache); llama_forward's logit
+        rows are the spliced rows whose NEXT row is a text token (scoring.score_targets: the rule, decided from the splice plan), each
+        with that token as its target, followed by ONE vt_logprob_rows launch over the rows of the whole batch.
+        packed_prefill=False (default): every sequence of a batch gets a decoder pass of its own, so its numbers are those of the
+        same sequence scored alone, bit for bit, whatever else is in the batch (ServingEngine's default admission makes the same
+        choice). True: ONE packed pass over all sequences, as generate() prefills a batch -- larger GEMMs; the logits then differ from
+        a solo call's by 16-bit GEMM noise (other tiles), as with ServingEngine(batch_prefill=True). Returns a dict of
+        device tensors, one value per position of input_ids:
+          "logprobs" fp32 [B, L], "rank" int32 [B, L] (1: the most likely token). A position without a target -- the first token, an
+          <image> / <objs> sentinel, padding, a token truncated away -- holds NaN / 0;
+          with top_logprobs = N in [1, 20]: "top_ids" int32 [B, L, N] and "top_logprobs" fp32 [B, L, N], the N most likely tokens at that
+          position (larger logit first, ties by the lower id) -- -1 / NaN where there is no target;
+          with return_logits: "logits" fp32 [n, V], the rows that were scored, and "logit_index" int64 [n, 3]: (sample, position of the
+          scored token in input_ids, spliced row that was read) of each.
+        The call takes its KV pages privately -- from the pool's free pages when they suffice, else from a pool of its own that lives for
+        the call -- and gives them back before it returns: the pool, the kept conversation (the KV prefix of generate()) and the
+        encoded-image cache's contents other than newly encoded items are what they were."""
+        from ...sampling import check_top_logprobs
+        from ...scoring import score_targets
+        check_top_logprobs(top_logprobs, "score")
+        n_top = int(top_logprobs)
+        dev = self.device
+        if isinstance(input_ids, (list, tuple)):
+            if attention_mask is not None:
+                raise ValueError("score: a list of sequences brings its own lengths; attention_mask is for a padded tensor")
+            seqs_in = [torch.as_tensor(t).reshape(-1).to(torch.long) for t in input_ids]
+            if not seqs_in or any(t.numel() == 0 for t in seqs_in):
+                raise ValueError("score: every sequence needs at least one token")
+            L = max(int(t.numel()) for t in seqs_in)
+            input_ids = torch.zeros((len(seqs_in), L), dtype=torch.long)
+            attention_mask = torch.zeros((len(seqs_in), L), dtype=torch.long)
+            for b, t in enumerate(seqs_in):
+                input_ids[b, :t.numel()] = t.cpu()
+                attention_mask[b, :t.numel()] = 1
+        elif input_ids.dim() == 1:
+            input_ids = input_ids.unsqueeze(0)
+        input_ids = input_ids.to(dev)
+        B, L = input_ids.shape
+        self._last_plan = None
+        embeds, mask_host, spliced = self._embed_prompt(input_ids, attention_mask, images, regions, use_vis_cache=True)
+        S = embeds.shape[1]
+        flat, flat_lo, lens, _ = self._pack_rows(embeds, mask_host)
+        ids_host = input_ids.cpu().tolist()
+        am_host = attention_mask.to(torch.int32).cpu().tolist() if attention_mask is not None else [[1] * L] * B
+        plan = self._last_plan if spliced else None
+        logit_rows, targets, where = [], [], []       # packed row read, its target, (sample, position, spliced row)
+        per_seq = []                                  # (first packed row, rows, the sequence's own rows to read)
+        row0 = 0
+        for b in range(B):
+            pos_of = [j for j in range(L) if am_host[b][j]]
+            ids_b = [ids_host[b][j] for j in pos_of]
+            kinds = [0] * lens[b] if plan is None else [int(plan[b, s, 0]) for s in range(S) if mask_host[b][s]]
+            rows_b, tg_b, at_b = score_targets(ids_b, kinds)
+            logit_rows += [row0 + r for r in rows_b]
+            targets += tg_b
+            where += [(b, pos_of[j], r) for j, r in zip(at_b, rows_b)]
+            per_seq.append((row0, lens[b], rows_b))
+            row0 += lens[b]
+        res = {"logprobs": torch.full((B, L), float("nan"), dtype=torch.float32, device=dev),
+               "rank": torch.zeros((B, L), dtype=torch.int32, device=dev)}
+        if n_top:
+            res["top_ids"] = torch.full((B, L, n_top), -1, dtype=torch.int32, device=dev)
+            res["top_logprobs"] = torch.full((B, L, n_top), float("nan"), dtype=torch.float32, device=dev)
+        if not logit_rows:
+            if return_logits:
+                res["logits"] = torch.empty((0, int(self.config.vocab_size)), dtype=torch.float32, device=dev)
+                res["logit_index"] = torch.empty((0, 3), dtype=torch.long)
+            return res
+        pages = [(l + 63) // 64 + 1 for l in lens]
+        need = sum(pages) if packed_prefill else max(pages)
+        kv = self.kv if (self.kv is not None and self.kv.kv_dtype == self._kv_format() and len(self.kv.free) >= need) \
+            else self.new_kv_pool(need)
+        llama = self.model.llama
+
+        def prefill(rows_from, n_rows, q_lens, read):
+            seqs = [SequenceState() for _ in q_lens]
+            try:
+                return llama_forward(llama, kv, seqs, flat[rows_from:rows_from + n_rows], q_lens, logit_rows=read,
+                                     embeds_lo=None if flat_lo is None else flat_lo[rows_from:rows_from + n_rows])
+            finally:                                  # the pages go back whatever happened
+                for s in seqs:
+                    if s.pages:
+                        kv.release(s.pages)
+                    s.pages, s.length = [], 0
+        if packed_prefill or B == 1:
+            logits = prefill(0, int(sum(lens)), lens, logit_rows)                                        # [n, V]
+        else:
+            logits = torch.cat([prefill(r0, l, [l], rows_b) for r0, l, rows_b in per_seq if rows_b], 0)
+        got = ops.logprob_rows(logits, torch.tensor(targets, dtype=torch.int32).to(dev), n_top, return_rank=True)
+        flat_at = torch.tensor([b * L + j for b, j, _ in where], dtype=torch.long).to(dev)
+        res["logprobs"].view(-1).index_copy_(0, flat_at, got["logprob"])
+        res["rank"].view(-1).index_copy_(0, flat_at, got["rank"])
+        if n_top:
+            res["top_ids"].view(B * L, n_top).index_copy_(0, flat_at, got["top_ids"])
+            res["top_logprobs"].view(B * L, n_top).index_copy_(0, flat_at, got["top_logprobs"])
+        if return_logits:
+            res["logits"] = logits
+            res["logit_index"] = torch.tensor(where, dtype=torch.long)
+        return res
+
+    @torch.no_grad()
+    def rank_options(self, prompt_ids, options, images=None, regions=None, normalize="sum", packed_prefill=False):
+        """Rank the answer options of a multiple-choice question by the log-probability the model gives their tokens behind the prompt.
+        prompt_ids: 1-D ids (sentinels as for generate()); options: non-empty id sequences; images / regions: the prompt's own (one
+        entry per <image> of the prompt), shared by all options. prompt + option is built for every option and the lot is scored as
+        ONE batch through score() (packed_prefill: as there -- by default an option's score does not depend on which other options
+        stand beside it); the image is encoded once: it enters the encoded-image cache with the first option and every
+        other option finds it there. An option's score is the sum of its tokens' log-probabilities (normalize="sum") or their mean
+        ("mean"). Returns (order, scores): the option indices by descending score -- ties keep option order -- and the fp64 scores
+        in option order. (Every option prefills the prompt again: sharing the prompt's KV pages is left open)"""
+        from ...scoring import option_score, rank_order
+        if normalize not in ("sum", "mean"):
+            raise ValueError(f"rank_options: normalize must be 'sum' or 'mean', got {normalize!r}")
+        prompt = torch.as_tensor(prompt_ids).reshape(-1).to(torch.long).cpu()
+        opts = [torch.as_tensor(o).reshape(-1).to(torch.long).cpu() for o in options]
+        if not opts or any(o.numel() == 0 for o in opts):
+            raise ValueError("rank_options: at least one option, and no empty one")
+        if any(int(o.min()) < 0 for o in opts):
+            raise ValueError("rank_options: an option holds a sentinel; options are text")
+        n = len(opts)
+        imgs = regs = None
+        if images is not None:
+            one = list(images)
+            if len(one) and n > 1:       # encode the prompt's items ONCE: the first option alone fills the cache, the batch then hits it
+                self._prime_visual_cache(prompt, one, regions)
+            imgs = one * n
+            regs = None if regions is None else list(regions) * n
+        out = self.score([torch.cat([prompt, o]) for o in opts], images=imgs, regions=regs, packed_prefill=packed_prefill)
+        lp = out["logprobs"].double().cpu()
+        P = int(prompt.numel())
+        scores = [option_score(lp[i, P:P + int(o.numel())].tolist(), normalize) for i, o in enumerate(opts)]
+        return rank_order(scores), torch.tensor(scores, dtype=torch.float64)
+
+    def _prime_visual_cache(self, prompt, images, regions):
+        """Run the prompt's images / clips through the towers as a batch of ONE sample, so that they sit in the encoded-image cache."""
+        if int(getattr(self.config, "vis_cache_entries", 16)) <= 0:
+            return
+        self._embed_prompt(prompt.unsqueeze(0).to(self.device), None, images, regions, use_vis_cache=True)
 
     # ---- the phases of generate() -------------------------------------------------------------------------------
     def _embed_prompt(self, input_ids, attention_mask, images, regions, use_vis_cache):

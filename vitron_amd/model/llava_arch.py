@@ -262,6 +262,7 @@ class LlavaMetaForCausalLM:
             ids_host, am_host, flat_blocks, flat_regs, getattr(self.config, "tokenizer_model_max_length", None),
             getattr(self.config, "tokenizer_padding_side", "right"))
         B, S = plan.shape[0], plan.shape[1]
+        self._last_plan = plan                    # host copy for score() (which rows are text, visual, region)
         tok_rows = plan[..., 1][plan[..., 0] == KIND_TOKEN]
         n_embed = self.get_model().llama.embed_rows
         if tok_rows.size and (int(tok_rows.min()) < 0 or int(tok_rows.max()) >= n_embed):   # nn.Embedding would raise

@@ -772,6 +772,74 @@ def beam_step(logits: torch.Tensor, beam_scores: torch.Tensor, groups: int, beam
     return res[0].view(torch.float32), res[1], res[2]
 
 
+LOGPROB_MAX_TOP = 20               # VT_LOGPROB_MAX_TOP
+
+
+def logprob_rows(logits: torch.Tensor, targets: Optional[torch.Tensor] = None, n_top: int = 0, return_rank: bool = False,
+                 return_lse: bool = False, out: Optional[dict] = None) -> dict:
+    """Log-probabilities of RAW logit rows on the device, one launch; see vt_logprob_rows in include/vitron_hip.h. logits: fp32 [rows, V]
+    with contiguous rows (row stride free). targets: int32 [rows] on the logits' device (an id outside [0, V) marks a row without a
+    target), or None. Returns a dict of device tensors holding what was asked for:
+      "logprob" fp32 [rows]           the targets' log-probabilities (NaN where a row has no target)         -- with targets
+      "rank"    int32 [rows]          1 + the number of tokens strictly ahead of the target (0: no target)    -- with targets and return_rank
+      "lse"     fp32 [rows]           the rows' log-sum-exp                                                   -- with return_lse
+      "top_ids" int32 [rows, n_top], "top_logprobs" fp32 [rows, n_top]   larger logit first, ties by the lower id; (-1, NaN) where a
+                                      row holds fewer than n_top takeable values                              -- with n_top > 0
+    out: a dict with preallocated tensors under those keys (contiguous, of exactly those shapes and dtypes, on the logits' device --
+    e.g. step s of [T, rows, n_top] buffers). Its keys then SAY what is computed -- the flags are not consulted; n_top > 0 needs both
+    top keys -- and the kernel writes into them: nothing is allocated and nothing waits. Without `out` everything comes from ONE
+    allocation (also returned as "packed", int32: the planes logprob, rank, lse, top_ids, top_logprobs in that order, those asked
+    for), so a caller can read all of it back with one copy."""
+    lib = _lib.load_any()
+    _chk_rows(logits, torch.float32, "logprob_rows.logits")
+    rows, V = logits.shape
+    n_top = int(n_top)
+    if not 0 <= n_top <= LOGPROB_MAX_TOP:
+        raise _lib.VitronHipError(f"logprob_rows: n_top={n_top} (0 <= n_top <= {LOGPROB_MAX_TOP})")
+    dev = logits.device
+    if targets is not None:
+        _chk(targets, torch.int32, "logprob_rows.targets")
+        if targets.device != dev or targets.numel() != rows:
+            raise _lib.VitronHipError(f"logprob_rows.targets: expected int32 [{rows}] on the logits' device")
+    out = {} if out is None else out
+    unknown = set(out) - {"logprob", "rank", "lse", "top_ids", "top_logprobs"}
+    if unknown:
+        raise _lib.VitronHipError(f"logprob_rows.out: unknown key(s) {sorted(unknown)}")
+    if out:
+        want = {k: k in out for k in ("logprob", "rank", "lse")}
+        want["top_ids"] = want["top_logprobs"] = n_top > 0
+    else:
+        want = {"logprob": targets is not None, "rank": targets is not None and bool(return_rank), "lse": bool(return_lse),
+                "top_ids": n_top > 0, "top_logprobs": n_top > 0}
+    spec = {"logprob": ((rows,), torch.float32), "rank": ((rows,), torch.int32), "lse": ((rows,), torch.float32),
+            "top_ids": ((rows, n_top), torch.int32), "top_logprobs": ((rows, n_top), torch.float32)}
+    if not any(want.values()):
+        raise _lib.VitronHipError("logprob_rows: nothing asked for (no targets, n_top = 0, no lse)")
+    res = {}
+    for key, t in out.items():
+        shape, dtype = spec[key]
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.VitronHipError(f"logprob_rows.out[{key!r}]: expected a contiguous {dtype} tensor of shape {shape} on the logits' device")
+        if want[key]:
+            res[key] = t
+    missing = [k for k in spec if want[k] and k not in res]
+    if out and missing:
+        raise _lib.VitronHipError(f"logprob_rows.out: n_top={n_top} needs preallocated {missing}")
+    if missing:                                  # (no `out`: everything in one allocation)
+        sizes = [rows * (n_top if k.startswith("top_") else 1) for k in missing]
+        buf = torch.empty((sum(sizes),), device=dev, dtype=torch.int32)
+        at = 0
+        for k, n in zip(missing, sizes):
+            shape, dtype = spec[k]
+            res[k] = buf[at:at + n].view(dtype).view(shape)
+            at += n
+        res["packed"] = buf
+    _lib.check(lib.vt_logprob_rows(_p(logits), rows, V, logits.stride(0), _p(targets), n_top, _p(res.get("lse")), _p(res.get("logprob")),
+                                   _p(res.get("rank")), _p(res.get("top_ids")), _p(res.get("top_logprobs")), _stream()),
+               "vt_logprob_rows", lib)
+    return res
+
+
 def kv_copy_pages(kv, src_pages, dst_pages) -> None:
     """Copy page src_pages[i] onto page dst_pages[i] of a PagedKVCache, in every layer and both pools (vt_kv_copy_pages; either pool
     format). The ids are host sequences: each is checked against the pool here, and no destination may also be a source."""

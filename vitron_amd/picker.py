@@ -19,7 +19,7 @@ import torch
 from . import ops
 from .engine import parse_kv_cache_dtype
 from .sampling import (BAN_ROW_BYTES, BIAS_ROW_BYTES, BIAS_ROWS_MAX_V, ROW_BYTES, allow_mask, check_penalties, check_sampling_values,
-                       check_truncation_values, mask_words, normalise_bias, pack_ban_rows, pack_bias_rows, pack_sample_rows,
+                       check_top_logprobs, check_truncation_values, mask_words, normalise_bias, pack_ban_rows, pack_bias_rows, pack_sample_rows,
                        pack_trunc_rows, truncation_active)
 
 
@@ -54,6 +54,7 @@ class GenerateArgs:
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
     trunc: Tuple[float, float, float, float] = (0.0, 1.0, 0.0, 0.0)   # (min_p, typical_p, epsilon_cutoff, eta_cutoff); off when greedy
+    top_logprobs: int = 0                        # N > 0: every step's N most likely tokens and the chosen token's rank (vt_logprob_rows)
 
     @property
     def constrained(self) -> bool:
@@ -106,12 +107,14 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
                           eos_token_id, pad_token_id, num_beams, seed, return_logits, padded_batch, repetition_penalty, return_logprobs,
                           suppress_tokens, begin_suppress_tokens, min_new_tokens, bad_words_ids, allowed_token_ids, num_return_sequences,
                           length_penalty, early_stopping, no_repeat_ngram_size, sequence_bias=None, presence_penalty=0.0,
-                          frequency_penalty=0.0, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None) -> GenerateArgs:
+                          frequency_penalty=0.0, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None,
+                          top_logprobs=0) -> GenerateArgs:
     """generate()'s keyword arguments as a GenerateArgs. Raises, in this order and before any device work: the argument errors of
     num_beams / no_repeat_ngram_size, everything a beam call refuses, the padded_batch refusals that depend on arguments alone, the
     sampling values, the constraint arguments, a step the constraints leave no token for, constraints with padded_batch, the values of
     sequence_bias / presence_penalty / frequency_penalty, those three with padded_batch, the values of min_p / typical_p / epsilon_cutoff /
-    eta_cutoff (None is off, as in GenerationConfig; ignored without do_sample), those four with padded_batch. The sample seed
+    eta_cutoff (None is off, as in GenerationConfig; ignored without do_sample), those four with padded_batch, the value of top_logprobs
+    (an int in [0, 20]; a beam call refuses it with its other optional arguments), top_logprobs with padded_batch. The sample seed
     is drawn from torch's global CPU generator (so torch.manual_seed makes sampling reproducible, as with GenerationMixin.sample) and
     only when sampling without `seed`, after the beam refusals: greedy and refused calls leave the RNG state alone."""
     num_beams = int(num_beams)
@@ -142,7 +145,8 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
                                                   ("frequency_penalty", frequency_penalty)) if value)
         + tuple(f"{name}=..." for name, value, off in (("min_p", min_p, 0.0), ("typical_p", typical_p, 1.0),
                                                        ("epsilon_cutoff", epsilon_cutoff, 0.0), ("eta_cutoff", eta_cutoff, 0.0))
-                if value is not None and value != off))
+                if value is not None and value != off)
+        + (("top_logprobs=...",) if top_logprobs else ()))
     if num_beams > 1:
         check_beam_arguments(a, int(config.vocab_size))
     elif a.num_return_sequences != 1:
@@ -194,6 +198,11 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
     if a.truncated and padded_batch:
         raise NotImplementedError("generate(padded_batch=True) does not take min_p / typical_p / epsilon_cutoff / eta_cutoff; use the "
                                   "default packed batch")
+    check_top_logprobs(top_logprobs, "generate")
+    if top_logprobs and padded_batch:
+        raise NotImplementedError("generate(padded_batch=True) does not take top_logprobs; use the default packed batch")
+    if top_logprobs:
+        a = dataclasses.replace(a, top_logprobs=int(top_logprobs))
     return a
 
 
@@ -270,7 +279,10 @@ class StepPicker:
         buffers never change and are built by ONE launch here, before the prefill;
       - with min_p / typical_p / epsilon_cutoff / eta_cutoff: the B vt_trunc_row entries, the same at every step; the
         sampler launch is vt_sample_rows_trunc then.
-    The histories grow on the device. The device-built masks and adjustments are never read back."""
+    The histories grow on the device. The device-built masks and adjustments are never read back.
+    With top_logprobs = N > 0, in every mode: the [steps, B, N] id and log-probability buffers and the [steps, B] rank
+    buffer are allocated here, and every pick is followed by ONE ops.logprob_rows launch over the step's RAW logits with the picked ids
+    as targets, which writes step `step` of them -- no allocation, no upload, no host wait. The pick itself is the launch it was."""
 
     def __init__(self, a: GenerateArgs, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], V: int):
         self.a = a
@@ -279,6 +291,11 @@ class StepPicker:
         self.device = input_ids.device
         self.mode = "rows" if a.per_row else ("top_p" if a.do_sample else "argmax")
         self._lp: List[torch.Tensor] = []
+        if a.top_logprobs and a.max_new_tokens > 0:
+            n = a.max_new_tokens
+            self.top_ids = torch.empty((n, B, a.top_logprobs), dtype=torch.int32, device=self.device)
+            self.top_lp = torch.empty((n, B, a.top_logprobs), dtype=torch.float32, device=self.device)
+            self.top_rank = torch.empty((n, B), dtype=torch.int32, device=self.device)
         if self.mode != "rows":
             return
         dev, steps = self.device, a.max_new_tokens
@@ -330,6 +347,13 @@ class StepPicker:
             raise RuntimeError(f"generate: the logit adjustments were built for V = {self.V}, the logits have {logits.shape[1]} columns")
 
     def pick(self, step: int, logits: torch.Tensor) -> torch.Tensor:
+        nxt = self._pick_ids(step, logits)
+        if self.a.top_logprobs:                  # the distribution behind the pick: RAW logits, the picked ids as targets
+            ops.logprob_rows(logits, nxt, self.a.top_logprobs, out={"rank": self.top_rank[step], "top_ids": self.top_ids[step],
+                                                                    "top_logprobs": self.top_lp[step]})
+        return nxt
+
+    def _pick_ids(self, step: int, logits: torch.Tensor) -> torch.Tensor:
         a = self.a
         if self.mode == "argmax":
             return ops.argmax(logits)
@@ -360,3 +384,14 @@ class StepPicker:
         if not self._lp:
             return torch.empty((self.B, 0), dtype=torch.float32, device=self.device)
         return torch.stack(self._lp, 1)[:, :n]
+
+    def top(self, n: int) -> dict:
+        """What the first n picks' ops.logprob_rows launches wrote: top_ids int32 [B, n, N], top_logprobs fp32 [B, n, N], rank int32
+        [B, n] (the picked id's rank in the RAW order)."""
+        N = self.a.top_logprobs
+        if not hasattr(self, "top_ids"):
+            return {"top_ids": torch.empty((self.B, 0, N), dtype=torch.int32, device=self.device),
+                    "top_logprobs": torch.empty((self.B, 0, N), dtype=torch.float32, device=self.device),
+                    "rank": torch.empty((self.B, 0), dtype=torch.int32, device=self.device)}
+        return {"top_ids": self.top_ids[:n].permute(1, 0, 2).contiguous(), "top_logprobs": self.top_lp[:n].permute(1, 0, 2).contiguous(),
+                "rank": self.top_rank[:n].permute(1, 0).contiguous()}

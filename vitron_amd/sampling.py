@@ -18,6 +18,9 @@ the contract.
 
 Truncation: min_p, typical_p, epsilon_cutoff and eta_cutoff are fields of `SamplingParams`; a row's four values are a
 struct vt_trunc_row (`pack_trunc_rows`) that vt_sample_rows_trunc reads.
+
+Top-N log-probabilities: `SamplingParams(top_logprobs=N)` asks for the N most likely tokens and the chosen token's rank
+at every generated token; they come from one vt_logprob_rows launch behind the pick and need no struct here.
 """
 from __future__ import annotations
 
@@ -78,6 +81,12 @@ def check_truncation_values(min_p, typical_p, epsilon_cutoff, eta_cutoff, what: 
     for name, x in (("epsilon_cutoff", epsilon_cutoff), ("eta_cutoff", eta_cutoff)):
         if not num(x) or not 0 <= x < 1:
             raise ValueError(f"{what}: {name} must be a finite number in [0, 1) (0 is off), got {x!r}")
+
+
+def check_top_logprobs(n, what: str = "sampling") -> None:
+    """top_logprobs is an int in [0, 20] (0 is off; 20 is VT_LOGPROB_MAX_TOP)."""
+    if not isinstance(n, numbers.Integral) or isinstance(n, bool) or not 0 <= n <= 20:
+        raise ValueError(f"{what}: top_logprobs must be an int in [0, 20] (0 is off), got {n!r}")
 
 
 def truncation_active(min_p, typical_p, epsilon_cutoff, eta_cutoff) -> bool:
@@ -188,12 +197,18 @@ class SamplingParams(_SamplingFields):
     (vt_sample_rows_trunc), on a sampled request only; a greedy one ignores them.
     The four are keyword arguments of the constructor, frozen, validated, and part of ==, hash, repr and replace() like every field --
     but they are attributes of this subclass, not dataclass fields: the field list is pinned as it is, so dataclasses.replace() would
-    drop them; use SamplingParams.replace()."""
+    drop them; use SamplingParams.replace().
+    top_logprobs is a fifth attribute of the same kind: an int in [0, TOP_LOGPROBS_MAX]; N > 0 collects, per generated
+    token, its log-probability, its rank and the N most likely tokens of the RAW distribution with their log-probabilities
+    (ServingEngine.top_logprobs; one vt_logprob_rows launch per step). It implies what logprobs=True collects. repr shows it when set."""
     TRUNC_NAMES = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
+    TOP_LOGPROBS_MAX = 20                        # VT_LOGPROB_MAX_TOP
 
-    def __init__(self, *args, min_p: float = 0.0, typical_p: float = 1.0, epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0, **kw):
+    def __init__(self, *args, min_p: float = 0.0, typical_p: float = 1.0, epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0,
+                 top_logprobs: int = 0, **kw):
         for name, value in zip(self.TRUNC_NAMES, (min_p, typical_p, epsilon_cutoff, eta_cutoff)):
             object.__setattr__(self, name, value)
+        object.__setattr__(self, "top_logprobs", top_logprobs)
         super().__init__(*args, **kw)            # (its __post_init__ validates: the four are set by then)
 
     def __setattr__(self, name, value):          # (the frozen base guards its own fields only once it is subclassed)
@@ -205,12 +220,18 @@ class SamplingParams(_SamplingFields):
     def validate(self) -> None:
         super().validate()
         check_truncation_values(*self.trunc_row_raw(), what="SamplingParams")
+        check_top_logprobs(self.top_logprobs, "SamplingParams")
+
+    @property
+    def wants_logprobs(self) -> bool:
+        """Is the chosen token's log-probability collected (logprobs=True, or implied by top_logprobs > 0)?"""
+        return bool(self.logprobs) or self.top_logprobs > 0
 
     def trunc_row_raw(self) -> tuple:
         return tuple(getattr(self, n) for n in self.TRUNC_NAMES)
 
     def _key(self) -> tuple:
-        return tuple(getattr(self, n) for n in self.__dataclass_fields__) + self.trunc_row_raw()
+        return tuple(getattr(self, n) for n in self.__dataclass_fields__) + self.trunc_row_raw() + (int(self.top_logprobs),)
 
     def __eq__(self, other):
         return self._key() == other._key() if other.__class__ is self.__class__ else NotImplemented
@@ -220,11 +241,13 @@ class SamplingParams(_SamplingFields):
 
     def __repr__(self):
         names = list(self.__dataclass_fields__) + list(self.TRUNC_NAMES)
+        if self.top_logprobs:
+            names.append("top_logprobs")
         return "SamplingParams(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in names) + ")"
 
     def replace(self, **changes) -> "SamplingParams":
         """A copy with some settings changed (dataclasses.replace knows only the dataclass fields)."""
-        kw = {n: getattr(self, n) for n in list(self.__dataclass_fields__) + list(self.TRUNC_NAMES)}
+        kw = {n: getattr(self, n) for n in list(self.__dataclass_fields__) + list(self.TRUNC_NAMES) + ["top_logprobs"]}
         kw.update(changes)
         return SamplingParams(**kw)
 

@@ -31,6 +31,7 @@ import collections
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import ops
@@ -63,6 +64,8 @@ class _Request:
     hist_len: int = 0
     last_lp: Optional[torch.Tensor] = None   # device fp32 [1]: log-probability of `last` (sampling.logprobs)
     logprobs: List[float] = field(default_factory=list)
+    last_top: Optional[tuple] = None         # (device int32 buffer, row, rows, n_top) of `last`'s vt_logprob_rows output (sampling.top_logprobs)
+    top: List[tuple] = field(default_factory=list)   # per emitted token: (rank, top ids, top log-probabilities)
     allow_host: dict = field(default_factory=dict)   # step_allow_mask's cache: the static host masks, the choices trie
     allow_dev: dict = field(default_factory=dict)    # static masks on the device ("pre" / "post"): uploaded once, released with hist
     allow_cur: Optional[torch.Tensor] = None         # the mask of the next pick (a static one, a step-dependent upload, or None)
@@ -150,7 +153,7 @@ class ServingEngine:
         for r in self.waiting:
             if r.rid == rid:
                 self.waiting.remove(r)
-                r.flat = None
+                r.flat = r.last_top = None
                 self._drop_masks(r)
                 return True
         return False
@@ -159,7 +162,7 @@ class ServingEngine:
         """The request failed on its own: it leaves the engine with its exception; nothing else is disturbed."""
         if r.seq.pages:
             self.model.kv.release(r.seq.pages)
-        r.seq.pages, r.seq.length, r.last, r.flat, r.hist, r.last_lp = [], 0, None, None, None, None
+        r.seq.pages, r.seq.length, r.last, r.flat, r.hist, r.last_lp, r.last_top = [], 0, None, None, None, None, None
         self._drop_masks(r)
         r.error, r.done = exc, True
         self.failed[r.rid] = r
@@ -216,7 +219,11 @@ class ServingEngine:
         A request whose SamplingParams are `truncated` (min_p, typical_p, epsilon_cutoff or eta_cutoff on a sampled request; DESIGN.md
         9.9) turns the launch into ONE vt_sample_rows_trunc: its row carries its four values, every other row an all-inactive entry,
         which the kernel treats bit for bit as vt_sample_rows_adj does. While no active request is truncated the launches are exactly
-        the ones above."""
+        the ones above.
+        A request with SamplingParams(top_logprobs=N > 0): AFTER the pick, ONE vt_logprob_rows launch over the span of
+        rows from the first to the last such request, the device ids just picked as targets and the largest N asked for as n_top (a
+        shorter list is a prefix of a longer one, bit for bit). Its output stays on the device (r.last_top) until step() reads it back
+        together with the tokens. While no row's request asks, the launches are exactly the ones above."""
         if reqs is None or all(r.sampling is None and r.adjust is None for r in reqs):
             if self.do_sample:
                 return ops.sample_top_p(logits, self.temperature, self.top_p, self.seed, self._step)
@@ -232,7 +239,7 @@ class ServingEngine:
                 r.hist, r.hist_len = buf[0], lens[0]
             rows.append((sp.temperature, sp.resolved_top_k(self.model.config), sp.top_p, sp.repetition_penalty, sp.seed, len(r.tokens), 0,
                          *((r.hist.data_ptr(), r.hist_len) if sp.repetition_penalty != 1.0 else (0, 0))))
-        want_lp = any(r.sampling is not None and r.sampling.logprobs for r in reqs)
+        want_lp = any(r.sampling is not None and r.sampling.wants_logprobs for r in reqs)
         allow = None
         if any(r.sampling is not None and r.sampling.constrained for r in reqs):
             for r in reqs:
@@ -290,8 +297,15 @@ class ServingEngine:
         res = ops.sample_rows(logits, pack_sample_rows(rows, logits.device), return_logprob=want_lp, allow=allow, adjust=adj, trunc=trunc)
         ids, lp = res if want_lp else (res, None)
         for i, r in enumerate(reqs):
-            if r.sampling is not None and r.sampling.logprobs:
+            if r.sampling is not None and r.sampling.wants_logprobs:
                 r.last_lp = lp[i:i + 1]
+        ask = [i for i, r in enumerate(reqs) if r.sampling is not None and r.sampling.top_logprobs > 0]
+        if ask:
+            i0, n = ask[0], ask[-1] + 1 - ask[0]
+            n_top = max(reqs[i].sampling.top_logprobs for i in ask)
+            got = ops.logprob_rows(logits[i0:i0 + n], ids[i0:i0 + n], n_top, return_rank=True)
+            for i in ask:
+                reqs[i].last_top = (got["packed"], i - i0, n, n_top)
         return ids
 
     def _embed(self, r: _Request) -> torch.Tensor:
@@ -429,7 +443,7 @@ class ServingEngine:
         r.done = True
         self.model.kv.release(r.seq.pages)
         r.seq.pages = []
-        r.hist = r.last_lp = None
+        r.hist = r.last_lp = r.last_top = None
         self._drop_masks(r)
         self.finished[r.rid] = r
 
@@ -449,6 +463,22 @@ class ServingEngine:
         if with_lp:
             for r, v in zip(with_lp, torch.cat([r.last_lp for r in with_lp]).tolist()):
                 r.logprobs.append(float(v))
+        with_top = [r for r in self.active if r.last_top is not None]
+        if with_top:                                    # the same read-back point: the stream has been waited for above
+            host = {}                                   # one copy per launch's buffer (a decode step: one buffer for all rows)
+            for r in with_top:
+                if id(r.last_top[0]) not in host:
+                    host[id(r.last_top[0])] = r.last_top[0].cpu().numpy()
+            for r in with_top:
+                buf, j, n, n_top = r.last_top
+                a = host[id(buf)]
+                # planes of ops.logprob_rows' packed buffer: logprob [n], rank [n], top_ids [n, n_top], top_logprobs [n, n_top]
+                k = r.sampling.top_logprobs
+                ids_at = 2 * n + j * n_top
+                lps_at = 2 * n + n * n_top + j * n_top
+                r.top.append((int(a[n + j]), tuple(int(t) for t in a[ids_at:ids_at + k]),
+                              tuple(float(v) for v in a[lps_at:lps_at + k].view(np.float32))))
+                r.last_top = None
         out: List[Tuple[int, int]] = []
         still: List[_Request] = []
         for r, t in zip(self.active, toks):
@@ -509,9 +539,21 @@ class ServingEngine:
         order; the request must have been submitted with SamplingParams(logprobs=True)."""
         for r in list(self.finished.values()) + self.active:
             if r.rid == rid:
-                if r.sampling is None or not r.sampling.logprobs:
+                if r.sampling is None or not r.sampling.wants_logprobs:
                     raise ValueError(f"request {rid} was not submitted with SamplingParams(logprobs=True)")
                 return torch.tensor(r.logprobs, dtype=torch.float32)
+        raise KeyError(f"request {rid} has emitted nothing (waiting, failed or unknown)")
+
+    def top_logprobs(self, rid: int) -> List[tuple]:
+        """One entry per token request `rid` has emitted so far, in order: (token, logprob, rank, top_ids, top_logprobs) -- the token, its
+        log-probability (what logprobs() returns for it), its rank in the RAW distribution (1: the most likely; larger logit first, ties
+        by the lower id), and the N most likely tokens with their log-probabilities as tuples. The request must have been submitted
+        with SamplingParams(top_logprobs=N > 0)."""
+        for r in list(self.finished.values()) + self.active:
+            if r.rid == rid:
+                if r.sampling is None or not r.sampling.top_logprobs:
+                    raise ValueError(f"request {rid} was not submitted with SamplingParams(top_logprobs=N > 0)")
+                return [(int(t), float(lp), rank, ids, lps) for t, lp, (rank, ids, lps) in zip(r.tokens, r.logprobs, r.top)]
         raise KeyError(f"request {rid} has emitted nothing (waiting, failed or unknown)")
 
     def errors(self) -> Dict[int, BaseException]:
