@@ -100,6 +100,8 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
  * vt_sample_rows, vt_sample_rows_allow and vt_sample_rows_adj do not change. */
 /* 114 also carries vt_logprob_rows WITHOUT a bump: one new symbol, no struct and no existing signature changes; the samplers and
  * vt_beam_step do not change. */
+/* 114 also carries vt_fsm_rows and struct vt_fsm_row WITHOUT a bump: one new symbol and one new struct; vt_ban_rows and the samplers do
+ * not change. */
 #define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
@@ -453,6 +455,64 @@ typedef struct vt_ban_row {
   int32_t seqs_len;
 } vt_ban_row;
 int vt_ban_rows(const vt_ban_row* rows /* DEVICE */, int n_rows, int V, void* stream);
+
+/* TOKEN AUTOMATA: guided decoding. A row carries a state of a finite automaton over token ids; the state decides which
+ * ids the row's COMING pick may be, the ids the row has emitted move the state. Built on the device in front of vt_sample_rows_allow, as
+ * vt_ban_rows is (the role of transformers' PrefixConstrainedLogitsProcessor and of vLLM's / outlines' guided decoding by regex or by
+ * choices). Nothing is read on the host.
+ * rows: DEVICE array of n_rows vt_fsm_row (96 bytes each, 8-byte aligned; the offsets are part of the ABI):
+ *    0 const int32_t*  gen          DEVICE ids this row has GENERATED so far (not the prompt); NULL = gen_len counts as 0
+ *    8 int32_t*        cell         DEVICE two int32 {state, consumed}, read and written; NULL = this row is skipped entirely
+ *   16 const uint32_t* base         DEVICE allow mask to intersect with, ceil(V / 32) words; NULL = every id of [0, V)
+ *   24 uint32_t*       out          DEVICE mask to write, ceil(V / 32) words; NULL = this row is skipped entirely
+ *   32 const int32_t*  offsets      DEVICE [n_states + 1]: state s lists the edges [offsets[s], offsets[s + 1]); NULL = n_states counts as 0
+ *   40 const int32_t*  edge_tok     DEVICE [n_edges] token ids, ascending and unique inside each state; NULL = n_edges counts as 0
+ *   48 const int32_t*  edge_next    DEVICE [n_edges] next state of the edge, or -1 = this token is forbidden here; NULL = n_edges counts as 0
+ *   56 const int32_t*  state_info   DEVICE [n_states][2] = {default_next, accept}; NULL = n_states counts as 0
+ *   64 int32_t         gen_len      ids readable at gen; <= 0: none
+ *   68 int32_t         n_states
+ *   72 int32_t         n_edges
+ *   76 int32_t         n_eos        clamped into [0, 4]
+ *   80 int32_t         eos[4]       the row's EOS ids, eos[0 .. n_eos)
+ * Word / bit layout: vt_sample_rows_allow's (token i is bit (i & 31) of word (i >> 5)).
+ * step(s, t), with plain int32 equality throughout:
+ *   - s outside [0, n_states) gives -1 (dead).
+ *   - the edges of s are the indices [lo, hi) with lo = offsets[s] and hi = offsets[s + 1] clamped into [0, n_edges] (hi not below lo).
+ *     If t == edge_tok[j] for one of them (found by binary search: the ids must ascend) the result is edge_next[j].
+ *   - else, if t is one of eos[0 .. n_eos): s when accept[s] != 0, and -1 otherwise. A default edge never covers an EOS id.
+ *   - else default_next[s].
+ *   - any result outside [0, n_states) is -1.
+ * Advance: consumed = max(cell[1], 0); for i in [consumed, gen_len): state = step(state, gen[i]), starting from state = cell[0]; then
+ *   cell = {state, max(consumed, gen_len)} (a state that consumed nothing is written back as it was). Launching the same row twice
+ *   therefore advances once (the launch is idempotent) and a row whose cell is k ids behind catches up.
+ * Mask: token t of [0, V) is allowed iff step(state after the advance, t) >= 0; out = (base, or the bits [0, V) when base is NULL) AND
+ *   allowed. Bits at positions >= V of the last word are CLEAR whatever base holds there. A dead state yields an all-zero mask (what
+ *   the sampler returns for a row with nothing allowed is defined at vt_sample_rows_allow).
+ * The kernel is total: no field value leads to an access outside gen[0 .. gen_len), the two ints of cell, offsets[0 .. n_states],
+ * edge_tok / edge_next[0 .. n_edges), state_info[0 .. 2 * n_states) or the ceil(V / 32) words of base and out (the inputs must be
+ * readable for those lengths when set); words of a larger buffer behind out are not touched. out must NOT alias base or another row's
+ * out; two rows must not share a cell. Edge ids that do not ascend, or that repeat inside a state, give a mask and a step that need not
+ * agree with each other, and nothing worse. The result does not depend on the order of the LDS atomics: it is deterministic.
+ * Refused with VT_STATUS_ARG and a message before any launch: V <= 0, V > VT_SAMPLE_ROWS_MAX_V, n_rows < 0, rows == NULL with n_rows > 0.
+ * n_rows == 0 is a success that launches nothing. One launch, one 1024-thread block per row: one thread advances the state, the mask is
+ * built in LDS (from ones under a default edge, else from zeros; atomicOr / atomicAnd per listed edge) and written once.
+ * 114 carries this entry point WITHOUT a bump: one new symbol and one new struct, nothing existing changes (see the note at VT_ABI_VERSION). */
+typedef struct vt_fsm_row {
+  const int32_t* gen;
+  int32_t* cell;
+  const uint32_t* base;
+  uint32_t* out;
+  const int32_t* offsets;
+  const int32_t* edge_tok;
+  const int32_t* edge_next;
+  const int32_t* state_info;
+  int32_t gen_len;
+  int32_t n_states;
+  int32_t n_edges;
+  int32_t n_eos;
+  int32_t eos[4];
+} vt_fsm_row;
+int vt_fsm_rows(const vt_fsm_row* rows /* DEVICE */, int n_rows, int V, void* stream);
 
 /* ADDITIVE ADJUSTMENTS: logit_bias / single-token sequence_bias and the presence / frequency penalties (the role of
  * transformers' SequenceBiasLogitsProcessor and of the OpenAI / vLLM penalties). A row's adjustment `adj` is V pairs (pre, post) of fp32:

@@ -281,6 +281,9 @@ int vt_logprob_rows_launch(const float* logits, int rows, int V, int ldl, const 
 // ---- vt_ban.hip -----------------------------------------------------------------------------------
 int vt_ban_rows_launch(const vt_ban_row* rows, int n_rows, int V, hipStream_t s);
 
+// ---- vt_fsm.hip -----------------------------------------------------------------------------------
+int vt_fsm_rows_launch(const vt_fsm_row* rows, int n_rows, int V, hipStream_t s);
+
 // ---- vt_bias.hip ----------------------------------------------------------------------------------
 int vt_bias_rows_launch(const vt_bias_row* rows, int n_rows, int V, hipStream_t s);
 

@@ -469,7 +469,8 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                  return_logits=False, padded_batch=False, repetition_penalty=1.0, return_logprobs=False, suppress_tokens=None,
                  begin_suppress_tokens=None, min_new_tokens=None, bad_words_ids=None, allowed_token_ids=None, num_return_sequences=1,
                  length_penalty=1.0, early_stopping=False, no_repeat_ngram_size=None, sequence_bias=None, presence_penalty=0.0,
-                 frequency_penalty=0.0, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, top_logprobs=0, **kwargs):
+                 frequency_penalty=0.0, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None, top_logprobs=0, automaton=None, choices=None,
+                 **kwargs):
         """repetition_penalty (RepetitionPenaltyLogitsProcessor; 1.0 is off) and return_logprobs: with both at their defaults a step
         launches what it always did (vt_argmax / vt_sample_top_p). Otherwise every step is ONE vt_sample_rows launch (row b: stream = b,
         counter = step -- today's draws) whose penalty history -- the sample's non-negative prompt ids plus what it has generated -- lives
@@ -522,7 +523,17 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         lower id) with their log-probabilities, and rank int32 [B, n_new], the emitted id's rank in that order (1 is the most likely).
         Every pick is followed by ONE vt_logprob_rows launch that writes into buffers allocated before the loop; the pick itself, the
         ids and return_logprobs are what they are without it. For a row that has finished the values are those of the id it would have
-        emitted, as with return_logprobs. Refused with NotImplementedError: num_beams > 1, padded_batch; ValueError outside [0, 20]."""
+        emitted, as with return_logprobs. Refused with NotImplementedError: num_beams > 1, padded_batch; ValueError outside [0, 20].
+        Guided decoding: automaton = a vitron_amd.automaton.TokenAutomaton (TokenAutomaton.from_regex(pattern, vocab),
+        .from_choices(...)); choices=[[ids], ...] is automaton=TokenAutomaton.from_choices(choices). Every sample runs the automaton from
+        its start state with a {state, consumed} cell of its own on the device: every step is one vt_fsm_rows launch, which moves the
+        state over the id the sample emitted last and builds its allow mask from (the step's static mask above, or nothing; the
+        state), then vt_ban_rows with that mask as its base when no_repeat_ngram_size is on, then one vt_sample_rows_allow launch that
+        reads the last mask built. The tables, the cells and every step's vt_fsm_row array are uploaded once before the loop: no host
+        wait, no per-step upload. The call's EOS ids are allowed exactly in the accepting states (min_new_tokens still withholds them).
+        The device-built mask is never read back: a state that allows nothing cannot raise. ValueError before the prefill: more than 4
+        EOS ids, an accepting state with no EOS id in [0, vocab_size), a start state that allows nothing, automaton together with
+        choices. Refused with NotImplementedError: num_beams > 1, padded_batch."""
         from ...picker import StepPicker, resolve_generate_args
         a = resolve_generate_args(
             self.config, input_ids.shape[1], do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k,
@@ -533,7 +544,7 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
             allowed_token_ids=allowed_token_ids, num_return_sequences=num_return_sequences, length_penalty=length_penalty,
             early_stopping=early_stopping, no_repeat_ngram_size=no_repeat_ngram_size, sequence_bias=sequence_bias,
             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p, typical_p=typical_p,
-            epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, top_logprobs=top_logprobs)
+            epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, top_logprobs=top_logprobs, automaton=automaton, choices=choices)
         dev = self.device
         input_ids = input_ids.to(dev)
         B, L0 = input_ids.shape

@@ -726,6 +726,23 @@ def ban_rows(rows_dev: torch.Tensor, n_rows: int, V: int) -> None:
     _lib.check(lib.vt_ban_rows(_p(rows_dev) if n_rows > 0 else None, n_rows, int(V), _stream()), "vt_ban_rows", lib)
 
 
+def fsm_rows(rows_dev: torch.Tensor, n_rows: int, V: int) -> None:
+    """Advance the automaton states of n_rows rows over the ids they have generated and build their allow masks on the device (guided
+    decoding); see vt_fsm_rows in include/vitron_hip.h. rows_dev: the device array of vt_fsm_row that sampling.pack_fsm_rows builds
+    (contiguous uint8, n_rows x 96 bytes). Every pointer inside it is dereferenced on the device as it is: the caller keeps the buffers
+    alive until the launch has run, sizes every `out` and `base` for ceil(V / 32) words, gives every row its own two-int cell and lets
+    no `out` alias a `base` or another `out`."""
+    from .sampling import FSM_ROW_BYTES
+    lib = _lib.load_any()
+    n_rows = int(n_rows)
+    if n_rows > 0:
+        _chk(rows_dev, torch.uint8, "fsm_rows.rows_dev")
+        if rows_dev.numel() != n_rows * FSM_ROW_BYTES:
+            raise _lib.VitronHipError(f"fsm_rows.rows_dev: expected {n_rows} x {FSM_ROW_BYTES} bytes (sampling.pack_fsm_rows), got "
+                                      f"{rows_dev.numel()}")
+    _lib.check(lib.vt_fsm_rows(_p(rows_dev) if n_rows > 0 else None, n_rows, int(V), _stream()), "vt_fsm_rows", lib)
+
+
 def bias_rows(rows_dev: torch.Tensor, n_rows: int, V: int) -> None:
     """Build the additive adjustments of n_rows rows on the device (logit bias, presence and frequency penalties over the generated
     ids); see vt_bias_rows in include/vitron_hip.h. rows_dev: the device array of vt_bias_row that sampling.pack_bias_rows builds

@@ -3,9 +3,9 @@
 `resolve_generate_args` turns generate()'s keyword arguments into one frozen `GenerateArgs` and raises every refusal that needs no device
 work, in a fixed order. `StepPicker` is built from that record once, before the prefill: it uploads everything the picks of ALL steps
 need (the static allow masks and every step's pointer array, every step's vt_sample_row / vt_ban_row / vt_bias_row array, the device
-histories, the adjustment buffers) and
+histories, the adjustment buffers, an automaton's cells and row array) and
 then serves `pick(step, logits) -> ids` without an upload or a host wait. `device_history` is the one builder of a penalty / ban
-history; ServingEngine fills a request's `hist` with it too. (DESIGN.md 9.3 - 9.8.)
+history; ServingEngine fills a request's `hist` with it too. (DESIGN.md 9.3 - 9.11.)
 """
 from __future__ import annotations
 
@@ -18,9 +18,9 @@ import torch
 
 from . import ops
 from .engine import parse_kv_cache_dtype
-from .sampling import (BAN_ROW_BYTES, BIAS_ROW_BYTES, BIAS_ROWS_MAX_V, ROW_BYTES, allow_mask, check_penalties, check_sampling_values,
-                       check_top_logprobs, check_truncation_values, mask_words, normalise_bias, pack_ban_rows, pack_bias_rows, pack_sample_rows,
-                       pack_trunc_rows, truncation_active)
+from .sampling import (BAN_ROW_BYTES, BIAS_ROW_BYTES, BIAS_ROWS_MAX_V, FSM_ROW_BYTES, ROW_BYTES, allow_mask, check_penalties, check_sampling_values,
+                       check_top_logprobs, check_truncation_values, mask_words, normalise_bias, pack_ban_rows, pack_bias_rows, pack_fsm_rows,
+                       pack_sample_rows, pack_trunc_rows, truncation_active)
 
 
 @dataclass(frozen=True, eq=False)
@@ -55,6 +55,7 @@ class GenerateArgs:
     frequency_penalty: float = 0.0
     trunc: Tuple[float, float, float, float] = (0.0, 1.0, 0.0, 0.0)   # (min_p, typical_p, epsilon_cutoff, eta_cutoff); off when greedy
     top_logprobs: int = 0                        # N > 0: every step's N most likely tokens and the chosen token's rank (vt_logprob_rows)
+    automaton: Any = None                        # a TokenAutomaton every row runs from its start state (vt_fsm_rows)
 
     @property
     def constrained(self) -> bool:
@@ -78,7 +79,7 @@ class GenerateArgs:
     def per_row(self) -> bool:
         """Does a step need the per-row sampler (vt_sample_rows) instead of vt_argmax / vt_sample_top_p?"""
         return (float(self.repetition_penalty) != 1.0 or bool(self.return_logprobs) or self.constrained or self.ngram > 0
-                or self.adjusted or self.truncated)
+                or self.adjusted or self.truncated or self.automaton is not None)
 
 
 def static_mask_schedule(V: int, steps: int, banned_always, banned_begin, min_new: int, eos, allowed_ids):
@@ -108,13 +109,15 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
                           suppress_tokens, begin_suppress_tokens, min_new_tokens, bad_words_ids, allowed_token_ids, num_return_sequences,
                           length_penalty, early_stopping, no_repeat_ngram_size, sequence_bias=None, presence_penalty=0.0,
                           frequency_penalty=0.0, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None,
-                          top_logprobs=0) -> GenerateArgs:
+                          top_logprobs=0, automaton=None, choices=None) -> GenerateArgs:
     """generate()'s keyword arguments as a GenerateArgs. Raises, in this order and before any device work: the argument errors of
     num_beams / no_repeat_ngram_size, everything a beam call refuses, the padded_batch refusals that depend on arguments alone, the
     sampling values, the constraint arguments, a step the constraints leave no token for, constraints with padded_batch, the values of
     sequence_bias / presence_penalty / frequency_penalty, those three with padded_batch, the values of min_p / typical_p / epsilon_cutoff /
     eta_cutoff (None is off, as in GenerationConfig; ignored without do_sample), those four with padded_batch, the value of top_logprobs
-    (an int in [0, 20]; a beam call refuses it with its other optional arguments), top_logprobs with padded_batch. The sample seed
+    (an int in [0, 20]; a beam call refuses it with its other optional arguments), top_logprobs with padded_batch, automaton / choices
+    with padded_batch, and what TokenAutomaton.check refuses for the call's EOS ids (a beam call refuses `automaton` with its other
+    optional arguments; choices=[...] is automaton=TokenAutomaton.from_choices(...), giving both is a ValueError). The sample seed
     is drawn from torch's global CPU generator (so torch.manual_seed makes sampling reproducible, as with GenerationMixin.sample) and
     only when sampling without `seed`, after the beam refusals: greedy and refused calls leave the RNG state alone."""
     num_beams = int(num_beams)
@@ -124,6 +127,15 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
         no_repeat_ngram_size = 0
     if not isinstance(no_repeat_ngram_size, int) or isinstance(no_repeat_ngram_size, bool) or not 0 <= no_repeat_ngram_size <= 2 ** 31 - 1:
         raise ValueError(f"generate: no_repeat_ngram_size must be None or an int >= 0 (0 is off), got {no_repeat_ngram_size!r}")
+    if choices is not None:
+        if automaton is not None:
+            raise ValueError("generate: give automaton or choices, not both")
+        from .automaton import TokenAutomaton
+        automaton = TokenAutomaton.from_choices(choices)
+    if automaton is not None:
+        from .automaton import TokenAutomaton
+        if not isinstance(automaton, TokenAutomaton):
+            raise ValueError(f"generate: automaton must be a TokenAutomaton or None, got {automaton!r}")
     eos = config.eos_token_id if eos_token_id is None else eos_token_id
     if max_new_tokens is None:
         max_new_tokens = (max_length - input_len) if max_length else 20
@@ -146,7 +158,7 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
         + tuple(f"{name}=..." for name, value, off in (("min_p", min_p, 0.0), ("typical_p", typical_p, 1.0),
                                                        ("epsilon_cutoff", epsilon_cutoff, 0.0), ("eta_cutoff", eta_cutoff, 0.0))
                 if value is not None and value != off)
-        + (("top_logprobs=...",) if top_logprobs else ()))
+        + (("top_logprobs=...",) if top_logprobs else ()) + (("automaton=...",) if automaton is not None else ()))
     if num_beams > 1:
         check_beam_arguments(a, int(config.vocab_size))
     elif a.num_return_sequences != 1:
@@ -203,6 +215,11 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
         raise NotImplementedError("generate(padded_batch=True) does not take top_logprobs; use the default packed batch")
     if top_logprobs:
         a = dataclasses.replace(a, top_logprobs=int(top_logprobs))
+    if automaton is not None:
+        if padded_batch:
+            raise NotImplementedError("generate(padded_batch=True) does not take automaton / choices; use the default packed batch")
+        automaton.check(V, sorted(a.eos))
+        a = dataclasses.replace(a, automaton=automaton)
     return a
 
 
@@ -279,6 +296,11 @@ class StepPicker:
         buffers never change and are built by ONE launch here, before the prefill;
       - with min_p / typical_p / epsilon_cutoff / eta_cutoff: the B vt_trunc_row entries, the same at every step; the
         sampler launch is vt_sample_rows_trunc then.
+      - with an automaton: its tables (once per device, kept on the automaton), the [B, 2] cells {start, 0}, the B
+        working masks vt_fsm_rows writes, the ids every row has GENERATED (the tail of the penalty history, or the history the
+        penalties count over, or one of its own) and the [steps, B] vt_fsm_row array (gen_len = step, base = the step's static mask or
+        NULL). A step is ONE ops.fsm_rows launch; with no_repeat_ngram_size its working masks are the `base` of the vt_ban_row array
+        instead of the static mask, and the sampler's allow pointers name the last mask built.
     The histories grow on the device. The device-built masks and adjustments are never read back.
     With top_logprobs = N > 0, in every mode: the [steps, B, N] id and log-probability buffers and the [steps, B] rank
     buffer are allocated here, and every pick is followed by ONE ops.logprob_rows launch over the step's RAW logits with the picked ids
@@ -311,12 +333,20 @@ class StepPicker:
             [(T, k, p, float(a.repetition_penalty), a.sample_seed, st, b,
               0 if self.hist is None else self.hist.row_ptr(b), 0 if self.hist is None else self.hist.lens[b] + st)
              for st in range(steps) for b in range(B)], dev).view(steps, B, ROW_BYTES)
+        self.fsm_rows = None
+        ban_base = step_base
+        if a.automaton is not None:
+            self.fsm_work = fw = torch.empty((B, mask_words(self.V)), dtype=torch.int32, device=dev)
+            fsm_ptr = [fw.data_ptr() + 4 * b * fw.stride(0) for b in range(B)]
+            self.fsm_ptrs = torch.tensor(fsm_ptr, dtype=torch.int64).to(dev)
+            ban_base = None                      # the ban's base is the row's automaton mask, whatever the step
         self.ban_rows = None
         if a.ngram:
             self.ban_hist = h = _History(input_ids, steps, attention_mask)
             self.ban_work = w = torch.empty((B, mask_words(self.V)), dtype=torch.int32, device=dev)
             work_ptr = [w.data_ptr() + 4 * b * w.stride(0) for b in range(B)]
-            self.ban_rows = pack_ban_rows([(h.row_ptr(b), h.lens[b] + st, step_base[st], work_ptr[b], a.ngram, 0, 0, 0)
+            self.ban_rows = pack_ban_rows([(h.row_ptr(b), h.lens[b] + st, fsm_ptr[b] if ban_base is None else ban_base[st], work_ptr[b],
+                                            a.ngram, 0, 0, 0)
                                            for st in range(steps) for b in range(B)], dev).view(steps, B, BAN_ROW_BYTES)
             self.ban_ptrs = torch.tensor(work_ptr, dtype=torch.int64).to(dev)
         self.trunc = pack_trunc_rows([a.trunc] * B, dev) if a.truncated else None
@@ -339,9 +369,21 @@ class StepPicker:
                 self.bias_rows = pack_bias_rows(
                     [(gen_ptr[b] if st else 0, st, ids_ptr, vals_ptr, len(a.bias), adj_ptr[b], a.presence_penalty, a.frequency_penalty)
                      for st in range(steps) for b in range(B)], dev).view(steps, B, BIAS_ROW_BYTES)
+        if a.automaton is not None:
+            if self.hist is not None:            # the generated ids are the tail of the penalty history
+                gen_ptr = [self.hist.row_ptr(b) + 4 * self.hist.lens[b] for b in range(B)]
+            else:
+                if self.gen_hist is None:
+                    self.gen_hist = _History(input_ids[:, :0], steps)
+                gen_ptr = [self.gen_hist.row_ptr(b) for b in range(B)]
+            self.fsm_cell = c = torch.tensor([[a.automaton.start, 0]] * B, dtype=torch.int32).to(dev)
+            cell_ptr = [c.data_ptr() + 8 * b for b in range(B)]
+            tables, eos = a.automaton.row_fields(dev), sorted(a.eos)
+            self.fsm_rows = pack_fsm_rows([(gen_ptr[b] if st else 0, st, cell_ptr[b], step_base[st], fsm_ptr[b], *tables, eos)
+                                           for st in range(steps) for b in range(B)], dev).view(steps, B, FSM_ROW_BYTES)
 
     def check_width(self, logits: torch.Tensor) -> None:
-        if self.mode == "rows" and (self.a.constrained or self.a.ngram) and logits.shape[1] != self.V:
+        if self.mode == "rows" and (self.a.constrained or self.a.ngram or self.a.automaton is not None) and logits.shape[1] != self.V:
             raise RuntimeError(f"generate: the allow masks were built for V = {self.V}, the logits have {logits.shape[1]} columns")
         if self.mode == "rows" and self.a.adjusted and logits.shape[1] != self.V:
             raise RuntimeError(f"generate: the logit adjustments were built for V = {self.V}, the logits have {logits.shape[1]} columns")
@@ -359,11 +401,13 @@ class StepPicker:
             return ops.argmax(logits)
         if self.mode == "top_p":   # device-side temperature / top-k / top-p sampler (no host sync, counter-based RNG)
             return ops.sample_top_p(logits, a.temperature, a.top_p if a.top_p else 1.0, a.sample_seed, step, top_k=int(a.top_k or 0))
+        ptrs = None if self.allow_ptrs is None else self.allow_ptrs[step]
+        if self.fsm_rows is not None:            # the rows' states catch up with what they emitted; their masks for this pick: one launch
+            ops.fsm_rows(self.fsm_rows[step], self.B, self.V)
+            ptrs = self.fsm_ptrs
         if self.ban_rows is not None:            # the rows' masks for this pick, from their histories: one launch, nothing uploaded
             ops.ban_rows(self.ban_rows[step], self.B, logits.shape[1])
             ptrs = self.ban_ptrs
-        else:
-            ptrs = None if self.allow_ptrs is None else self.allow_ptrs[step]
         if self.bias_rows is not None:           # the rows' adjustments for this pick, from what they have generated: one launch
             ops.bias_rows(self.bias_rows[step], self.B, self.V)
         nxt = ops.sample_rows(logits, self.rows[step], return_logprob=bool(a.return_logprobs), _allow_ptrs=ptrs, _adjust_ptrs=self.adj_ptrs,

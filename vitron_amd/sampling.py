@@ -19,6 +19,10 @@ the contract.
 Truncation: min_p, typical_p, epsilon_cutoff and eta_cutoff are fields of `SamplingParams`; a row's four values are a
 struct vt_trunc_row (`pack_trunc_rows`) that vt_sample_rows_trunc reads.
 
+Token automata: `SamplingParams(automaton=A)` holds the reply to the language of a vitron_amd.automaton.TokenAutomaton
+(a regex over the vocabulary's strings, a set of choices). The allowed set depends on where the reply stands, so the mask is built on the
+DEVICE from a two-int cell per request (struct vt_fsm_row, `pack_fsm_rows`, ops.fsm_rows); nothing is uploaded per step.
+
 Top-N log-probabilities: `SamplingParams(top_logprobs=N)` asks for the N most likely tokens and the chosen token's rank
 at every generated token; they come from one vt_logprob_rows launch behind the pick and need no struct here.
 """
@@ -49,6 +53,15 @@ BAN_ROW_DTYPE = np.dtype({
     "itemsize": 48,
 })
 BAN_ROW_BYTES = BAN_ROW_DTYPE.itemsize
+# struct vt_fsm_row: the offsets are part of the ABI (tests/test_fsm_ref_host.py checks them against the header's table)
+FSM_ROW_DTYPE = np.dtype({
+    "names": ["gen", "cell", "base", "out", "offsets", "edge_tok", "edge_next", "state_info", "gen_len", "n_states", "n_edges", "n_eos", "eos"],
+    "formats": ["<u8", "<u8", "<u8", "<u8", "<u8", "<u8", "<u8", "<u8", "<i4", "<i4", "<i4", "<i4", ("<i4", (4,))],
+    "offsets": [0, 8, 16, 24, 32, 40, 48, 56, 64, 68, 72, 76, 80],
+    "itemsize": 96,
+})
+FSM_ROW_BYTES = FSM_ROW_DTYPE.itemsize
+FSM_MAX_EOS = 4                    # the eos[4] of vt_fsm_row
 # struct vt_bias_row: the offsets are part of the ABI (tests/test_bias_ref_host.py checks them against the header's table)
 BIAS_ROW_DTYPE = np.dtype({
     "names": ["history", "bias_ids", "bias_vals", "out", "history_len", "n_bias", "presence", "frequency"],
@@ -200,15 +213,19 @@ class SamplingParams(_SamplingFields):
     drop them; use SamplingParams.replace().
     top_logprobs is a fifth attribute of the same kind: an int in [0, TOP_LOGPROBS_MAX]; N > 0 collects, per generated
     token, its log-probability, its rank and the N most likely tokens of the RAW distribution with their log-probabilities
-    (ServingEngine.top_logprobs; one vt_logprob_rows launch per step). It implies what logprobs=True collects. repr shows it when set."""
+    (ServingEngine.top_logprobs; one vt_logprob_rows launch per step). It implies what logprobs=True collects. repr shows it when set.
+    automaton is a sixth: None, or a vitron_amd.automaton.TokenAutomaton the reply has to follow (guided decoding by
+    regex or choices). It makes the request `constrained`; its mask is built on the device by vt_fsm_rows from the request's own
+    {state, consumed} cell and intersects with every other constraint. Compared and hashed by identity; repr shows it when set."""
     TRUNC_NAMES = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
     TOP_LOGPROBS_MAX = 20                        # VT_LOGPROB_MAX_TOP
 
     def __init__(self, *args, min_p: float = 0.0, typical_p: float = 1.0, epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0,
-                 top_logprobs: int = 0, **kw):
+                 top_logprobs: int = 0, automaton=None, **kw):
         for name, value in zip(self.TRUNC_NAMES, (min_p, typical_p, epsilon_cutoff, eta_cutoff)):
             object.__setattr__(self, name, value)
         object.__setattr__(self, "top_logprobs", top_logprobs)
+        object.__setattr__(self, "automaton", automaton)
         super().__init__(*args, **kw)            # (its __post_init__ validates: the four are set by then)
 
     def __setattr__(self, name, value):          # (the frozen base guards its own fields only once it is subclassed)
@@ -221,6 +238,14 @@ class SamplingParams(_SamplingFields):
         super().validate()
         check_truncation_values(*self.trunc_row_raw(), what="SamplingParams")
         check_top_logprobs(self.top_logprobs, "SamplingParams")
+        if self.automaton is not None:
+            from .automaton import TokenAutomaton
+            if not isinstance(self.automaton, TokenAutomaton):
+                raise ValueError(f"SamplingParams: automaton must be a TokenAutomaton or None, got {self.automaton!r}")
+
+    @property
+    def constrained(self) -> bool:
+        return super().constrained or self.automaton is not None
 
     @property
     def wants_logprobs(self) -> bool:
@@ -231,7 +256,8 @@ class SamplingParams(_SamplingFields):
         return tuple(getattr(self, n) for n in self.TRUNC_NAMES)
 
     def _key(self) -> tuple:
-        return tuple(getattr(self, n) for n in self.__dataclass_fields__) + self.trunc_row_raw() + (int(self.top_logprobs),)
+        return tuple(getattr(self, n) for n in self.__dataclass_fields__) + self.trunc_row_raw() + (int(self.top_logprobs),) \
+            + (None if self.automaton is None else id(self.automaton),)
 
     def __eq__(self, other):
         return self._key() == other._key() if other.__class__ is self.__class__ else NotImplemented
@@ -243,11 +269,13 @@ class SamplingParams(_SamplingFields):
         names = list(self.__dataclass_fields__) + list(self.TRUNC_NAMES)
         if self.top_logprobs:
             names.append("top_logprobs")
+        if self.automaton is not None:
+            names.append("automaton")
         return "SamplingParams(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in names) + ")"
 
     def replace(self, **changes) -> "SamplingParams":
         """A copy with some settings changed (dataclasses.replace knows only the dataclass fields)."""
-        kw = {n: getattr(self, n) for n in list(self.__dataclass_fields__) + list(self.TRUNC_NAMES) + ["top_logprobs"]}
+        kw = {n: getattr(self, n) for n in list(self.__dataclass_fields__) + list(self.TRUNC_NAMES) + ["top_logprobs", "automaton"]}
         kw.update(changes)
         return SamplingParams(**kw)
 
@@ -483,6 +511,33 @@ def pack_ban_rows(rows: Sequence[tuple], device):
     import torch
     arr = ban_rows_array(rows)
     return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), BAN_ROW_BYTES)).to(device)
+
+
+# ---- token automata: struct vt_fsm_row (the host statement of the contract is vitron_amd.automaton.TokenAutomaton) ---------------------
+def fsm_rows_array(rows: Sequence[tuple]) -> np.ndarray:
+    """Host array of vt_fsm_row from one tuple per row:
+        (gen_ptr, gen_len, cell_ptr, base_ptr, out_ptr, offsets_ptr, edge_tok_ptr, edge_next_ptr, state_info_ptr, n_states, n_edges, eos)
+    eos: at most 4 EOS ids. The pointers are DEVICE addresses (tensor.data_ptr(), 0 for NULL) whose owners the caller keeps alive until
+    the launch has run; (offsets_ptr .. n_edges) is TokenAutomaton.row_fields(device)."""
+    arr = np.zeros((len(rows),), dtype=FSM_ROW_DTYPE)
+    for i, (gen_ptr, gen_len, cell_ptr, base_ptr, out_ptr, off_ptr, tok_ptr, nxt_ptr, info_ptr, n_states, n_edges, eos) in enumerate(rows):
+        eos = [int(e) for e in eos]
+        ptrs = [int(x) for x in (gen_ptr, cell_ptr, base_ptr, out_ptr, off_ptr, tok_ptr, nxt_ptr, info_ptr)]
+        if min(ptrs) < 0 or (int(gen_len) > 0 and not gen_ptr) or (int(n_states) > 0 and not (off_ptr and info_ptr)) \
+                or (int(n_edges) > 0 and not (tok_ptr and nxt_ptr)):
+            raise ValueError(f"fsm row {i}: a negative address, or a length without its buffer")
+        if len(eos) > FSM_MAX_EOS or any(not -2 ** 31 <= e < 2 ** 31 for e in eos):
+            raise ValueError(f"fsm row {i}: at most {FSM_MAX_EOS} EOS ids, each an int32, got {eos!r}")
+        arr[i] = (ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], ptrs[5], ptrs[6], ptrs[7], int(gen_len), int(n_states), int(n_edges),
+                  len(eos), eos + [0] * (FSM_MAX_EOS - len(eos)))
+    return arr
+
+
+def pack_fsm_rows(rows: Sequence[tuple], device):
+    """Device form of `fsm_rows_array(rows)`: a uint8 tensor [len(rows), 96] for ops.fsm_rows."""
+    import torch
+    arr = fsm_rows_array(rows)
+    return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), FSM_ROW_BYTES)).to(device)
 
 
 # ---- additive adjustments: struct vt_bias_row and the host statement of vt_bias_rows' contract --------------------------------------

@@ -38,7 +38,7 @@ from . import ops
 from .engine import PagedKVCache, SequenceState, llama_forward, pair_lo, parse_kv_cache_dtype
 from .picker import device_history
 from .sampling import (BIAS_ROWS_MAX_V, LogitAdjust, SamplingParams, check_constraints, flatten_ban_seqs, mask_words, pack_ban_rows,
-                       pack_bias_rows, pack_sample_rows, pack_trunc_rows, step_allow_mask)
+                       pack_bias_rows, pack_fsm_rows, pack_sample_rows, pack_trunc_rows, step_allow_mask)
 
 
 @dataclass
@@ -77,8 +77,10 @@ class _Request:
     adj_buf: Optional[torch.Tensor] = None           # device fp32 [V, 2]: the (pre, post) pairs vt_bias_rows writes, vt_sample_rows_adj reads
     adj_ids: Optional[torch.Tensor] = None           # device int32 / fp32: the logit bias, uploaded once
     adj_vals: Optional[torch.Tensor] = None
-    gen: Optional[torch.Tensor] = None               # device int32 [max_new_tokens]: the tokens fed back (what the penalties count over)
-    gen_len: int = 0
+    gen: Optional[torch.Tensor] = None               # device int32 [max_new_tokens]: the tokens fed back (what the penalties count over,
+    gen_len: int = 0                                 # what an automaton's state moves over)
+    fsm_cell: Optional[torch.Tensor] = None          # device int32 [2]: {state, consumed} of sampling.automaton
+    fsm_mask: Optional[torch.Tensor] = None          # device int32 [ceil(V / 32)]: the working mask vt_fsm_rows writes before every pick
 
 
 class ServingEngine:
@@ -130,6 +132,8 @@ class ServingEngine:
         eos_set = frozenset(eos) if isinstance(eos, (list, tuple, set, frozenset)) else (frozenset([eos]) if eos is not None else frozenset())
         if sampling is not None and sampling.constrained:
             check_constraints(sampling, eos_set, int(self.model.config.vocab_size))     # ValueError: nothing is queued
+            if sampling.automaton is not None:
+                sampling.automaton.check(int(self.model.config.vocab_size), sorted(eos_set))
         if adjust is not None:                   # rejected here too
             if not isinstance(adjust, LogitAdjust):
                 raise TypeError(f"submit(adjust=...) takes a LogitAdjust, got {type(adjust).__name__}")
@@ -177,6 +181,7 @@ class ServingEngine:
         r.allow_dev, r.allow_host, r.allow_cur, r.allow_at = {}, {}, None, -1
         r.ban_mask = r.ban_seqs = None
         r.adj_buf = r.adj_ids = r.adj_vals = r.gen = None
+        r.fsm_cell = r.fsm_mask = None
 
     def _prepare_allow(self, r: _Request) -> None:
         """The allow mask of r's next pick: a pure host function of (r.sampling, r.tokens, r.eos) -- the host has read back
@@ -212,6 +217,12 @@ class ServingEngine:
         of all such rows, and those rows' allow pointers name their working masks. Nothing is uploaded per step but the 48-byte rows, and
         the masks are never read back: a row they leave nothing for returns what vt_sample_rows_allow defines for it instead of failing.
         While no active request carries such a ban the launches are exactly the ones above.
+        A request with SamplingParams(automaton=A) keeps a {state, consumed} cell, one working mask and the tokens it
+        has generated on the device; A's tables are uploaded once per device and shared. ONE vt_fsm_rows launch, in front of the ban
+        launch, moves every such row's state over the token fed last and turns (the mask above as base, or NULL; the state) into its
+        working mask, which is the base of its vt_ban_row when it has a device ban too and what its allow pointer names otherwise.
+        Nothing is uploaded per step but the 96-byte rows; the request's mask_uploads counts only what its other constraints cost.
+        While no active request carries an automaton the launches are exactly the ones above.
         A request with `adjust` owns a [V][2] adjustment, its bias and its generated tokens on the device: ONE
         vt_bias_rows launch serves every row that needs a rebuild (a row with penalties at every pick, a bias-only row at its first pick
         only), the launch is vt_sample_rows_adj and the row's adjust pointer names its buffer; all other rows pass NULL. While no
@@ -246,19 +257,39 @@ class ServingEngine:
                 if r.sampling is not None and r.sampling.constrained:
                     self._prepare_allow(r)
             allow = [r.allow_cur for r in reqs]
+            fsm = [r for r in reqs if r.sampling is not None and r.sampling.automaton is not None]
+            if fsm:
+                V = int(logits.shape[1])
+                fsm_rows = []
+                for r in fsm:
+                    if r.allow_cur is not None and r.allow_cur.numel() != mask_words(V):        # (the base is read for ceil(V / 32) words)
+                        raise ValueError(f"request {r.rid}: its allow mask has {r.allow_cur.numel()} words, the logits have {V} columns")
+                    A = r.sampling.automaton
+                    if r.fsm_cell is None:
+                        r.fsm_cell = torch.tensor([A.start, 0], dtype=torch.int32).to(logits.device)
+                        r.fsm_mask = torch.empty((mask_words(V),), dtype=torch.int32, device=logits.device)
+                        if r.gen is None:
+                            r.gen = torch.zeros((max(r.max_new_tokens, 1),), dtype=torch.int32, device=logits.device)
+                    n_gen = min(r.gen_len, int(r.gen.numel()))
+                    fsm_rows.append((r.gen.data_ptr() if n_gen else 0, n_gen, r.fsm_cell.data_ptr(),
+                                     0 if r.allow_cur is None else r.allow_cur.data_ptr(), r.fsm_mask.data_ptr(), *A.row_fields(logits.device),
+                                     sorted(r.eos)))
+                ops.fsm_rows(pack_fsm_rows(fsm_rows, logits.device), len(fsm_rows), V)
+                allow = [r.fsm_mask if (r.sampling is not None and r.sampling.automaton is not None) else a for r, a in zip(reqs, allow)]
             ban = [r for r in reqs if r.sampling is not None and r.sampling.device_bans]
             if ban:
                 V = int(logits.shape[1])
                 ban_rows = []
                 for r in ban:
-                    if r.allow_cur is not None and r.allow_cur.numel() != mask_words(V):        # (the base is read for ceil(V / 32) words)
-                        raise ValueError(f"request {r.rid}: its allow mask has {r.allow_cur.numel()} words, the logits have {V} columns")
+                    base = r.fsm_mask if r.sampling.automaton is not None else r.allow_cur      # the automaton's mask holds allow_cur already
+                    if base is not None and base.numel() != mask_words(V):                      # (the base is read for ceil(V / 32) words)
+                        raise ValueError(f"request {r.rid}: its allow mask has {base.numel()} words, the logits have {V} columns")
                     if r.ban_mask is None:
                         r.ban_mask = torch.empty((mask_words(V),), dtype=torch.int32, device=logits.device)
                         if r.sampling.bad_words:
                             r.ban_seqs = torch.from_numpy(flatten_ban_seqs(r.sampling.bad_words)).to(logits.device)
                     n_ints = 0 if r.ban_seqs is None else int(r.ban_seqs.numel())
-                    ban_rows.append((r.hist.data_ptr(), r.hist_len, 0 if r.allow_cur is None else r.allow_cur.data_ptr(),
+                    ban_rows.append((r.hist.data_ptr(), r.hist_len, 0 if base is None else base.data_ptr(),
                                      r.ban_mask.data_ptr(), r.sampling.no_repeat_ngram_size,
                                      0 if r.ban_seqs is None else r.ban_seqs.data_ptr(), len(r.sampling.bad_words or ()), n_ints))
                 ops.ban_rows(pack_ban_rows(ban_rows, logits.device), len(ban_rows), V)
@@ -278,7 +309,7 @@ class ServingEngine:
                     if r.adjust.bias:
                         r.adj_ids = torch.tensor([t for t, _ in r.adjust.bias], dtype=torch.int32).to(dev)
                         r.adj_vals = torch.tensor([v for _, v in r.adjust.bias], dtype=torch.float32).to(dev)
-                    if r.adjust.penalties:
+                    if r.adjust.penalties and r.gen is None:
                         r.gen = torch.zeros((max(r.max_new_tokens, 1),), dtype=torch.int32, device=dev)
                 elif r.adj_buf.numel() != 2 * V:                  # (the buffer is read for 2 * V floats)
                     raise ValueError(f"request {r.rid}: its adjustment was built for V = {r.adj_buf.numel() // 2}, the logits have {V} columns")
