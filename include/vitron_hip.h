@@ -102,6 +102,8 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
  * vt_beam_step do not change. */
 /* 114 also carries vt_fsm_rows and struct vt_fsm_row WITHOUT a bump: one new symbol and one new struct; vt_ban_rows and the samplers do
  * not change. */
+/* 114 also carries vt_cfg_rows and struct vt_cfg_row WITHOUT a bump: one new symbol and one new struct; vt_logprob_rows, vt_ban_rows,
+ * vt_fsm_rows and the samplers do not change. */
 #define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
@@ -666,6 +668,51 @@ int vt_logprob_rows(const float* logits, int rows, int V, int ldl,
                     const int* target /* DEVICE int32 [rows], or NULL */, int n_top /* 0 .. VT_LOGPROB_MAX_TOP */,
                     float* lse /* [rows] or NULL */, float* target_lp /* [rows] or NULL */, int* target_rank /* [rows] or NULL */,
                     int* top_ids /* [rows][n_top] */, float* top_lp /* [rows][n_top] */, void* stream);
+
+/* CLASSIFIER-FREE GUIDANCE (the role of transformers' UnbatchedClassifierFreeGuidanceLogitsProcessor -- guidance_scale /
+ * negative_prompt_ids -- and of contrastive decoding: two torch.log_softmax and a blend over rows, five or six launches and three [B, V]
+ * temporaries as torch ops). A row names the logits of the same step under two contexts; the guided row goes in front of every other
+ * logits processor and of the samplers. Nothing is read on the host.
+ * rows: DEVICE array of n_rows vt_cfg_row (56 bytes each, 8-byte aligned; the offsets are part of the ABI):
+ *    0 const float*    cond         DEVICE conditional logit row, fp32 [V]; NULL = this row is skipped entirely, nothing is written
+ *    8 const float*    uncond       DEVICE unconditional logit row, fp32 [V]
+ *   16 float*          out          DEVICE guided row, fp32 [V]; MAY alias cond (in place); must NOT alias uncond
+ *   24 const uint32_t* base         DEVICE allow mask to start from, ceil(V / 32) words; NULL = every id of [0, V) allowed
+ *   32 uint32_t*       mask_out     DEVICE plausibility mask to write, ceil(V / 32) words; NULL = none is written
+ *   40 float*          lse_out      DEVICE two floats {lse_c, lse_u}; NULL = not written
+ *   48 fp32            scale        the guidance scale s
+ *   52 fp32            log_beta     log(beta), computed on the host; -inf = no plausibility cut
+ * Per row, everything in fp32, c = cond, u = uncond:
+ *     lse_c = m_c + logf(sum_i expf(c_i - m_c)),  m_c = max_i c_i        (vt_logprob_rows' expression and reduction order; lse_u likewise)
+ *     cl = c_i - lse_c;  ul = u_i - lse_u;  out_i = ul + s * (cl - ul)   -- the two subtractions, the inner subtraction, the product and
+ *       the sum are each rounded to nearest on their own (no fused multiply-add anywhere), so out follows BIT FOR BIT from the inputs and
+ *       the two values written to lse_out
+ *     mask_out bit i = base bit i AND (c_i >= m_c + log_beta), i in [0, V)   (beta in (0, 1]: a token stays iff p_cond >= beta max p_cond)
+ * Word / bit layout: vt_sample_rows_allow's (token i is bit (i & 31) of word (i >> 5)). Bits at positions >= V of the last word follow
+ * vt_ban_rows: copied from base as they are, clear when base is NULL. A NaN c_i fails the comparison (its bit is clear); the maxima skip
+ * NaNs (fmaxf) while the sums do not, so a row that holds a NaN has a NaN lse and a NaN guided row. +-inf and NaN propagate by IEEE
+ * rules, nothing is special-cased (log_beta = -inf with m_c = +inf gives a NaN threshold, which clears every bit).
+ * No value read from a row is used as an index. cond, uncond and out must be readable / writable for V floats and 4-byte aligned, base
+ * and mask_out for ceil(V / 32) words; words and floats of larger buffers behind them are not touched. out must not alias another row's
+ * input or output, mask_out must NOT alias base.
+ * Refused with VT_STATUS_ARG and a message before any launch: rows == NULL, n_rows <= 0, V <= 0, V > VT_LOGPROB_MAX_V, rows not 8-byte
+ * aligned.
+ * One launch, one 1024-thread block per row, no workspace, no atomics. Two forms, chosen per ROW: V <= 32 * 1024 with cond, uncond and
+ * out 16-byte aligned -- both rows are read once with 16-byte loads, 2 x 32 values per thread, and everything runs over registers; any
+ * other V or alignment -- a thread re-reads its elements (L2) for the sums and again for the write. In place is safe in both: a thread
+ * writes only elements it has read itself, after the block-wide reductions.
+ * 114 carries this entry point WITHOUT a bump: one new symbol and one new struct, nothing existing changes (see the note at VT_ABI_VERSION). */
+typedef struct vt_cfg_row {
+  const float* cond;
+  const float* uncond;
+  float* out;
+  const uint32_t* base;
+  uint32_t* mask_out;
+  float* lse_out;
+  float scale;
+  float log_beta;
+} vt_cfg_row;
+int vt_cfg_rows(const vt_cfg_row* rows /* DEVICE */, int n_rows, int V, void* stream);
 
 /* vt_kv_copy_pages: for every layer and every i < n, page src_pages[i] is copied onto page dst_pages[i] in both the K pool and the V^T
  * pool (k / vt: [num_layers][num_pages][page_bytes] each). It counts in bytes -- page_bytes = heads * 64 * head_dim * element size, a

@@ -122,6 +122,7 @@ SIGNATURES = {
     "vt_ban_rows": (_i, [vp, _i, _i, vp]),
     "vt_bias_rows": (_i, [vp, _i, _i, vp]),
     "vt_fsm_rows": (_i, [vp, _i, _i, vp]),
+    "vt_cfg_rows": (_i, [vp, _i, _i, vp]),
     "vt_projector_workspace_bytes": (_sz, [_i, _i]),
     "vt_projector_forward": (_i, [vp, _i, _i, vp, vp, _i, vp, vp, _i, vp, vp, _sz, vp]),
     "vt_projector_precise_workspace_bytes": (_sz, [_i, _i, _i]),

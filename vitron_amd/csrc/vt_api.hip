@@ -509,6 +509,7 @@ int vt_ban_rows(const vt_ban_row* rows, int n_rows, int V, void* stream) { retur
 int vt_bias_rows(const vt_bias_row* rows, int n_rows, int V, void* stream) { return vt_bias_rows_launch(rows, n_rows, V, S(stream)); }
 // ---- token automata (vt_fsm.hip) -----------------------------------------------------------------------------------------
 int vt_fsm_rows(const vt_fsm_row* rows, int n_rows, int V, void* stream) { return vt_fsm_rows_launch(rows, n_rows, V, S(stream)); }
+int vt_cfg_rows(const vt_cfg_row* rows, int n_rows, int V, void* stream) { return vt_cfg_rows_launch(rows, n_rows, V, S(stream)); }
 
 // ---- mm_projector ---------------------------------------------------------------------------------------------------
 size_t vt_projector_workspace_bytes(int M, int Dh) { return align_up((size_t)M * Dh * 2, 256) + 256; }

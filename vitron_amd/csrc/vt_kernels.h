@@ -284,6 +284,9 @@ int vt_ban_rows_launch(const vt_ban_row* rows, int n_rows, int V, hipStream_t s)
 // ---- vt_fsm.hip -----------------------------------------------------------------------------------
 int vt_fsm_rows_launch(const vt_fsm_row* rows, int n_rows, int V, hipStream_t s);
 
+// ---- vt_cfg.hip -----------------------------------------------------------------------------------
+int vt_cfg_rows_launch(const vt_cfg_row* rows, int n_rows, int V, hipStream_t s);
+
 // ---- vt_bias.hip ----------------------------------------------------------------------------------
 int vt_bias_rows_launch(const vt_bias_row* rows, int n_rows, int V, hipStream_t s);
 

@@ -890,8 +890,10 @@ class DecodeState:
         t = self.tok_pin[slot].tolist()
         return t[0], [bool(f) for f in t[1]]
 
-    def forward(self) -> torch.Tensor:
-        """One decoder pass over the rows feed() just wrote; fp32 logits [B, V]. No host -> device traffic."""
+    def forward(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One decoder pass over the rows feed() just wrote; fp32 logits [B, V]. No host -> device traffic. out: a contiguous fp32
+        [B, V_pad] buffer of the caller's to write the logits to (a caller that has handed its address to the device, as guided
+        generate() does); the default is a fresh tensor per pass."""
         if self.passes >= self.fed:
             raise _lib.VitronHipError("DecodeState.forward: feed() the sampled tokens first")
         llama, B = self.llama, self.B
@@ -901,7 +903,12 @@ class DecodeState:
                 raise _lib.VitronHipError(f"llama_forward: position {s.length} beyond rope table ({llama.rope_len})")
             if s.length + 1 > len(s.pages) * PAGE_TOKENS:
                 raise _lib.VitronHipError("DecodeState.forward: more steps than pages were reserved for")
-        logits = torch.empty((B, llama.V_pad), dtype=torch.float32, device=llama.device)
+        if out is None:
+            logits = torch.empty((B, llama.V_pad), dtype=torch.float32, device=llama.device)
+        else:
+            if out.dtype != torch.float32 or tuple(out.shape) != (B, llama.V_pad) or not out.is_contiguous() or out.device != self.x.device:
+                raise _lib.VitronHipError(f"DecodeState.forward: out must be a contiguous fp32 [{B}, {llama.V_pad}] tensor on the model's device")
+            logits = out
         if getattr(self.kv, "kv_dtype", "16bit") == "fp8":
             nt = int(self.table.numel())
             ws = llama.ws.get(lib.vt_llama_workspace_bytes_kv8(C.byref(llama.model), B, B, B, self.max_len, nt))

@@ -533,8 +533,27 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         wait, no per-step upload. The call's EOS ids are allowed exactly in the accepting states (min_new_tokens still withholds them).
         The device-built mask is never read back: a state that allows nothing cannot raise. ValueError before the prefill: more than 4
         EOS ids, an accepting state with no EOS id in [0, vocab_size), a start state that allows nothing, automaton together with
-        choices. Refused with NotImplementedError: num_beams > 1, padded_batch."""
-        from ...picker import StepPicker, resolve_generate_args
+        choices. Refused with NotImplementedError: num_beams > 1, padded_batch.
+        Classifier-free guidance (transformers' guidance_scale / negative_prompt_ids, its
+        UnbatchedClassifierFreeGuidanceLogitsProcessor), taken from **kwargs: guidance_scale = s (None or 1 is off and the call runs the
+        launches it always ran), negative_prompt_ids ([B, Ln], or [1, Ln] for every sample; None: each sample's last token, a
+        ValueError when that is a sentinel), negative_attention_mask, negative_images / negative_regions (for the sentinels of the negative
+        prompt, as images / regions are for input_ids; with a [1, Ln] prompt they are given once and used for every sample) and
+        guidance_plausibility = beta in [0, 1] (0 is off; contrastive decoding's cut: a token stays only if p_cond >= beta max p_cond).
+        The call owns 2B sequences: the conditional prefill is the unguided call's (same packing, same prefix reuse, so the step-0
+        conditional logits are bit-identical), the negative prompts are prefilled in a pass of their own and neither take nor leave a KV
+        prefix, and one DecodeState steps all 2B with the picked ids fed twice. A step is one decoder pass over 2B rows, ONE vt_cfg_rows
+        launch that writes scale * (log_softmax(cond) - log_softmax(uncond)) + log_softmax(uncond) in place over the conditional rows, then
+        the picker as it is: penalties, bias, masks, the sampler, return_logprobs and top_logprobs all see the guided row (transformers
+        runs its CFG processor first). return_logits keeps returning the conditional model rows. Every step's vt_cfg_row array is
+        uploaded once before the loop. With beta > 0 the picker runs per row and the launch also writes each row's plausibility mask
+        from (the step's static mask, the conditional row); that mask is the base of vt_fsm_rows / vt_ban_rows or what the sampler
+        reads. ValueError before any device work: a scale that is not finite, beta outside [0, 1], a negative_* argument or beta
+        without a scale, an empty negative prompt or one whose batch size is neither 1 nor B. Refused with NotImplementedError:
+        num_beams > 1, padded_batch."""
+        from ...picker import StepPicker, negative_prompt, resolve_generate_args
+        guide = {k: kwargs.pop(k, None) for k in ("guidance_scale", "negative_prompt_ids", "negative_attention_mask", "negative_images",
+                                                  "negative_regions", "guidance_plausibility")}
         a = resolve_generate_args(
             self.config, input_ids.shape[1], do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k,
             max_new_tokens=max_new_tokens, max_length=max_length, stopping_criteria=stopping_criteria, eos_token_id=eos_token_id,
@@ -544,8 +563,12 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
             allowed_token_ids=allowed_token_ids, num_return_sequences=num_return_sequences, length_penalty=length_penalty,
             early_stopping=early_stopping, no_repeat_ngram_size=no_repeat_ngram_size, sequence_bias=sequence_bias,
             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p, typical_p=typical_p,
-            epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, top_logprobs=top_logprobs, automaton=automaton, choices=choices)
+            epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, top_logprobs=top_logprobs, automaton=automaton, choices=choices,
+            batch_size=input_ids.shape[0], **guide)
         dev = self.device
+        neg_ids = neg_mask = None
+        if a.guided and a.num_beams == 1:
+            neg_ids, neg_mask = negative_prompt(input_ids, attention_mask, guide["negative_prompt_ids"], guide["negative_attention_mask"])
         input_ids = input_ids.to(dev)
         B, L0 = input_ids.shape
         max_new_tokens, eos_ids = a.max_new_tokens, sorted(a.eos)
@@ -559,9 +582,21 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         if a.num_beams > 1:
             return self._generate_beams(a, input_ids, seqs, flat, flat_lo, lens)
         pad_mode, ids_valid = self._padded_batch_rules(a.padded_batch, input_ids, attention_mask, embeds_spliced, S, lens)
-        kept = self._ensure_generate_pages(seqs, lens, max_new_tokens, kept, S if pad_mode else None)
+        tower_items = self.last_tower_items
+        nseqs, nlens = [], []
+        if a.guided:     # the negative prompts: B more sequences, embedded without the feature cache (they leave no prefix signature)
+            n_img, n_reg = guide["negative_images"], guide["negative_regions"]
+            if guide["negative_prompt_ids"] is not None and guide["negative_prompt_ids"].shape[0] == 1 and B > 1:
+                n_img = None if n_img is None else list(n_img) * B
+                n_reg = None if n_reg is None else list(n_reg) * B
+            nemb, nmask_host, _ = self._embed_prompt(neg_ids.to(dev), neg_mask, n_img, n_reg, use_vis_cache=False)
+            nflat, nflat_lo, nlens, _ = self._pack_rows(nemb, nmask_host)
+            nseqs = [SequenceState() for _ in range(B)]
+        kept = self._ensure_generate_pages(seqs, lens + nlens, max_new_tokens, kept, S if pad_mode else None)
         self.last_generate_stats = {"prompt_rows": int(sum(lens)), "reused_tokens": int(kept),
-                                    "prefill_rows": int(sum(lens) - kept), "tower_items": self.last_tower_items}
+                                    "prefill_rows": int(sum(lens) - kept), "tower_items": tower_items}
+        if a.guided:
+            self.last_generate_stats["negative_rows"] = int(sum(nlens))
         if kept:
             flat, lens = flat[kept:], [lens[0] - kept]
             flat_lo = None if flat_lo is None else flat_lo[kept:]
@@ -583,6 +618,12 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                 for b, lg in fix["pad_logits"].items():       # shorter samples: the first token comes from their last PAD row
                     logits[b] = lg
                 self.last_generate_stats["padded_batch"] = {"pad_rows": {b: S - lens[b] for b in fix["pad_logits"]}, "masked_rows": fix["holes"]}
+            bufs = None
+            if a.guided:     # a pass of their own; the steps' vt_cfg_row arrays name these rows and the two decode buffers: one upload
+                ulogits = llama_forward(llama, self.kv, nseqs, nflat, nlens, embeds_lo=nflat_lo)
+                if max_new_tokens > 1:
+                    bufs = [torch.empty((2 * B, llama.V_pad), dtype=torch.float32, device=dev) for _ in range(2)]
+                picker.attach_guidance(logits, ulogits, bufs)
             for step in range(max_new_tokens):
                 if a.return_logits:
                     all_logits.append(logits.clone())
@@ -594,11 +635,12 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                     fin = [t in a.eos for t in toks]
                 else:
                     if state is None:
-                        state = DecodeState(llama, self.kv, seqs, max_new_tokens, eos_ids, a.pad)
-                    slot = state.feed(nxt)
-                    if not last:
-                        logits = state.forward()          # speculative: rolled back below if this token ends the run
+                        state = DecodeState(llama, self.kv, seqs + nseqs, max_new_tokens, eos_ids, a.pad)
+                    slot = state.feed(torch.cat((nxt, nxt)) if a.guided else nxt)
+                    if not last:                          # speculative: rolled back below if this token ends the run
+                        logits = state.forward(bufs[(step + 1) & 1])[:B] if a.guided else state.forward()
                     toks, fin = state.read(slot)
+                    toks, fin = toks[:B], fin[:B]
                 out_host[:, n_out] = torch.tensor(toks, dtype=torch.long)
                 n_out += 1
                 stop = all(fin)
@@ -610,6 +652,8 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                     break
         finally:
             self._leave_prefix(sig, seqs, out_host[0, L0:n_out])
+            for s in nseqs:
+                self.kv.release(s.pages)
         out = out_host[:, :n_out].to(dev)
         res = (out,) + ((all_logits,) if a.return_logits else ()) + ((picker.logprobs(n_out - L0),) if a.return_logprobs else ()) \
             + ((picker.top(n_out - L0),) if a.top_logprobs else ())

@@ -743,6 +743,23 @@ def fsm_rows(rows_dev: torch.Tensor, n_rows: int, V: int) -> None:
     _lib.check(lib.vt_fsm_rows(_p(rows_dev) if n_rows > 0 else None, n_rows, int(V), _stream()), "vt_fsm_rows", lib)
 
 
+def cfg_rows(rows_dev: Optional[torch.Tensor], n_rows: int, V: int) -> None:
+    """Classifier-free guidance over n_rows logit rows on the device: out = ul + scale * (cl - ul) from the log-softmaxes of a conditional
+    and an unconditional row, optionally the plausibility mask and the two lse values; see vt_cfg_rows in include/vitron_hip.h. rows_dev:
+    the device array of vt_cfg_row that sampling.pack_cfg_rows builds (contiguous uint8, n_rows x 56 bytes). Every pointer inside it is
+    dereferenced on the device as it is: the caller keeps the buffers alive until the launch has run, sizes `cond`, `uncond` and `out`
+    for V floats and `base` / `mask_out` for ceil(V / 32) words; `out` may be `cond` itself and nothing else that the launch reads."""
+    from .sampling import CFG_ROW_BYTES
+    lib = _lib.load_any()
+    n_rows = int(n_rows)
+    if rows_dev is not None and n_rows > 0:
+        _chk(rows_dev, torch.uint8, "cfg_rows.rows_dev")
+        if rows_dev.numel() != n_rows * CFG_ROW_BYTES:
+            raise _lib.VitronHipError(f"cfg_rows.rows_dev: expected {n_rows} x {CFG_ROW_BYTES} bytes (sampling.pack_cfg_rows), got "
+                                      f"{rows_dev.numel()}")
+    _lib.check(lib.vt_cfg_rows(_p(rows_dev) if rows_dev is not None else None, n_rows, int(V), _stream()), "vt_cfg_rows", lib)
+
+
 def bias_rows(rows_dev: torch.Tensor, n_rows: int, V: int) -> None:
     """Build the additive adjustments of n_rows rows on the device (logit bias, presence and frequency penalties over the generated
     ids); see vt_bias_rows in include/vitron_hip.h. rows_dev: the device array of vt_bias_row that sampling.pack_bias_rows builds

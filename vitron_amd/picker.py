@@ -5,11 +5,15 @@ work, in a fixed order. `StepPicker` is built from that record once, before the 
 need (the static allow masks and every step's pointer array, every step's vt_sample_row / vt_ban_row / vt_bias_row array, the device
 histories, the adjustment buffers, an automaton's cells and row array) and
 then serves `pick(step, logits) -> ids` without an upload or a host wait. `device_history` is the one builder of a penalty / ban
-history; ServingEngine fills a request's `hist` with it too.
+history; ServingEngine fills a request's `hist` with it too. With guidance_scale `negative_prompt` yields the second
+prompt of every sample and `StepPicker.attach_guidance` uploads every step's vt_cfg_row array between the prefills and the loop.
+
 """
 from __future__ import annotations
 
 import dataclasses
+import math
+import numbers
 from dataclasses import dataclass
 from typing import Any, FrozenSet, List, Optional, Tuple
 
@@ -18,9 +22,9 @@ import torch
 
 from . import ops
 from .engine import parse_kv_cache_dtype
-from .sampling import (BAN_ROW_BYTES, BIAS_ROW_BYTES, BIAS_ROWS_MAX_V, FSM_ROW_BYTES, ROW_BYTES, allow_mask, check_penalties, check_sampling_values,
-                       check_top_logprobs, check_truncation_values, mask_words, normalise_bias, pack_ban_rows, pack_bias_rows, pack_fsm_rows,
-                       pack_sample_rows, pack_trunc_rows, truncation_active)
+from .sampling import (BAN_ROW_BYTES, BIAS_ROW_BYTES, BIAS_ROWS_MAX_V, CFG_ROW_BYTES, FSM_ROW_BYTES, ROW_BYTES, allow_mask, check_penalties,
+                       check_sampling_values, check_top_logprobs, check_truncation_values, log_beta, mask_words, normalise_bias, pack_ban_rows,
+                       pack_bias_rows, pack_cfg_rows, pack_fsm_rows, pack_sample_rows, pack_trunc_rows, truncation_active)
 
 
 @dataclass(frozen=True, eq=False)
@@ -56,6 +60,12 @@ class GenerateArgs:
     trunc: Tuple[float, float, float, float] = (0.0, 1.0, 0.0, 0.0)   # (min_p, typical_p, epsilon_cutoff, eta_cutoff); off when greedy
     top_logprobs: int = 0                        # N > 0: every step's N most likely tokens and the chosen token's rank (vt_logprob_rows)
     automaton: Any = None                        # a TokenAutomaton every row runs from its start state (vt_fsm_rows)
+    guidance_scale: Optional[float] = None       # classifier-free guidance (vt_cfg_rows); None is off (a scale of 1 resolves to it)
+    guidance_plausibility: float = 0.0           # beta of the adaptive plausibility cut; 0 is off
+
+    @property
+    def guided(self) -> bool:
+        return self.guidance_scale is not None
 
     @property
     def constrained(self) -> bool:
@@ -79,7 +89,7 @@ class GenerateArgs:
     def per_row(self) -> bool:
         """Does a step need the per-row sampler (vt_sample_rows) instead of vt_argmax / vt_sample_top_p?"""
         return (float(self.repetition_penalty) != 1.0 or bool(self.return_logprobs) or self.constrained or self.ngram > 0
-                or self.adjusted or self.truncated or self.automaton is not None)
+                or self.adjusted or self.truncated or self.automaton is not None or self.guidance_plausibility > 0)
 
 
 def static_mask_schedule(V: int, steps: int, banned_always, banned_begin, min_new: int, eos, allowed_ids):
@@ -109,7 +119,9 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
                           suppress_tokens, begin_suppress_tokens, min_new_tokens, bad_words_ids, allowed_token_ids, num_return_sequences,
                           length_penalty, early_stopping, no_repeat_ngram_size, sequence_bias=None, presence_penalty=0.0,
                           frequency_penalty=0.0, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None,
-                          top_logprobs=0, automaton=None, choices=None) -> GenerateArgs:
+                          top_logprobs=0, automaton=None, choices=None, guidance_scale=None, negative_prompt_ids=None,
+                          negative_attention_mask=None, negative_images=None, negative_regions=None, guidance_plausibility=0.0,
+                          batch_size=None) -> GenerateArgs:
     """generate()'s keyword arguments as a GenerateArgs. Raises, in this order and before any device work: the argument errors of
     num_beams / no_repeat_ngram_size, everything a beam call refuses, the padded_batch refusals that depend on arguments alone, the
     sampling values, the constraint arguments, a step the constraints leave no token for, constraints with padded_batch, the values of
@@ -117,7 +129,11 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
     eta_cutoff (None is off, as in GenerationConfig; ignored without do_sample), those four with padded_batch, the value of top_logprobs
     (an int in [0, 20]; a beam call refuses it with its other optional arguments), top_logprobs with padded_batch, automaton / choices
     with padded_batch, and what TokenAutomaton.check refuses for the call's EOS ids (a beam call refuses `automaton` with its other
-    optional arguments; choices=[...] is automaton=TokenAutomaton.from_choices(...), giving both is a ValueError). The sample seed
+    optional arguments; choices=[...] is automaton=TokenAutomaton.from_choices(...), giving both is a ValueError), and last the
+    guidance arguments: ValueError for a guidance_scale that is not a finite number, a guidance_plausibility outside
+    [0, 1], a negative_* argument or a plausibility > 0 without a guidance_scale other than 1, an empty negative prompt or one whose batch
+    size is neither 1 nor `batch_size`; NotImplementedError with padded_batch (a beam call refuses guidance_scale with its other optional
+    arguments). guidance_scale None or 1 is off and resolves to None. The sample seed
     is drawn from torch's global CPU generator (so torch.manual_seed makes sampling reproducible, as with GenerationMixin.sample) and
     only when sampling without `seed`, after the beam refusals: greedy and refused calls leave the RNG state alone."""
     num_beams = int(num_beams)
@@ -158,7 +174,8 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
         + tuple(f"{name}=..." for name, value, off in (("min_p", min_p, 0.0), ("typical_p", typical_p, 1.0),
                                                        ("epsilon_cutoff", epsilon_cutoff, 0.0), ("eta_cutoff", eta_cutoff, 0.0))
                 if value is not None and value != off)
-        + (("top_logprobs=...",) if top_logprobs else ()) + (("automaton=...",) if automaton is not None else ()))
+        + (("top_logprobs=...",) if top_logprobs else ()) + (("automaton=...",) if automaton is not None else ())
+        + (("guidance_scale=...",) if guidance_scale is not None and guidance_scale != 1 else ()))
     if num_beams > 1:
         check_beam_arguments(a, int(config.vocab_size))
     elif a.num_return_sequences != 1:
@@ -220,7 +237,82 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
             raise NotImplementedError("generate(padded_batch=True) does not take automaton / choices; use the default packed batch")
         automaton.check(V, sorted(a.eos))
         a = dataclasses.replace(a, automaton=automaton)
+    scale, beta = check_guidance(guidance_scale, guidance_plausibility, negative_prompt_ids, negative_attention_mask, negative_images,
+                                 negative_regions, batch_size)
+    if scale is not None:
+        if padded_batch:
+            raise NotImplementedError("generate(padded_batch=True) does not take guidance_scale; use the default packed batch")
+        a = dataclasses.replace(a, guidance_scale=scale, guidance_plausibility=beta)
     return a
+
+
+def check_guidance(guidance_scale, guidance_plausibility, negative_prompt_ids, negative_attention_mask, negative_images, negative_regions,
+                   batch_size, what: str = "generate"):
+    """The values of the guidance arguments, before any device work: returns (scale or None when guidance is off, beta)."""
+    def num(x):
+        return isinstance(x, numbers.Real) and not isinstance(x, bool)
+    if guidance_scale is not None and (not num(guidance_scale) or not math.isfinite(guidance_scale)):
+        raise ValueError(f"{what}: guidance_scale must be None or a finite number (None and 1 are off), got {guidance_scale!r}")
+    beta = guidance_plausibility
+    if beta is None:
+        beta = 0.0
+    if not num(beta) or not 0 <= beta <= 1:       # (a NaN fails both comparisons)
+        raise ValueError(f"{what}: guidance_plausibility must be a number in [0, 1] (0 is off), got {guidance_plausibility!r}")
+    on = guidance_scale is not None and guidance_scale != 1
+    if not on:
+        for name, value in (("negative_prompt_ids", negative_prompt_ids), ("negative_attention_mask", negative_attention_mask),
+                            ("negative_images", negative_images), ("negative_regions", negative_regions)):
+            if value is not None and guidance_scale is None:
+                raise ValueError(f"{what}: {name} needs guidance_scale")
+        if beta > 0:
+            raise ValueError(f"{what}: guidance_plausibility needs a guidance_scale other than 1")
+        return None, 0.0
+    if negative_prompt_ids is None:
+        for name, value in (("negative_attention_mask", negative_attention_mask), ("negative_images", negative_images),
+                            ("negative_regions", negative_regions)):
+            if value is not None:
+                raise ValueError(f"{what}: {name} needs negative_prompt_ids")
+    else:
+        shape = tuple(getattr(negative_prompt_ids, "shape", ()))
+        if len(shape) != 2:
+            raise ValueError(f"{what}: negative_prompt_ids must be a [B, Ln] or [1, Ln] tensor of ids, got shape {shape}")
+        if shape[1] == 0 or shape[0] == 0:
+            raise ValueError(f"{what}: negative_prompt_ids is empty (shape {shape})")
+        if batch_size is not None and shape[0] not in (1, int(batch_size)):
+            raise ValueError(f"{what}: negative_prompt_ids has batch size {shape[0]}, expected 1 or {int(batch_size)}")
+        if negative_attention_mask is not None:
+            if tuple(negative_attention_mask.shape) != shape:
+                raise ValueError(f"{what}: negative_attention_mask has shape {tuple(negative_attention_mask.shape)}, negative_prompt_ids {shape}")
+            if not bool((negative_attention_mask != 0).any(-1).all()):
+                raise ValueError(f"{what}: negative_attention_mask leaves a negative prompt empty")
+    return float(guidance_scale), float(beta)
+
+
+def negative_prompt(input_ids: torch.Tensor, attention_mask, negative_prompt_ids, negative_attention_mask):
+    """The [B, Ln] negative prompt of a guided call and its mask (or None). Without negative_prompt_ids it is the last token of every
+    sample's input_ids -- the last one its attention_mask keeps -- as transformers' UnbatchedClassifierFreeGuidanceLogitsProcessor takes
+    input_ids[:, -1:]; an image / region sentinel there raises ValueError. A [1, Ln] prompt is every sample's."""
+    B = input_ids.shape[0]
+    if negative_prompt_ids is None:
+        ids = input_ids.cpu()
+        if attention_mask is None:
+            last = ids[:, -1:]
+        else:
+            am = attention_mask.cpu() != 0
+            if not bool(am.any(-1).all()):
+                raise ValueError("generate(guidance_scale=...): a sample without a valid token has no default negative prompt")
+            idx = (am.long() * torch.arange(1, ids.shape[1] + 1)).argmax(-1, keepdim=True)
+            last = ids.gather(1, idx)
+        if bool((last < 0).any()):
+            raise ValueError("generate(guidance_scale=...): the default negative prompt is each sample's last token, which is an image / "
+                             "region sentinel here; give negative_prompt_ids")
+        return last.to(input_ids.device), None
+    neg = negative_prompt_ids.to(input_ids.device)
+    am = negative_attention_mask
+    if neg.shape[0] == 1 and B > 1:
+        neg = neg.expand(B, -1).contiguous()
+        am = None if am is None else am.expand(B, -1).contiguous()
+    return neg, am
 
 
 def check_beam_arguments(a: GenerateArgs, V: int) -> None:
@@ -304,7 +396,14 @@ class StepPicker:
     The histories grow on the device. The device-built masks and adjustments are never read back.
     With top_logprobs = N > 0, in every mode: the [steps, B, N] id and log-probability buffers and the [steps, B] rank
     buffer are allocated here, and every pick is followed by ONE ops.logprob_rows launch over the step's RAW logits with the picked ids
-    as targets, which writes step `step` of them -- no allocation, no upload, no host wait. The pick itself is the launch it was."""
+    as targets, which writes step `step` of them -- no allocation, no upload, no host wait. The pick itself is the launch it was.
+    With guidance_scale, in every mode: `attach_guidance`, called once between the prefills and the loop, uploads the
+    [steps, B] vt_cfg_row array over the addresses the steps' logits will have (the two prefills' rows at step 0, the caller's two
+    alternating [2B, V_pad] decode buffers after it), and every pick starts with ONE ops.cfg_rows launch that writes the guided rows in
+    place over the conditional ones. Everything behind it -- penalties and bias, masks, the sampler, return_logprobs, top_logprobs --
+    sees the guided row. With guidance_plausibility > 0 the mode is per-row: the launch also writes the B working masks
+    (base = the step's static mask or NULL), which take the static mask's place as the `base` of the vt_fsm_row array, or of the
+    vt_ban_row array when there is no automaton, or as the sampler's allow pointers when there is neither."""
 
     def __init__(self, a: GenerateArgs, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], V: int):
         self.a = a
@@ -318,6 +417,8 @@ class StepPicker:
             self.top_ids = torch.empty((n, B, a.top_logprobs), dtype=torch.int32, device=self.device)
             self.top_lp = torch.empty((n, B, a.top_logprobs), dtype=torch.float32, device=self.device)
             self.top_rank = torch.empty((n, B), dtype=torch.int32, device=self.device)
+        self.cfg_rows = self.cfg_ptrs = self.cfg_mask_ptr = None
+        self.step_base: List[int] = [0] * max(a.max_new_tokens, 0)
         if self.mode != "rows":
             return
         dev, steps = self.device, a.max_new_tokens
@@ -333,6 +434,13 @@ class StepPicker:
             [(T, k, p, float(a.repetition_penalty), a.sample_seed, st, b,
               0 if self.hist is None else self.hist.row_ptr(b), 0 if self.hist is None else self.hist.lens[b] + st)
              for st in range(steps) for b in range(B)], dev).view(steps, B, ROW_BYTES)
+        self.step_base = step_base
+        cfg_ptr = None
+        if a.guidance_plausibility > 0:          # the plausibility masks vt_cfg_rows writes stand where the static masks stood
+            self.cfg_work = cw = torch.empty((B, mask_words(self.V)), dtype=torch.int32, device=dev)
+            cfg_ptr = [cw.data_ptr() + 4 * b * cw.stride(0) for b in range(B)]
+            self.cfg_ptrs = torch.tensor(cfg_ptr, dtype=torch.int64).to(dev)
+        self.cfg_mask_ptr = cfg_ptr
         self.fsm_rows = None
         ban_base = step_base
         if a.automaton is not None:
@@ -345,7 +453,7 @@ class StepPicker:
             self.ban_hist = h = _History(input_ids, steps, attention_mask)
             self.ban_work = w = torch.empty((B, mask_words(self.V)), dtype=torch.int32, device=dev)
             work_ptr = [w.data_ptr() + 4 * b * w.stride(0) for b in range(B)]
-            self.ban_rows = pack_ban_rows([(h.row_ptr(b), h.lens[b] + st, fsm_ptr[b] if ban_base is None else ban_base[st], work_ptr[b],
+            self.ban_rows = pack_ban_rows([(h.row_ptr(b), h.lens[b] + st, fsm_ptr[b] if ban_base is None else (ban_base[st] if cfg_ptr is None else cfg_ptr[b]), work_ptr[b],
                                             a.ngram, 0, 0, 0)
                                            for st in range(steps) for b in range(B)], dev).view(steps, B, BAN_ROW_BYTES)
             self.ban_ptrs = torch.tensor(work_ptr, dtype=torch.int64).to(dev)
@@ -379,8 +487,30 @@ class StepPicker:
             self.fsm_cell = c = torch.tensor([[a.automaton.start, 0]] * B, dtype=torch.int32).to(dev)
             cell_ptr = [c.data_ptr() + 8 * b for b in range(B)]
             tables, eos = a.automaton.row_fields(dev), sorted(a.eos)
-            self.fsm_rows = pack_fsm_rows([(gen_ptr[b] if st else 0, st, cell_ptr[b], step_base[st], fsm_ptr[b], *tables, eos)
+            self.fsm_rows = pack_fsm_rows([(gen_ptr[b] if st else 0, st, cell_ptr[b], step_base[st] if cfg_ptr is None else cfg_ptr[b], fsm_ptr[b], *tables, eos)
                                            for st in range(steps) for b in range(B)], dev).view(steps, B, FSM_ROW_BYTES)
+
+    def attach_guidance(self, cond0: torch.Tensor, uncond0: torch.Tensor, bufs) -> None:
+        """Upload every step's vt_cfg_row array, once. cond0 / uncond0: the fp32 [B, V] logits of the two prefills (step 0). bufs: the two
+        contiguous fp32 [2B, V_pad] buffers the decode passes write in turn -- step st >= 1 reads bufs[st & 1], rows [0, B) conditional and
+        rows [B, 2B) unconditional. The guided row goes in place over the conditional one."""
+        a, B = self.a, self.B
+        if not a.guided or a.max_new_tokens <= 0:
+            return
+        if cond0.shape[1] != self.V or uncond0.shape[1] != self.V:
+            raise RuntimeError(f"generate: guidance was set up for V = {self.V}, the logits have {cond0.shape[1]} columns")
+        lb = log_beta(a.guidance_plausibility)
+
+        def row_ptr(t, r):
+            return t.data_ptr() + 4 * r * t.stride(0)
+
+        rows = []
+        for st in range(a.max_new_tokens):
+            for b in range(B):
+                c, u = (row_ptr(cond0, b), row_ptr(uncond0, b)) if st == 0 else (row_ptr(bufs[st & 1], b), row_ptr(bufs[st & 1], B + b))
+                rows.append((c, u, c, self.step_base[st], 0 if self.cfg_mask_ptr is None else self.cfg_mask_ptr[b], 0, a.guidance_scale, lb))
+        self._cfg_keep = (cond0, uncond0, bufs)
+        self.cfg_rows = pack_cfg_rows(rows, self.device).view(a.max_new_tokens, B, CFG_ROW_BYTES)
 
     def check_width(self, logits: torch.Tensor) -> None:
         if self.mode == "rows" and (self.a.constrained or self.a.ngram or self.a.automaton is not None) and logits.shape[1] != self.V:
@@ -389,6 +519,8 @@ class StepPicker:
             raise RuntimeError(f"generate: the logit adjustments were built for V = {self.V}, the logits have {logits.shape[1]} columns")
 
     def pick(self, step: int, logits: torch.Tensor) -> torch.Tensor:
+        if self.cfg_rows is not None:            # the guided rows, in place over the conditional ones `logits` names: one launch
+            ops.cfg_rows(self.cfg_rows[step], self.B, self.V)
         nxt = self._pick_ids(step, logits)
         if self.a.top_logprobs:                  # the distribution behind the pick: RAW logits, the picked ids as targets
             ops.logprob_rows(logits, nxt, self.a.top_logprobs, out={"rank": self.top_rank[step], "top_ids": self.top_ids[step],
@@ -402,6 +534,8 @@ class StepPicker:
         if self.mode == "top_p":   # device-side temperature / top-k / top-p sampler (no host sync, counter-based RNG)
             return ops.sample_top_p(logits, a.temperature, a.top_p if a.top_p else 1.0, a.sample_seed, step, top_k=int(a.top_k or 0))
         ptrs = None if self.allow_ptrs is None else self.allow_ptrs[step]
+        if self.cfg_ptrs is not None:            # the plausibility masks ops.cfg_rows has just written (they start from the static one)
+            ptrs = self.cfg_ptrs
         if self.fsm_rows is not None:            # the rows' states catch up with what they emitted; their masks for this pick: one launch
             ops.fsm_rows(self.fsm_rows[step], self.B, self.V)
             ptrs = self.fsm_ptrs

@@ -23,6 +23,10 @@ Token automata: `SamplingParams(automaton=A)` holds the reply t
 (a regex over the vocabulary's strings, a set of choices). The allowed set depends on where the reply stands, so the mask is built on the
 DEVICE from a two-int cell per request (struct vt_fsm_row, `pack_fsm_rows`, ops.fsm_rows); nothing is uploaded per step.
 
+Classifier-free guidance: `SamplingParams(guidance_scale=s, negative_prompt_ids=...)` blends the request's logits with
+those of a second sequence that runs its negative prompt, in front of everything above: struct vt_cfg_row (`pack_cfg_rows`,
+ops.cfg_rows); `log_beta` is the field of generate()'s plausibility cut.
+
 Top-N log-probabilities: `SamplingParams(top_logprobs=N)` asks for the N most likely tokens and the chosen token's rank
 at every generated token; they come from one vt_logprob_rows launch behind the pick and need no struct here.
 """
@@ -62,6 +66,14 @@ FSM_ROW_DTYPE = np.dtype({
 })
 FSM_ROW_BYTES = FSM_ROW_DTYPE.itemsize
 FSM_MAX_EOS = 4                    # the eos[4] of vt_fsm_row
+# struct vt_cfg_row: the offsets are part of the ABI (tests/test_cfg_ref_host.py checks them against the header's table)
+CFG_ROW_DTYPE = np.dtype({
+    "names": ["cond", "uncond", "out", "base", "mask_out", "lse_out", "scale", "log_beta"],
+    "formats": ["<u8", "<u8", "<u8", "<u8", "<u8", "<u8", "<f4", "<f4"],
+    "offsets": [0, 8, 16, 24, 32, 40, 48, 52],
+    "itemsize": 56,
+})
+CFG_ROW_BYTES = CFG_ROW_DTYPE.itemsize
 # struct vt_bias_row: the offsets are part of the ABI (tests/test_bias_ref_host.py checks them against the header's table)
 BIAS_ROW_DTYPE = np.dtype({
     "names": ["history", "bias_ids", "bias_vals", "out", "history_len", "n_bias", "presence", "frequency"],
@@ -216,16 +228,29 @@ class SamplingParams(_SamplingFields):
     (ServingEngine.top_logprobs; one vt_logprob_rows launch per step). It implies what logprobs=True collects. repr shows it when set.
     automaton is a sixth: None, or a vitron_amd.automaton.TokenAutomaton the reply has to follow (guided decoding by
     regex or choices). It makes the request `constrained`; its mask is built on the device by vt_fsm_rows from the request's own
-    {state, consumed} cell and intersects with every other constraint. Compared and hashed by identity; repr shows it when set."""
+    {state, consumed} cell and intersects with every other constraint. Compared and hashed by identity; repr shows it when set.
+    guidance_scale and negative_prompt_ids are of the same kind: classifier-free guidance against a TEXT-ONLY negative
+    prompt (a sequence of ids >= 0, stored as a tuple; None: the last token of the request's prompt). None or 1 is off. A guided request
+    owns a second sequence and two decode rows; its logits are blended by vt_cfg_rows in front of everything else the request asks for.
+    guidance_plausibility and negative_images exist to be refused (NotImplementedError): the engine runs neither. repr shows them when set."""
+    GUIDE_NAMES = ("guidance_scale", "negative_prompt_ids", "guidance_plausibility", "negative_images")
     TRUNC_NAMES = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
     TOP_LOGPROBS_MAX = 20                        # VT_LOGPROB_MAX_TOP
 
     def __init__(self, *args, min_p: float = 0.0, typical_p: float = 1.0, epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0,
-                 top_logprobs: int = 0, automaton=None, **kw):
+                 top_logprobs: int = 0, automaton=None, guidance_scale=None, negative_prompt_ids=None, guidance_plausibility=0.0,
+                 negative_images=None, **kw):
         for name, value in zip(self.TRUNC_NAMES, (min_p, typical_p, epsilon_cutoff, eta_cutoff)):
             object.__setattr__(self, name, value)
         object.__setattr__(self, "top_logprobs", top_logprobs)
         object.__setattr__(self, "automaton", automaton)
+        if negative_prompt_ids is not None:      # a tensor, an array or a sequence (one prompt; a [1, Ln] batch of one is taken as it)
+            flat = np.asarray(negative_prompt_ids.cpu() if hasattr(negative_prompt_ids, "cpu") else negative_prompt_ids)
+            if flat.ndim == 2 and flat.shape[0] == 1:
+                flat = flat[0]
+            negative_prompt_ids = tuple(flat.tolist()) if flat.ndim == 1 else flat
+        for name, value in zip(self.GUIDE_NAMES, (guidance_scale, negative_prompt_ids, guidance_plausibility, negative_images)):
+            object.__setattr__(self, name, value)
         super().__init__(*args, **kw)            # (its __post_init__ validates: the four are set by then)
 
     def __setattr__(self, name, value):          # (the frozen base guards its own fields only once it is subclassed)
@@ -242,6 +267,29 @@ class SamplingParams(_SamplingFields):
             from .automaton import TokenAutomaton
             if not isinstance(self.automaton, TokenAutomaton):
                 raise ValueError(f"SamplingParams: automaton must be a TokenAutomaton or None, got {self.automaton!r}")
+        if self.negative_images is not None:
+            raise NotImplementedError("SamplingParams: negative_images is not implemented (the engine's negative prompt is text-only; use "
+                                      "generate(negative_images=...))")
+        if self.guidance_plausibility:
+            raise NotImplementedError("SamplingParams: guidance_plausibility is not implemented in the engine; use "
+                                      "generate(guidance_plausibility=...)")
+        g = self.guidance_scale
+        if g is not None and (not isinstance(g, numbers.Real) or isinstance(g, bool) or not math.isfinite(g)):
+            raise ValueError(f"SamplingParams: guidance_scale must be None or a finite number (None and 1 are off), got {g!r}")
+        n = self.negative_prompt_ids
+        if n is not None:
+            if g is None:
+                raise ValueError("SamplingParams: negative_prompt_ids needs guidance_scale")
+            if not isinstance(n, tuple) or not n:
+                raise ValueError("SamplingParams: negative_prompt_ids must be one non-empty sequence of token ids")
+            if any(not isinstance(t, numbers.Integral) or isinstance(t, bool) or t < 0 for t in n):
+                raise ValueError("SamplingParams: negative_prompt_ids is text-only here: every entry must be a token id >= 0 (no image / "
+                                 "region sentinels)")
+
+    @property
+    def guided(self) -> bool:
+        """Does the request run classifier-free guidance (a second sequence, vt_cfg_rows in front of its pick)?"""
+        return self.guidance_scale is not None and self.guidance_scale != 1
 
     @property
     def constrained(self) -> bool:
@@ -257,7 +305,8 @@ class SamplingParams(_SamplingFields):
 
     def _key(self) -> tuple:
         return tuple(getattr(self, n) for n in self.__dataclass_fields__) + self.trunc_row_raw() + (int(self.top_logprobs),) \
-            + (None if self.automaton is None else id(self.automaton),)
+            + (None if self.automaton is None else id(self.automaton),) \
+            + ((self.guidance_scale, self.negative_prompt_ids) if self.guidance_scale is not None or self.negative_prompt_ids is not None else ())
 
     def __eq__(self, other):
         return self._key() == other._key() if other.__class__ is self.__class__ else NotImplemented
@@ -271,11 +320,13 @@ class SamplingParams(_SamplingFields):
             names.append("top_logprobs")
         if self.automaton is not None:
             names.append("automaton")
+        names += [n for n, off in zip(self.GUIDE_NAMES, (None, None, 0.0, None)) if getattr(self, n) is not off and getattr(self, n) != off]
         return "SamplingParams(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in names) + ")"
 
     def replace(self, **changes) -> "SamplingParams":
         """A copy with some settings changed (dataclasses.replace knows only the dataclass fields)."""
-        kw = {n: getattr(self, n) for n in list(self.__dataclass_fields__) + list(self.TRUNC_NAMES) + ["top_logprobs", "automaton"]}
+        kw = {n: getattr(self, n) for n in list(self.__dataclass_fields__) + list(self.TRUNC_NAMES) + ["top_logprobs", "automaton"]
+              + list(self.GUIDE_NAMES)}
         kw.update(changes)
         return SamplingParams(**kw)
 
@@ -538,6 +589,37 @@ def pack_fsm_rows(rows: Sequence[tuple], device):
     import torch
     arr = fsm_rows_array(rows)
     return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), FSM_ROW_BYTES)).to(device)
+
+
+# ---- classifier-free guidance: struct vt_cfg_row (the host statement of the contract is tests/cfg_ref.py) -----------------------------
+def log_beta(beta: float) -> float:
+    """The `log_beta` field of vt_cfg_row for a plausibility beta in [0, 1]: log(beta), -inf (no cut) for beta == 0."""
+    return math.log(beta) if beta > 0 else -math.inf
+
+
+def cfg_rows_array(rows: Sequence[tuple]) -> np.ndarray:
+    """Host array of vt_cfg_row from one tuple per row:
+        (cond_ptr, uncond_ptr, out_ptr, base_ptr, mask_out_ptr, lse_out_ptr, scale, log_beta)
+    cond_ptr == 0 makes the row one the kernel skips. The pointers are DEVICE addresses (tensor.data_ptr(), 0 for NULL) whose owners the
+    caller keeps alive until the launch has run; out_ptr may equal cond_ptr (in place) and must not equal uncond_ptr."""
+    arr = np.zeros((len(rows),), dtype=CFG_ROW_DTYPE)
+    for i, (cond, uncond, out, base, mask_out, lse_out, scale, lb) in enumerate(rows):
+        ptrs = [int(x) for x in (cond, uncond, out, base, mask_out, lse_out)]
+        if min(ptrs) < 0 or (ptrs[0] and not (ptrs[1] and ptrs[2])):
+            raise ValueError(f"cfg row {i}: a negative address, or a conditional row without its uncond and out")
+        if ptrs[0] and ptrs[2] == ptrs[1]:
+            raise ValueError(f"cfg row {i}: out must not alias uncond")
+        if ptrs[0] and ptrs[4] and ptrs[4] == ptrs[3]:
+            raise ValueError(f"cfg row {i}: mask_out must not alias base")
+        arr[i] = (*ptrs, float(scale), float(lb))
+    return arr
+
+
+def pack_cfg_rows(rows: Sequence[tuple], device):
+    """Device form of `cfg_rows_array(rows)`: a uint8 tensor [len(rows), 56] for ops.cfg_rows."""
+    import torch
+    arr = cfg_rows_array(rows)
+    return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), CFG_ROW_BYTES)).to(device)
 
 
 # ---- additive adjustments: struct vt_bias_row and the host statement of vt_bias_rows' contract --------------------------------------

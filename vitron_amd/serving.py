@@ -38,7 +38,7 @@ from . import ops
 from .engine import PagedKVCache, SequenceState, llama_forward, pair_lo, parse_kv_cache_dtype
 from .picker import device_history
 from .sampling import (BIAS_ROWS_MAX_V, LogitAdjust, SamplingParams, check_constraints, flatten_ban_seqs, mask_words, pack_ban_rows,
-                       pack_bias_rows, pack_fsm_rows, pack_sample_rows, pack_trunc_rows, step_allow_mask)
+                       pack_bias_rows, pack_cfg_rows, pack_fsm_rows, pack_sample_rows, pack_trunc_rows, step_allow_mask)
 
 
 @dataclass
@@ -81,6 +81,15 @@ class _Request:
     gen_len: int = 0                                 # what an automaton's state moves over)
     fsm_cell: Optional[torch.Tensor] = None          # device int32 [2]: {state, consumed} of sampling.automaton
     fsm_mask: Optional[torch.Tensor] = None          # device int32 [ceil(V / 32)]: the working mask vt_fsm_rows writes before every pick
+    nseq: Optional[SequenceState] = None             # a guided request's second sequence: its negative prompt
+    neg_ids: Optional[torch.Tensor] = None           # device ids [1, Ln] of the negative prompt (text only)
+    neg_flat: Optional[torch.Tensor] = None          # its embedded rows [Ln, H] (kept while the request waits for pages)
+    need_neg: int = 0                                # the part of `need` that is the second sequence's
+
+    @property
+    def rows(self) -> int:
+        """Decode rows the request takes in a step: a guided one runs its negative sequence beside its own."""
+        return 2 if self.nseq is not None else 1
 
 
 class ServingEngine:
@@ -120,7 +129,10 @@ class ServingEngine:
         adjust: this request's own LogitAdjust: a logit bias added before the repetition penalty, presence / frequency
         penalties over the tokens it has generated after it. Its tokens equal generate(sequence_bias=..., presence_penalty=...,
         frequency_penalty=...) for the request alone, whatever else is in the batch; a request with `adjust` and without `sampling` keeps
-        its legacy row parameters."""
+        its legacy row parameters.
+        sampling.guidance_scale (None or 1 is off): classifier-free guidance against sampling.negative_prompt_ids (text
+        only; None: the prompt's last token, a ValueError when that is a sentinel). The request owns a second sequence and takes two of
+        max_batch's rows; its tokens equal generate(guidance_scale=, negative_prompt_ids=) for the request alone."""
         ids = input_ids if input_ids.dim() == 2 else input_ids.unsqueeze(0)
         if ids.shape[0] != 1:
             raise ValueError("submit() takes one sequence per request")
@@ -134,6 +146,18 @@ class ServingEngine:
             check_constraints(sampling, eos_set, int(self.model.config.vocab_size))     # ValueError: nothing is queued
             if sampling.automaton is not None:
                 sampling.automaton.check(int(self.model.config.vocab_size), sorted(eos_set))
+        neg = None
+        if sampling is not None and sampling.guided:
+            if self.max_batch < 2:
+                raise ValueError("submit(sampling=SamplingParams(guidance_scale=...)): a guided request takes two decode rows, max_batch is "
+                                 f"{self.max_batch}")
+            if sampling.negative_prompt_ids is not None:
+                neg = torch.tensor([list(sampling.negative_prompt_ids)], dtype=ids.dtype)
+            else:                                # transformers' default: the last token of the prompt
+                neg = ids[:, -1:].cpu()
+                if int(neg[0, 0]) < 0:
+                    raise ValueError("submit(sampling=SamplingParams(guidance_scale=...)): the default negative prompt is the prompt's last "
+                                     "token, which is an image / region sentinel here; give negative_prompt_ids")
         if adjust is not None:                   # rejected here too
             if not isinstance(adjust, LogitAdjust):
                 raise TypeError(f"submit(adjust=...) takes a LogitAdjust, got {type(adjust).__name__}")
@@ -145,6 +169,8 @@ class ServingEngine:
                 adjust = None
         r = _Request(self._next_id, ids.to(self.model.device), images, regions, int(max_new_tokens), eos_set, sampling=sampling,
                      adjust=adjust)
+        if neg is not None:
+            r.nseq, r.neg_ids = SequenceState(), neg.to(self.model.device)
         self._next_id += 1
         self.waiting.append(r)
         return r.rid
@@ -157,19 +183,40 @@ class ServingEngine:
         for r in self.waiting:
             if r.rid == rid:
                 self.waiting.remove(r)
-                r.flat = r.last_top = None
+                r.flat = r.last_top = r.neg_flat = None
                 self._drop_masks(r)
                 return True
         return False
 
     def _fail(self, r: _Request, exc: BaseException) -> None:
         """The request failed on its own: it leaves the engine with its exception; nothing else is disturbed."""
-        if r.seq.pages:
-            self.model.kv.release(r.seq.pages)
-        r.seq.pages, r.seq.length, r.last, r.flat, r.hist, r.last_lp, r.last_top = [], 0, None, None, None, None, None
+        self._release(r)
+        r.last, r.flat, r.hist, r.last_lp, r.last_top, r.neg_flat = None, None, None, None, None, None
         self._drop_masks(r)
         r.error, r.done = exc, True
         self.failed[r.rid] = r
+
+    def _release(self, r: _Request) -> None:
+        """The request's pages, those of a guided request's second sequence included, go back to the pool."""
+        for q in (r.seq, r.nseq):
+            if q is not None:
+                if q.pages:
+                    self.model.kv.release(q.pages)
+                q.pages, q.length = [], 0
+
+    def _guide(self, logits: torch.Tensor, reqs: List[_Request], uncond: Dict[int, torch.Tensor]) -> None:
+        """Classifier-free guidance in front of _pick: ONE vt_cfg_rows launch over the rows of `logits` writes the guided
+        row in place over the conditional row of every guided request (uncond[i]: the fp32 [V] row of reqs[i]'s negative sequence);
+        every other row carries cond = NULL and is untouched."""
+        V = int(logits.shape[1])
+        rows = []
+        for i, r in enumerate(reqs):
+            if i in uncond:
+                c = logits[i].data_ptr()
+                rows.append((c, uncond[i].data_ptr(), c, 0, 0, 0, float(r.sampling.guidance_scale), -float("inf")))
+            else:
+                rows.append((0, 0, 0, 0, 0, 0, 1.0, -float("inf")))
+        ops.cfg_rows(pack_cfg_rows(rows, logits.device), len(rows), V)
 
     @staticmethod
     def _is_device_error(exc: BaseException) -> bool:
@@ -368,6 +415,10 @@ class ServingEngine:
                 try:
                     r.flat = self._embed(r)
                     r.need = (r.flat.shape[0] + r.max_new_tokens + 63) // 64 + 1
+                    if r.nseq is not None:                  # a guided request reserves its second sequence's worst case too
+                        r.neg_flat = m.get_model().embed_tokens(r.neg_ids)[0]
+                        r.need_neg = (r.neg_flat.shape[0] + r.max_new_tokens + 63) // 64 + 1
+                        r.need += r.need_neg
                 except Exception as e:  # noqa: BLE001 -- classified below
                     if self._is_device_error(e):
                         for q in reversed([x for x in reqs if x.error is None]):
@@ -402,12 +453,14 @@ class ServingEngine:
                                                    + (f" (capped at {self.kv_cap})" if self.kv_cap is not None else "")))
                         continue
                     break                                   # wait for running requests to retire (or for an idle engine to grow the pool)
-                r.seq.pages = m.kv.alloc(r.need)
+                pages = m.kv.alloc(r.need)
+                r.seq.pages = pages[:r.need - r.need_neg]
+                if r.nseq is not None:
+                    r.nseq.pages = pages[r.need - r.need_neg:]
                 admitted.append(r)
         except Exception:
             for r in admitted:
-                m.kv.release(r.seq.pages)
-                r.seq.pages = []
+                self._release(r)
             for r in reversed(live):
                 if r.error is None:
                     self.waiting.appendleft(r)
@@ -415,9 +468,15 @@ class ServingEngine:
         rest = [r for r in live if r.error is None and r not in admitted]
         ok: List[_Request] = []
 
+        def prefill_neg(r):      # a guided request's negative prompt: always a solo pass, as in generate() for the request alone
+            return llama_forward(llama, m.kv, [r.nseq], r.neg_flat, [r.neg_flat.shape[0]])[0]
+
         def prefill_one(r):
             try:
-                r.last = self._pick(llama_forward(llama, m.kv, [r.seq], r.flat, [r.flat.shape[0]], embeds_lo=getattr(r, "flat_lo", None)), [r])
+                logits = llama_forward(llama, m.kv, [r.seq], r.flat, [r.flat.shape[0]], embeds_lo=getattr(r, "flat_lo", None))
+                if r.nseq is not None:
+                    self._guide(logits, [r], {0: prefill_neg(r)})
+                r.last = self._pick(logits, [r])
                 ok.append(r)
             except Exception as e:  # noqa: BLE001
                 if self._is_device_error(e):
@@ -443,6 +502,9 @@ class ServingEngine:
                     if any(l is not None for l in los):      # (requests without visual rows have an exact 16-bit embedding: low half zero)
                         lo_cat = torch.cat([l if l is not None else torch.zeros_like(f) for l, f in zip(los, flats)], 0)
                     logits = llama_forward(llama, m.kv, [r.seq for r in admitted], torch.cat(flats, 0), [f.shape[0] for f in flats], embeds_lo=lo_cat)
+                    unc = {i: prefill_neg(r) for i, r in enumerate(admitted) if r.nseq is not None}
+                    if unc:
+                        self._guide(logits, admitted, unc)
                     nxt = self._pick(logits, admitted)
                     for i, r in enumerate(admitted):
                         r.last = nxt[i:i + 1]
@@ -452,6 +514,8 @@ class ServingEngine:
                         raise
                     for r in admitted:                      # find the culprit: every request on its own (a solo prefill is always legal)
                         r.seq.length = 0
+                        if r.nseq is not None:
+                            r.nseq.length = 0
                         prefill_one(r)
             else:
                 for r in admitted:
@@ -459,21 +523,20 @@ class ServingEngine:
         except Exception:                                   # device-level: pages back, every surviving candidate queued again
             for r in admitted:
                 if r.error is None:
-                    m.kv.release(r.seq.pages)
-                    r.seq.pages, r.seq.length, r.last = [], 0, None
+                    self._release(r)
+                    r.last = None
             for r in reversed(live):
                 if r.error is None:
                     self.waiting.appendleft(r)
             raise
         for r in ok:
-            r.flat = r.flat_lo = None                       # the rows are in the cache now
+            r.flat = r.flat_lo = r.neg_flat = None                       # the rows are in the cache now
         self.active += ok
         return rest
 
     def _retire(self, r: _Request) -> None:
         r.done = True
-        self.model.kv.release(r.seq.pages)
-        r.seq.pages = []
+        self._release(r)
         r.hist = r.last_lp = r.last_top = None
         self._drop_masks(r)
         self.finished[r.rid] = r
@@ -481,7 +544,9 @@ class ServingEngine:
     def step(self) -> List[Tuple[int, int]]:
         """Admit waiting requests while there is room, emit one token for every active request. Returns [(request id, token)]."""
         cand: List[_Request] = []
-        while self.waiting and len(self.active) + len(cand) < self.max_batch:
+        rows = sum(r.rows for r in self.active)         # max_batch counts decode rows: a guided request takes two
+        while self.waiting and rows + self.waiting[0].rows <= self.max_batch:
+            rows += self.waiting[0].rows
             cand.append(self.waiting.popleft())
         if cand:
             for r in reversed(self._admit(cand)):          # what did not fit keeps its place at the head of the queue
@@ -532,10 +597,18 @@ class ServingEngine:
         if self.active:
             m = self.model
             llama = m.get_model().llama
-            ids = torch.cat([r.last for r in self.active]).to(torch.int32)
+            # the active sequences, then the negative sequences of the guided ones (fed the same token): one pass
+            guided = [i for i, r in enumerate(self.active) if r.nseq is not None]
+            seqs = [r.seq for r in self.active] + [self.active[i].nseq for i in guided]
+            ids = torch.cat([r.last for r in self.active] + [self.active[i].last for i in guided]).to(torch.int32)
             plan = torch.stack([torch.zeros_like(ids), ids], dim=1).contiguous()
             x = ops.embed_splice(llama.embed, None, None, plan)
-            logits = llama_forward(llama, m.kv, [r.seq for r in self.active], x, [1] * len(self.active))
+            logits = llama_forward(llama, m.kv, seqs, x, [1] * len(seqs))
+            if guided:
+                n = len(self.active)
+                unc = {i: logits[n + j] for j, i in enumerate(guided)}
+                logits = logits[:n]
+                self._guide(logits, self.active, unc)
             for r in self.active:                       # the token just fed joins the request's penalty / ban history, on the device
                 if r.hist is not None:
                     r.hist[r.hist_len:r.hist_len + 1].copy_(r.last)
