@@ -104,6 +104,8 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
  * not change. */
 /* 114 also carries vt_cfg_rows and struct vt_cfg_row WITHOUT a bump: one new symbol and one new struct; vt_logprob_rows, vt_ban_rows,
  * vt_fsm_rows and the samplers do not change. */
+/* 114 also carries vt_unit_rows, vt_contrast_rows and struct vt_contrast_row WITHOUT a bump: two new symbols and one new struct;
+ * vt_logprob_rows and vt_kv_copy_pages do not change. */
 #define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
@@ -713,6 +715,69 @@ typedef struct vt_cfg_row {
   float log_beta;
 } vt_cfg_row;
 int vt_cfg_rows(const vt_cfg_row* rows /* DEVICE */, int n_rows, int V, void* stream);
+
+/* CONTRASTIVE SEARCH (Su et al. 2022, "A Contrastive Framework for Neural Text Generation"; transformers'
+ * generate(penalty_alpha=, top_k=), whose contrastive_search / _ranking_fast are no longer part of its core). Each of a sequence's k most
+ * probable next tokens is run as a decode row; its final hidden state is compared, by cosine similarity, with the final hidden state of
+ * EVERY earlier position (the context bank, visual rows included); the candidate with the largest (1 - alpha) p - alpha max_j cos wins.
+ *
+ * vt_unit_rows: out[r][i] = op16(y_i * rnorm), y_i = w[i] * x[r][i] (w == NULL: y_i = x[r][i]), rnorm = 1 / sqrt(sum_i y_i^2), everything
+ * in fp32 (the sum by fused multiply-adds), one rounding to the operand format at the store. A row whose sum is 0 gives zeros. With
+ * w = the final RMSNorm weight and x = the fp32 stream behind the last layer this is the direction of the final-normed state: RMSNorm's
+ * per-row scalar cancels in a cosine. x: fp32 [rows][ldx], out: operand format [rows][ldo], ldx, ldo >= H; `out` must not alias `x`.
+ * Refused with VT_STATUS_ARG: x or out NULL, rows <= 0, H <= 0, ldx < H, ldo < H. One 256-thread block per row; H <= 4096 with 16-byte
+ * aligned rows is read once, anything else twice. */
+int vt_unit_rows(const float* x, int ldx, const float* w /* fp32 [H] or NULL */, uint16_t* out, int ldo, int rows, int H, void* stream);
+
+/* vt_contrast_rows: rows is a HOST array of n_groups vt_contrast_row (64 bytes each; the offsets are part of the ABI), one per sequence.
+ * It is read before the call returns and travels to the kernels by value: nothing is uploaded, and every field is checked first.
+ *    0 uint16_t*       bank         DEVICE operand format [bank_cap][H], contiguous rows: the unit vectors of the context, rows [0, bank_len)
+ *    8 const float*    cand_lp      DEVICE fp32 [k]: the candidates' log-probabilities, as vt_logprob_rows wrote them (top_lp)
+ *   16 float*          d_out        DEVICE fp32 [k]
+ *   24 float*          score_out    DEVICE fp32 [k]
+ *   32 int*            sel_out      DEVICE int32 [1]
+ *   40 int             bank_len     T: 1 <= T < bank_cap
+ *   44 int             bank_cap     rows the bank holds
+ *   48 int             k            candidates of this sequence, 1 <= k <= VT_CONTRAST_MAX_K
+ *   52 int             first        its candidates are the rows [first, first + k) of cand
+ *   56 fp32            alpha        in [0, 1]
+ *   60 int             reserved     0
+ * cand: DEVICE operand format [n_cand][ld] unit rows (vt_unit_rows), ld >= H, ld % 8 == 0, H % 32 == 0, 16-byte aligned.
+ * Per group, c in [0, k):
+ *     d[c]     = max_{j < T} dot(bank[j], cand[first + c])     fp32 accumulation of the exact products of the 16-bit values (MFMA)
+ *     score[c] = fmaf(-alpha, d[c], t),  t = (1 - alpha) * __expf(cand_lp[c])     1 - alpha and t rounded to fp32 on their own
+ *     sel      = the arg-max of those score values, exact ties to the lower c. sel starts at 0 and moves only on a strictly greater
+ *                score: it lies in [0, k) whatever the inputs (inputs are expected finite)
+ *     bank[T]  = cand[first + sel], bit for bit the vector that was compared: the bank grows on the device; bank_len is the caller's
+ * Bank rows at and beyond T are never read; rows beyond T are not written. workspace: DEVICE, at least
+ * VT_CONTRAST_WORKSPACE_BYTES(n_groups, the largest bank_len) bytes, 4-byte aligned; it holds the chunk maxima between the two stages.
+ * Refused with VT_STATUS_ARG and a message before any launch: rows or cand NULL, n_groups <= 0, n_cand <= 0, H not a positive multiple of
+ * 32, ld < H or ld % 8 != 0, cand misaligned, and per group: a NULL pointer, a misaligned bank, k outside [1, VT_CONTRAST_MAX_K],
+ * bank_len < 1, bank_len >= bank_cap, [first, first + k) outside [0, n_cand), alpha outside [0, 1]; a workspace that is NULL or too small.
+ * Two stages per 32 groups, no atomics: grid (chunks of VT_CONTRAST_CHUNK bank rows, groups) x 512 threads -- the chunk's rows are the
+ * 16-row operand of v_mfma_f32_16x16x32_{bf16,f16}, the candidates its 16 columns, both loaded from global memory straight into the
+ * fragments with 16-byte loads, K sliced over the 8 waves (80 VGPRs, no scratch, 9 KiB of LDS) -- then one 512-thread block per group:
+ * maxima, scores, selection, append.
+ * 114 carries these two entry points WITHOUT a bump: two new symbols and one new struct, nothing existing changes. */
+#define VT_CONTRAST_MAX_K 16
+#define VT_CONTRAST_CHUNK 16
+#define VT_CONTRAST_WORKSPACE_BYTES(n_groups, max_bank_len) \
+  ((size_t)(n_groups) * (size_t)(((max_bank_len) + VT_CONTRAST_CHUNK - 1) / VT_CONTRAST_CHUNK) * 16 * sizeof(float))
+typedef struct vt_contrast_row {
+  uint16_t* bank;
+  const float* cand_lp;
+  float* d_out;
+  float* score_out;
+  int* sel_out;
+  int bank_len;
+  int bank_cap;
+  int k;
+  int first;
+  float alpha;
+  int reserved;
+} vt_contrast_row;
+int vt_contrast_rows(const vt_contrast_row* rows /* HOST */, int n_groups, const uint16_t* cand, int n_cand, int ld, int H,
+                     void* workspace, size_t workspace_bytes, void* stream);
 
 /* vt_kv_copy_pages: for every layer and every i < n, page src_pages[i] is copied onto page dst_pages[i] in both the K pool and the V^T
  * pool (k / vt: [num_layers][num_pages][page_bytes] each). It counts in bytes -- page_bytes = heads * 64 * head_dim * element size, a

@@ -77,6 +77,11 @@ class VtKvCache8(C.Structure):   # the FP8 (e4m3fn) pool: the same fields, pages
     _fields_ = [("k", vp), ("vt", vp), ("num_pages", C.c_int)]
 
 
+class VtContrastRow(C.Structure):   # struct vt_contrast_row (64 bytes; a HOST array: vt_contrast_rows reads it before it returns)
+    _fields_ = [("bank", vp), ("cand_lp", vp), ("d_out", vp), ("score_out", vp), ("sel_out", vp), ("bank_len", C.c_int),
+                ("bank_cap", C.c_int), ("k", C.c_int), ("first", C.c_int), ("alpha", C.c_float), ("reserved", C.c_int)]
+
+
 _i, _f, _sz = C.c_int, C.c_float, C.c_size_t
 # name -> (restype, argtypes); this table is also what tests check against the header
 SIGNATURES = {
@@ -123,6 +128,8 @@ SIGNATURES = {
     "vt_bias_rows": (_i, [vp, _i, _i, vp]),
     "vt_fsm_rows": (_i, [vp, _i, _i, vp]),
     "vt_cfg_rows": (_i, [vp, _i, _i, vp]),
+    "vt_unit_rows": (_i, [vp, _i, vp, vp, _i, _i, _i, vp]),
+    "vt_contrast_rows": (_i, [vp, _i, vp, _i, _i, _i, vp, _sz, vp]),
     "vt_projector_workspace_bytes": (_sz, [_i, _i]),
     "vt_projector_forward": (_i, [vp, _i, _i, vp, vp, _i, vp, vp, _i, vp, vp, _sz, vp]),
     "vt_projector_precise_workspace_bytes": (_sz, [_i, _i, _i]),

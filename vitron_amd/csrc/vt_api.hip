@@ -510,6 +510,14 @@ int vt_bias_rows(const vt_bias_row* rows, int n_rows, int V, void* stream) { ret
 // ---- token automata (vt_fsm.hip) -----------------------------------------------------------------------------------------
 int vt_fsm_rows(const vt_fsm_row* rows, int n_rows, int V, void* stream) { return vt_fsm_rows_launch(rows, n_rows, V, S(stream)); }
 int vt_cfg_rows(const vt_cfg_row* rows, int n_rows, int V, void* stream) { return vt_cfg_rows_launch(rows, n_rows, V, S(stream)); }
+// ---- contrastive search (vt_contrast.hip) ------------------------------------------------------------------------------------
+int vt_unit_rows(const float* x, int ldx, const float* w, uint16_t* out, int ldo, int rows, int H, void* stream) {
+  return vt_unit_rows_launch(x, ldx, w, out, ldo, rows, H, S(stream));
+}
+int vt_contrast_rows(const vt_contrast_row* rows, int n_groups, const uint16_t* cand, int n_cand, int ld, int H, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  return vt_contrast_rows_launch(rows, n_groups, cand, n_cand, ld, H, workspace, workspace_bytes, S(stream));
+}
 
 // ---- mm_projector ---------------------------------------------------------------------------------------------------
 size_t vt_projector_workspace_bytes(int M, int Dh) { return align_up((size_t)M * Dh * 2, 256) + 256; }

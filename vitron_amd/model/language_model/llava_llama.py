@@ -550,10 +550,25 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         from (the step's static mask, the conditional row); that mask is the base of vt_fsm_rows / vt_ban_rows or what the sampler
         reads. ValueError before any device work: a scale that is not finite, beta outside [0, 1], a negative_* argument or beta
         without a scale, an empty negative prompt or one whose batch size is neither 1 nor B. Refused with NotImplementedError:
-        num_beams > 1, padded_batch."""
+        num_beams > 1, padded_batch.
+        Contrastive search (transformers' penalty_alpha / top_k, Su et al. 2022), penalty_alpha taken from **kwargs: the
+        mode is on when penalty_alpha > 0, top_k > 1, do_sample is False and num_beams == 1 (transformers' rule); penalty_alpha None or 0,
+        or top_k == 1, is off and the call runs the launches it always ran. Per sequence and step: the k = top_k most probable ids of the
+        current logit row with their probabilities p (softmax over the full vocabulary, no warper), k single-query decode rows behind
+        the same context, d = the largest cosine between a candidate's final-normed hidden state and that of EVERY earlier position
+        (prompt, visual and generated rows -- the context bank, unit vectors in the operand format), and the candidate with the largest
+        (1 - alpha) p - alpha d is emitted (ties to the lower rank); its hidden state joins the bank on the device and its logit row is the
+        next step's current row. A step is ONE vt_logprob_rows launch, one decoder pass over the live sequences' k rows, ONE vt_unit_rows
+        and ONE vt_contrast_rows launch and one read-back (the selection and the id, per sequence); a contrastive.CandidateGroup copies
+        at most k - 1 KV pages. n new tokens cost n passes of k rows. The call neither takes nor leaves a KV prefix. stopping_criteria
+        is served. ValueError before any device work: penalty_alpha not a finite number in [0, 1], or > 0 with do_sample=True. Refused
+        with NotImplementedError, naming the argument: top_k left at its default or outside [2, 16] (1 is off), num_beams > 1,
+        padded_batch, repetition_penalty != 1, every optional processor argument (suppress_tokens ... automaton), return_logits,
+        return_logprobs, top_logprobs, guidance_scale."""
         from ...picker import StepPicker, negative_prompt, resolve_generate_args
         guide = {k: kwargs.pop(k, None) for k in ("guidance_scale", "negative_prompt_ids", "negative_attention_mask", "negative_images",
                                                   "negative_regions", "guidance_plausibility")}
+        penalty_alpha = kwargs.pop("penalty_alpha", None)
         a = resolve_generate_args(
             self.config, input_ids.shape[1], do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k,
             max_new_tokens=max_new_tokens, max_length=max_length, stopping_criteria=stopping_criteria, eos_token_id=eos_token_id,
@@ -564,7 +579,7 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
             early_stopping=early_stopping, no_repeat_ngram_size=no_repeat_ngram_size, sequence_bias=sequence_bias,
             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p, typical_p=typical_p,
             epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, top_logprobs=top_logprobs, automaton=automaton, choices=choices,
-            batch_size=input_ids.shape[0], **guide)
+            batch_size=input_ids.shape[0], penalty_alpha=penalty_alpha, **guide)
         dev = self.device
         neg_ids = neg_mask = None
         if a.guided and a.num_beams == 1:
@@ -577,10 +592,12 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         S = embeds.shape[1]
         flat, flat_lo, lens, _ = self._pack_rows(embeds, mask_host)
         seqs = [SequenceState() for _ in range(B)]
-        # (a beam call neither reuses nor leaves a KV prefix)
-        sig, kept = self._take_prefix(reuse and a.num_beams == 1, input_ids, mask_host, embeds_spliced, seqs[0])
+        # (a beam call and a contrastive call neither reuse nor leave a KV prefix)
+        sig, kept = self._take_prefix(reuse and a.num_beams == 1 and not a.contrastive, input_ids, mask_host, embeds_spliced, seqs[0])
         if a.num_beams > 1:
             return self._generate_beams(a, input_ids, seqs, flat, flat_lo, lens)
+        if a.contrastive:
+            return self._generate_contrastive(a, input_ids, seqs, flat, flat_lo, lens, stopping_criteria)
         pad_mode, ids_valid = self._padded_batch_rules(a.padded_batch, input_ids, attention_mask, embeds_spliced, S, lens)
         tower_items = self.last_tower_items
         nseqs, nlens = [], []
@@ -992,6 +1009,86 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                 out[g * n_return + r, L0:L0 + len(h)] = torch.tensor(h, dtype=torch.long)
         self.last_beam_scores = torch.tensor([sc for grp in best for sc, _ in grp], dtype=torch.float32).to(dev)
         return out.to(dev)
+
+    # ---- contrastive search -------------------------------------------------------------------
+    def _generate_contrastive(self, a, input_ids, seqs, flat, flat_lo, lens, stopping_criteria):
+        """The contrastive branch of generate(): `seqs` are fresh SequenceStates, `flat` the packed prompt rows. One host round trip per
+        step: the selections and the chosen ids of the live sequences, in one copy."""
+        from ...contrastive import CandidateGroup
+        k, alpha, max_new_tokens, pad = int(a.top_k), float(a.penalty_alpha), int(a.max_new_tokens), a.pad
+        if max_new_tokens < 1:
+            raise ValueError(f"generate(penalty_alpha > 0): max_new_tokens must be >= 1, got {max_new_tokens}")
+        dev = self.device
+        llama = self.model.llama
+        B, L0 = input_ids.shape
+        need = sum((l + 63) // 64 + 1 + k + (l + max_new_tokens) // 64 - l // 64 for l in lens)
+        if self.kv is None or len(self.kv.free) < need:
+            self._ensure_kv(need)
+        self.last_generate_stats = {"prompt_rows": int(sum(lens)), "reused_tokens": 0, "prefill_rows": int(sum(lens)),
+                                    "tower_items": self.last_tower_items, "top_k": k, "penalty_alpha": alpha, "contrastive_steps": 0,
+                                    "pages_copied": 0}
+        out_host = torch.full((B, L0 + max_new_tokens), int(pad), dtype=torch.long)
+        out_host[:, :L0] = input_ids.cpu()
+        n_out = L0
+        groups = {}
+        try:
+            # the prefill, with the stream behind the last layer for EVERY row: the context bank holds the prompt's rows, visual ones included
+            cur, hidden = llama_forward(llama, self.kv, seqs, flat, lens, embeds_lo=flat_lo, return_hidden=True)
+            banks, at = [], 0
+            for b in range(B):
+                bank = torch.zeros((lens[b] + max_new_tokens, llama.H), dtype=llama.dtype, device=dev)
+                ops.unit_rows(hidden[at:at + lens[b]], llama.final_norm, out=bank[:lens[b]])
+                banks.append(bank)
+                at += lens[b]
+            self.last_generate_stats["bank_len"] = list(lens)
+            del hidden
+            for b in range(B):
+                groups[b] = CandidateGroup(llama, self.kv, seqs[b], k, max_new_tokens)
+            live = list(range(B))
+            d_t = torch.empty((B, k), dtype=torch.float32, device=dev)
+            score_t = torch.empty((B, k), dtype=torch.float32, device=dev)
+            sel_t = torch.empty((B,), dtype=torch.int32, device=dev)
+            ws = ops.contrast_workspace(B, max(lens) + max_new_tokens, dev)
+            for step in range(max_new_tokens):
+                n = len(live)
+                top = ops.logprob_rows(cur, None, k)                       # the k most probable ids of every current row, exact order
+                ids = top["top_ids"].reshape(-1)
+                plan = torch.stack((torch.zeros_like(ids), ids), 1).contiguous()
+                x = ops.embed_splice(llama.embed, None, None, plan)
+                logits, hid = llama_forward(llama, self.kv, [s for b in live for s in groups[b].seqs], x, [1] * (n * k), return_hidden=True)
+                cand = ops.unit_rows(hid, llama.final_norm, dtype=llama.dtype)
+                ops.contrast_rows([{"bank": banks[b], "bank_len": lens[b] + step, "k": k, "first": j * k, "alpha": alpha,
+                                    "lp": top["top_logprobs"][j], "d": d_t[j], "score": score_t[j], "sel": sel_t[j:j + 1]}
+                                   for j, b in enumerate(live)], cand, ws)
+                sel_dev = sel_t[:n]
+                picked = top["top_ids"].gather(1, sel_dev.long().unsqueeze(1)).squeeze(1)
+                host = torch.stack((sel_dev, picked)).cpu()               # the step's one read-back
+                sels, toks = host[0].tolist(), host[1].tolist()
+                self.last_generate_stats["contrastive_steps"] += 1
+                keep_rows, nxt_live = [], []
+                for j, b in enumerate(live):
+                    self.last_generate_stats["pages_copied"] += groups[b].select(sels[j])
+                    out_host[b, n_out] = toks[j]
+                    if toks[j] not in a.eos:
+                        keep_rows.append(j * k + sels[j])
+                        nxt_live.append(b)
+                n_out += 1
+                scores = cur
+                live = nxt_live
+                stop = not live
+                if not stop and stopping_criteria is not None:
+                    stop = any(c(out_host[:, :n_out], scores) for c in stopping_criteria)    # StoppingCriteriaList: any()
+                if stop:
+                    break
+                if step + 1 < max_new_tokens:
+                    cur = logits[torch.tensor(keep_rows, dtype=torch.long).to(dev)]           # the chosen rows: the next current rows
+        finally:
+            for grp in groups.values():
+                grp.release()
+            for s in seqs:          # prompts no group took over (a failure before or inside the prefill)
+                self.kv.release(s.pages)
+                s.pages, s.length = [], 0
+        return out_host[:, :n_out].to(dev)
 
 
 VitronLlamaForCausalLM = LlavaLlamaForCausalLM  # name used by BASELINE.json's north_star; the reference class is LlavaLlamaForCausalLM

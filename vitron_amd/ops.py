@@ -874,6 +874,84 @@ def logprob_rows(logits: torch.Tensor, targets: Optional[torch.Tensor] = None, n
     return res
 
 
+CONTRAST_MAX_K = 16                # VT_CONTRAST_MAX_K
+CONTRAST_CHUNK = 16                # VT_CONTRAST_CHUNK
+
+
+def unit_rows(x: torch.Tensor, w: Optional[torch.Tensor], out: Optional[torch.Tensor] = None, dtype=None) -> torch.Tensor:
+    """out[r] = (w * x[r]) / |w * x[r]| in the operand format, the norm and the products in fp32 (a zero row gives zeros); see vt_unit_rows in
+    include/vitron_hip.h. x: fp32 [rows, H], contiguous or a row-strided view. w: fp32 [H] or None. out: a bf16 / fp16 [rows, H] tensor or
+    row-strided view to write (e.g. rows of a context bank) -- its dtype picks the library build; without it a new tensor of `dtype`."""
+    _chk_view(x, torch.float32, "unit_rows.x")
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise _lib.VitronHipError(f"unit_rows.x: expected fp32 [rows, H] with rows, H >= 1, got {tuple(x.shape)}")
+    rows, H = x.shape
+    if w is not None:
+        _chk(w, torch.float32, "unit_rows.w")
+        if w.numel() != H or w.device != x.device:
+            raise _lib.VitronHipError(f"unit_rows.w: expected fp32 [{H}] on x's device, got {tuple(w.shape)}")
+    if out is None:
+        if dtype is None:
+            raise _lib.VitronHipError("unit_rows: give out or dtype (bf16 / fp16)")
+        out = torch.empty((rows, H), dtype=dtype, device=x.device)
+    lib, dt = _op16(out, "unit_rows.out")
+    _chk_view(out, dt, "unit_rows.out")
+    if tuple(out.shape) != (rows, H) or out.device != x.device:
+        raise _lib.VitronHipError(f"unit_rows.out: expected [{rows}, {H}] on x's device, got {tuple(out.shape)}")
+    _lib.check(lib.vt_unit_rows(_p(x), x.stride(0) if rows > 1 else H, _p(w), _p(out), out.stride(0) if rows > 1 else H, rows, H, _stream()),
+               "vt_unit_rows", lib)
+    return out
+
+
+def contrast_workspace(n_groups: int, max_bank_len: int, device) -> torch.Tensor:
+    """A workspace for contrast_rows: VT_CONTRAST_WORKSPACE_BYTES(n_groups, max_bank_len) as fp32."""
+    return torch.empty((max(int(n_groups), 1) * ((max(int(max_bank_len), 1) + CONTRAST_CHUNK - 1) // CONTRAST_CHUNK) * 16,),
+                       dtype=torch.float32, device=device)
+
+
+def contrast_rows(groups: Sequence[dict], cand: torch.Tensor, workspace: Optional[torch.Tensor] = None) -> None:
+    """The selection step of contrastive search for len(groups) sequences, on the device; see vt_contrast_rows in include/vitron_hip.h.
+    cand: bf16 / fp16 [n_cand, H] unit rows (unit_rows), contiguous or row-strided. Each group is a dict:
+      "bank"      bf16 / fp16 [cap, H] contiguous, cand's dtype: the context's unit rows in [0, bank_len); row bank_len is WRITTEN
+      "bank_len"  T, 1 <= T < cap          "k" in [1, 16]          "first": the group's candidates are cand[first : first + k]
+      "alpha"     in [0, 1]                "lp" fp32, at least k contiguous values: the candidates' log-probabilities
+      "d", "score" fp32 [>= k], "sel" int32 [>= 1]: written (contiguous)
+    Per candidate d = max_j dot(bank[j], cand), score = (1 - alpha) exp(lp) - alpha d; sel = the arg-max of the scores, ties to the lower
+    candidate; bank[T] = cand[first + sel]. The row array stays on the host (nothing is uploaded); shapes are checked here, values by the
+    launcher. workspace: fp32, contrast_workspace(len(groups), max T) elements; allocated when None."""
+    lib, dt = _op16(cand, "contrast_rows.cand")
+    _chk_view(cand, dt, "contrast_rows.cand")
+    if cand.dim() != 2:
+        raise _lib.VitronHipError(f"contrast_rows.cand: expected [n_cand, H], got {tuple(cand.shape)}")
+    n_cand, H = cand.shape
+    n = len(groups)
+    if n < 1:
+        raise _lib.VitronHipError("contrast_rows: no groups")
+    arr = (_lib.VtContrastRow * n)()
+    max_T = 1
+    for g, grp in enumerate(groups):
+        bank, k = grp["bank"], int(grp["k"])
+        _chk(bank, dt, f"contrast_rows.groups[{g}].bank")
+        if bank.dim() != 2 or bank.shape[1] != H or bank.device != cand.device:
+            raise _lib.VitronHipError(f"contrast_rows.groups[{g}].bank: expected [cap, {H}] on cand's device, got {tuple(bank.shape)}")
+        for key, tdt, need in (("lp", torch.float32, k), ("d", torch.float32, k), ("score", torch.float32, k), ("sel", torch.int32, 1)):
+            t = grp[key]
+            _chk(t, tdt, f"contrast_rows.groups[{g}].{key}")
+            if t.numel() < max(need, 1) or t.device != cand.device:
+                raise _lib.VitronHipError(f"contrast_rows.groups[{g}].{key}: expected at least {need} elements on cand's device, got {t.numel()}")
+        r = arr[g]
+        r.bank, r.cand_lp, r.d_out, r.score_out, r.sel_out = _p(bank), _p(grp["lp"]), _p(grp["d"]), _p(grp["score"]), _p(grp["sel"])
+        r.bank_len, r.bank_cap, r.k, r.first, r.alpha, r.reserved = int(grp["bank_len"]), bank.shape[0], k, int(grp["first"]), float(grp["alpha"]), 0
+        max_T = max(max_T, int(grp["bank_len"]))
+    if workspace is None:
+        workspace = contrast_workspace(n, max_T, cand.device)
+    _chk(workspace, torch.float32, "contrast_rows.workspace")
+    if workspace.device != cand.device:
+        raise _lib.VitronHipError("contrast_rows.workspace: expected a tensor on cand's device")
+    _lib.check(lib.vt_contrast_rows(arr, n, _p(cand), n_cand, cand.stride(0) if n_cand > 1 else H, H, _p(workspace), workspace.numel() * 4,
+                                    _stream()), "vt_contrast_rows", lib)
+
+
 def kv_copy_pages(kv, src_pages, dst_pages) -> None:
     """Copy page src_pages[i] onto page dst_pages[i] of a PagedKVCache, in every layer and both pools (vt_kv_copy_pages; either pool
     format). The ids are host sequences: each is checked against the pool here, and no destination may also be a source."""

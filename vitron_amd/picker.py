@@ -7,7 +7,8 @@ histories, the adjustment buffers, an automaton's cells and row array) and
 then serves `pick(step, logits) -> ids` without an upload or a host wait. `device_history` is the one builder of a penalty / ban
 history; ServingEngine fills a request's `hist` with it too. With guidance_scale `negative_prompt` yields the second
 prompt of every sample and `StepPicker.attach_guidance` uploads every step's vt_cfg_row array between the prefills and the loop.
-(DESIGN.md 9.3 - 9.12.)
+`penalty_alpha` (contrastive search) resolves to `GenerateArgs.penalty_alpha` / `.contrastive`; that mode has a loop of
+its own and no StepPicker.
 """
 from __future__ import annotations
 
@@ -62,10 +63,16 @@ class GenerateArgs:
     automaton: Any = None                        # a TokenAutomaton every row runs from its start state (vt_fsm_rows)
     guidance_scale: Optional[float] = None       # classifier-free guidance (vt_cfg_rows); None is off (a scale of 1 resolves to it)
     guidance_plausibility: float = 0.0           # beta of the adaptive plausibility cut; 0 is off
+    penalty_alpha: float = 0.0                   # contrastive search (vt_contrast_rows); 0 is off
 
     @property
     def guided(self) -> bool:
         return self.guidance_scale is not None
+
+    @property
+    def contrastive(self) -> bool:
+        """transformers' rule for the mode: penalty_alpha > 0 and top_k > 1, greedy, one beam."""
+        return self.penalty_alpha > 0 and int(self.top_k or 0) > 1 and not self.do_sample and self.num_beams == 1
 
     @property
     def constrained(self) -> bool:
@@ -121,7 +128,7 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
                           frequency_penalty=0.0, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None,
                           top_logprobs=0, automaton=None, choices=None, guidance_scale=None, negative_prompt_ids=None,
                           negative_attention_mask=None, negative_images=None, negative_regions=None, guidance_plausibility=0.0,
-                          batch_size=None) -> GenerateArgs:
+                          batch_size=None, penalty_alpha=None) -> GenerateArgs:
     """generate()'s keyword arguments as a GenerateArgs. Raises, in this order and before any device work: the argument errors of
     num_beams / no_repeat_ngram_size, everything a beam call refuses, the padded_batch refusals that depend on arguments alone, the
     sampling values, the constraint arguments, a step the constraints leave no token for, constraints with padded_batch, the values of
@@ -133,12 +140,17 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
     guidance arguments: ValueError for a guidance_scale that is not a finite number, a guidance_plausibility outside
     [0, 1], a negative_* argument or a plausibility > 0 without a guidance_scale other than 1, an empty negative prompt or one whose batch
     size is neither 1 nor `batch_size`; NotImplementedError with padded_batch (a beam call refuses guidance_scale with its other optional
-    arguments). guidance_scale None or 1 is off and resolves to None. The sample seed
+    arguments). guidance_scale None or 1 is off and resolves to None. Contrastive search: the VALUE of penalty_alpha
+    (ValueError: not a finite number in [0, 1]; > 0 together with do_sample=True) is checked right behind num_beams; a beam call refuses
+    penalty_alpha > 0 with its other optional arguments; everything else the mode refuses comes last, behind the guidance arguments, in
+    check_contrastive's order. penalty_alpha None or 0, or top_k == 1, is off. The sample seed
     is drawn from torch's global CPU generator (so torch.manual_seed makes sampling reproducible, as with GenerationMixin.sample) and
     only when sampling without `seed`, after the beam refusals: greedy and refused calls leave the RNG state alone."""
     num_beams = int(num_beams)
     if num_beams < 1:
         raise ValueError(f"generate: num_beams must be >= 1, got {num_beams}")
+    alpha = check_penalty_alpha(penalty_alpha, do_sample)
+    top_k_given = top_k
     if no_repeat_ngram_size is None:
         no_repeat_ngram_size = 0
     if not isinstance(no_repeat_ngram_size, int) or isinstance(no_repeat_ngram_size, bool) or not 0 <= no_repeat_ngram_size <= 2 ** 31 - 1:
@@ -175,7 +187,8 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
                                                        ("epsilon_cutoff", epsilon_cutoff, 0.0), ("eta_cutoff", eta_cutoff, 0.0))
                 if value is not None and value != off)
         + (("top_logprobs=...",) if top_logprobs else ()) + (("automaton=...",) if automaton is not None else ())
-        + (("guidance_scale=...",) if guidance_scale is not None and guidance_scale != 1 else ()))
+        + (("guidance_scale=...",) if guidance_scale is not None and guidance_scale != 1 else ())
+        + (("penalty_alpha=...",) if alpha > 0 else ()))
     if num_beams > 1:
         check_beam_arguments(a, int(config.vocab_size))
     elif a.num_return_sequences != 1:
@@ -243,7 +256,45 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
         if padded_batch:
             raise NotImplementedError("generate(padded_batch=True) does not take guidance_scale; use the default packed batch")
         a = dataclasses.replace(a, guidance_scale=scale, guidance_plausibility=beta)
+    if alpha > 0 and num_beams == 1:
+        check_contrastive(a, top_k_given)
+        a = dataclasses.replace(a, penalty_alpha=alpha)
     return a
+
+
+def check_penalty_alpha(penalty_alpha, do_sample, what: str = "generate") -> float:
+    """The value of penalty_alpha: None is 0 (off). ValueError for anything but a finite number in [0, 1], and for a value > 0 together with
+    do_sample=True (transformers' rule makes that a sampling call and drops the penalty silently; here it is said)."""
+    if penalty_alpha is None:
+        return 0.0
+    if not isinstance(penalty_alpha, numbers.Real) or isinstance(penalty_alpha, bool) or not 0 <= penalty_alpha <= 1:     # (a NaN fails both)
+        raise ValueError(f"{what}: penalty_alpha must be None or a finite number in [0, 1] (None and 0 are off), got {penalty_alpha!r}")
+    if penalty_alpha > 0 and do_sample:
+        raise ValueError(f"{what}: penalty_alpha={penalty_alpha!r} with do_sample=True: contrastive search is deterministic")
+    return float(penalty_alpha)
+
+
+CONTRASTIVE_MAX_K = 16          # VT_CONTRAST_MAX_K: the candidates are the 16-wide operand of one MFMA
+
+
+def check_contrastive(a: GenerateArgs, top_k_given) -> None:
+    """Everything a call with penalty_alpha > 0 and one beam refuses, before any page is taken, in this order. top_k == 1 is the mode's off
+    switch (transformers' rule) and refuses nothing. stopping_criteria is served."""
+    if top_k_given is None:
+        raise NotImplementedError("generate(penalty_alpha > 0) needs an explicit top_k in [2, 16]: the configuration's default of "
+                                  f"{a.top_k} would be {a.top_k} decode rows per sequence and step")
+    if int(top_k_given) == 1:
+        return
+    if not 2 <= int(top_k_given) <= CONTRASTIVE_MAX_K:
+        raise NotImplementedError(f"generate(penalty_alpha > 0, top_k={top_k_given!r}): top_k must lie in [2, {CONTRASTIVE_MAX_K}] "
+                                  "(vt_contrast_rows; top_k=1 switches the mode off)")
+    if a.padded_batch:
+        raise NotImplementedError("generate(penalty_alpha > 0, padded_batch=True) is not implemented: the candidates run in the packed batch")
+    if float(a.repetition_penalty) != 1.0:
+        raise NotImplementedError("generate(penalty_alpha > 0, repetition_penalty != 1) is not implemented")
+    given = [g for g in a.given if g not in ("stopping_criteria=...", "penalty_alpha=...")]
+    if given:
+        raise NotImplementedError(f"generate(penalty_alpha > 0, {given[0]}) is not implemented")
 
 
 def check_guidance(guidance_scale, guidance_plausibility, negative_prompt_ids, negative_attention_mask, negative_images, negative_regions,
