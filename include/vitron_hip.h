@@ -106,6 +106,9 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
  * vt_fsm_rows and the samplers do not change. */
 /* 114 also carries vt_unit_rows, vt_contrast_rows and struct vt_contrast_row WITHOUT a bump: two new symbols and one new struct;
  * vt_logprob_rows and vt_kv_copy_pages do not change. */
+/* 114 also carries vt_dola_rows and struct vt_dola_row WITHOUT a bump: one new symbol and one new struct; and two fields appended to the
+ * END of struct vt_llama_model (logit_row_trace, logit_row_trace_layers), as hidden_trace was: a caller that zero-initialises the struct
+ * gets the launches it got. */
 #define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
@@ -716,6 +719,64 @@ typedef struct vt_cfg_row {
 } vt_cfg_row;
 int vt_cfg_rows(const vt_cfg_row* rows /* DEVICE */, int n_rows, int V, void* stream);
 
+/* DOLA (Chuang et al. 2023, "DoLa: Decoding by Contrasting Layers Improves Factuality in Large Language Models";
+ * transformers 4.4x' generate(dola_layers=...): GenerationMixin._dola_decoding with _dola_select_contrast and _relative_top_filter). A
+ * row names the final layer's logit row and n_cand rows of earlier layers' residual streams put through the bare lm_head; the kernel picks
+ * the candidate whose distribution is furthest from the final one and writes the contrast of the two log-softmaxes, restricted to the
+ * tokens the final layer finds plausible. It goes in front of every other logits processor and of the samplers. Nothing is read on the host.
+ * rows: DEVICE array of n_rows vt_dola_row (80 bytes each, 8-byte aligned; the offsets are part of the ABI):
+ *    0 const float*    final             DEVICE final-layer logit row, fp32 [V]; NULL = this row is skipped entirely, nothing is written
+ *    8 const float*    prem              DEVICE candidate rows, fp32: candidate j is the V floats at prem + j * prem_stride
+ *   16 float*          out               DEVICE contrasted row, fp32 [V]; MAY alias final (in place); must NOT overlap a candidate
+ *   24 const uint32_t* base              DEVICE allow mask to start from, ceil(V / 32) words; NULL = every id of [0, V) allowed
+ *   32 uint32_t*       mask_out          DEVICE mask of the kept tokens to write, ceil(V / 32) words; NULL = none is written
+ *   40 int*            layer_out         DEVICE one int: the chosen candidate j*; NULL = not written
+ *   48 float*          div_out           DEVICE n_cand floats: the divergences; NULL = not written
+ *   56 float*          lse_out           DEVICE 1 + n_cand floats {lse_final, lse_0, ..}; NULL = not written
+ *   64 int64           prem_stride       elements between candidates
+ *   72 int             n_cand            1 .. VT_DOLA_MAX_LAYERS
+ *   76 fp32            log_relative_top  log(relative_top), computed on the host; -inf = nothing is filtered
+ * Per row, everything in fp32, f = final, x = candidate j:
+ *     lse_f = m_f + logf(sum_i expf(f_i - m_f)),  m_f = max_i f_i      (vt_logprob_rows' expression and reduction order; lse_j likewise)
+ *     lpf = f_i - lse_f;  lpj = x_i - lse_j;  M = 0.5 (expf(lpf) + expf(lpj))
+ *     div_j = 0.5 * sum_i [ M (logf(M) - lpf) + M (logf(M) - lpj) ],  a term with M == 0 counting 0
+ *       -- F.kl_div(input = log_softmax, target = the average distribution) summed, KL(M || p) twice: what transformers computes under the
+ *       name of the Jensen-Shannon divergence; unbounded (a token with p_f = 0 < p_j contributes +inf). With n_cand == 1 no divergence
+ *       is computed and div_out[0] = 0.
+ *     j* = 0; for j = 1 .. n_cand - 1: if (div_j > div_j*) j* = j       -- the largest divergence; exact ties and NaNs go to the lower j
+ *     keep_i = f_i >= m_f + log_relative_top                             -- _relative_top_filter with min_tokens_to_keep = 1 in vt_cfg_rows' form
+ *     out_i = keep_i ? (f_i - lse_f) - (x*_i - lse_j*) : -inf            -- the three subtractions each rounded to nearest on their own,
+ *       so out follows BIT FOR BIT from the inputs, lse_out[0], lse_out[1 + j*] and j*
+ *     mask_out bit i = base bit i AND keep_i, i in [0, V); word / bit layout and the bits at positions >= V as in vt_cfg_rows
+ * Two bitwise equal candidate rows of one row get bitwise equal lse and div (same form, same reduction order), so the tie rule is exact.
+ * The maxima skip NaNs (fmaxf), the sums do not: a row that holds a NaN has NaN lse and NaN divergences (j* = 0), out is NaN where
+ * keep_i holds and -inf elsewhere (a NaN f_i fails the comparison). +-inf propagate by IEEE rules, nothing is special-cased.
+ * Bad row content: a live row whose n_cand is outside [1, VT_DOLA_MAX_LAYERS] reads and writes nothing except layer_out = -1 (when
+ * given); the other rows of the launch are served.
+ * No value read from a row is used as an index. final, out and every candidate must be readable / writable for V floats and 4-byte
+ * aligned; floats and words of larger buffers behind them are not touched. mask_out must NOT alias base.
+ * Refused with VT_STATUS_ARG and a message before any launch: rows == NULL, n_rows <= 0, V <= 0, V > VT_LOGPROB_MAX_V, rows not 8-byte
+ * aligned.
+ * One launch, one 1024-thread block per row, no workspace, no atomics. Two forms, chosen per ROW: V <= 32 * 1024 with final, prem and out
+ * 16-byte aligned and prem_stride % 4 == 0 -- the final row stays in registers, every candidate is read once (the chosen one a second
+ * time for the write); any other V or alignment -- a thread re-reads its elements (L2) for each reduction.
+ * 114 carries this entry point WITHOUT a bump: one new symbol and one new struct, nothing existing changes (see the note at VT_ABI_VERSION). */
+#define VT_DOLA_MAX_LAYERS 16
+typedef struct vt_dola_row {
+  const float* final;
+  const float* prem;
+  float* out;
+  const uint32_t* base;
+  uint32_t* mask_out;
+  int* layer_out;
+  float* div_out;
+  float* lse_out;
+  long long prem_stride;
+  int n_cand;
+  float log_relative_top;
+} vt_dola_row;
+int vt_dola_rows(const vt_dola_row* rows /* DEVICE */, int n_rows, int V, void* stream);
+
 /* CONTRASTIVE SEARCH (Su et al. 2022, "A Contrastive Framework for Neural Text Generation"; transformers'
  * generate(penalty_alpha=, top_k=), whose contrastive_search / _ranking_fast are no longer part of its core). Each of a sequence's k most
  * probable next tokens is run as a decode row; its final hidden state is compared, by cosine similarity, with the final hidden state of
@@ -991,6 +1052,16 @@ typedef struct vt_llama_model {
                                    copied there (entry 0 = the input embeddings) -- what `output_hidden_states=True` of the reference's
                                    LlamaModel collects before each decoder layer (llava_llama.py:69, transformers 4.31 LlamaModel.forward).
                                    NULL (default): nothing is copied. */
+  uint16_t* logit_row_trace;    /* optional DEVICE buffer in the operand format, [num_layers][n_logit_rows][H]: when non-NULL entry [l][i] is the
+                                   INPUT residual stream of decoder layer l (what hidden_trace holds) at row logit_rows[i], rounded ONCE to the
+                                   operand format (round to nearest even; the fp16 build saturates at +-65504 like every operand store): the A
+                                   operand of an lm_head over an early layer (DoLa) without the [L][rows][H] fp32 trace. One
+                                   small gather launch per written layer; every pass shape and precise level, both pools, NF4 layers (the
+                                   stream is fp32 [rows][H] at the top of every layer in all of them). No logit and no page bit changes.
+                                   NULL (default), or n_logit_rows == 0: nothing is launched. ABI 114 carries the two fields WITHOUT a bump,
+                                   appended at the end as hidden_trace was. */
+  const uint8_t* logit_row_trace_layers; /* HOST array [num_layers], or NULL for all layers: only layers with a non-zero flag are written, the
+                                   other entries of logit_row_trace are left untouched. */
 } vt_llama_model;
 
 /* KV pool: k  [num_layers][num_pages][heads][64][head_dim]   (K rows, rotary applied)

@@ -66,7 +66,7 @@ class VtLlamaModel(C.Structure):
                 ("num_layers", C.c_int), ("vocab", C.c_int), ("rms_eps", C.c_float), ("final_norm", vp),
                 ("lm_head", vp), ("rope_cos", vp), ("rope_sin", vp), ("rope_len", C.c_int),
                 ("layers", C.POINTER(VtLlamaLayer)), ("prefill_norm_fold", C.c_int), ("qkv_fuse", C.c_int), ("precise_qk", C.c_int), ("last_layer_full", C.c_int),
-                ("embeds_lo", vp), ("hidden_trace", vp)]
+                ("embeds_lo", vp), ("hidden_trace", vp), ("logit_row_trace", vp), ("logit_row_trace_layers", vp)]
 
 
 class VtKvCache(C.Structure):
@@ -128,6 +128,7 @@ SIGNATURES = {
     "vt_bias_rows": (_i, [vp, _i, _i, vp]),
     "vt_fsm_rows": (_i, [vp, _i, _i, vp]),
     "vt_cfg_rows": (_i, [vp, _i, _i, vp]),
+    "vt_dola_rows": (_i, [vp, _i, _i, vp]),
     "vt_unit_rows": (_i, [vp, _i, vp, vp, _i, _i, _i, vp]),
     "vt_contrast_rows": (_i, [vp, _i, vp, _i, _i, _i, vp, _sz, vp]),
     "vt_projector_workspace_bytes": (_sz, [_i, _i]),

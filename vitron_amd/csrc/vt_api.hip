@@ -510,6 +510,8 @@ int vt_bias_rows(const vt_bias_row* rows, int n_rows, int V, void* stream) { ret
 // ---- token automata (vt_fsm.hip) -----------------------------------------------------------------------------------------
 int vt_fsm_rows(const vt_fsm_row* rows, int n_rows, int V, void* stream) { return vt_fsm_rows_launch(rows, n_rows, V, S(stream)); }
 int vt_cfg_rows(const vt_cfg_row* rows, int n_rows, int V, void* stream) { return vt_cfg_rows_launch(rows, n_rows, V, S(stream)); }
+// ---- DoLa (vt_dola.hip) --------------------------------------------------------------------------------------------------
+int vt_dola_rows(const vt_dola_row* rows, int n_rows, int V, void* stream) { return vt_dola_rows_launch(rows, n_rows, V, S(stream)); }
 // ---- contrastive search (vt_contrast.hip) ------------------------------------------------------------------------------------
 int vt_unit_rows(const float* x, int ldx, const float* w, uint16_t* out, int ldo, int rows, int H, void* stream) {
   return vt_unit_rows_launch(x, ldx, w, out, ldo, rows, H, S(stream));
@@ -1007,6 +1009,9 @@ int llama_forward_body(const vt_llama_model* m, const vt_kv_cache* kv16, const v
     const vt_llama_layer& L = m->layers[l];
     if (m->hidden_trace)
       VT_HIP(hipMemcpyAsync(m->hidden_trace + (size_t)l * rows * H, w.x, (size_t)rows * H * 4, hipMemcpyDeviceToDevice, s));
+    // the same stream at the logit rows only, rounded once to the operand format (DoLa's candidate layers: DESIGN.md 9.14)
+    if (m->logit_row_trace && n_logit_rows > 0 && (!m->logit_row_trace_layers || m->logit_row_trace_layers[l]))
+      VT_TRY(vt_gather_f32_to_bf16_launch(w.x, logit_rows, m->logit_row_trace + (size_t)l * n_logit_rows * H, n_logit_rows, H, s));
     // fp8 pool: kt / vt are the staging pool (prefills only; decode steps read k8 / vt8)
     bf16_t* kt = kv8 ? w.stage_k : kv16->k + l * layer_stride;
     bf16_t* vt = kv8 ? w.stage_vt : kv16->vt + l * layer_stride;

@@ -287,6 +287,9 @@ int vt_fsm_rows_launch(const vt_fsm_row* rows, int n_rows, int V, hipStream_t s)
 // ---- vt_cfg.hip -----------------------------------------------------------------------------------
 int vt_cfg_rows_launch(const vt_cfg_row* rows, int n_rows, int V, hipStream_t s);
 
+// ---- vt_dola.hip ----------------------------------------------------------------------------------
+int vt_dola_rows_launch(const vt_dola_row* rows, int n_rows, int V, hipStream_t s);
+
 // ---- vt_contrast.hip ------------------------------------------------------------------------------
 int vt_unit_rows_launch(const float* x, int ldx, const float* w, op16_t* out, int ldo, int rows, int H, hipStream_t s);
 int vt_contrast_rows_launch(const vt_contrast_row* rows, int n_groups, const op16_t* cand, int n_cand, int ld, int H, void* workspace,

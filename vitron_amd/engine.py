@@ -653,13 +653,17 @@ class SequenceState:
 
 def llama_forward(llama: PackedLlama, kv: PagedKVCache, seqs: Sequence[SequenceState], embeds: torch.Tensor,
                   q_lens: Sequence[int], positions: Optional[torch.Tensor] = None, logit_rows: Optional[Sequence[int]] = None,
-                  return_hidden: bool = False, return_all_hidden: bool = False, embeds_lo: Optional[torch.Tensor] = None):
+                  return_hidden: bool = False, return_all_hidden: bool = False, embeds_lo: Optional[torch.Tensor] = None,
+                  trace_rows_layers: Optional[Sequence[int]] = None, trace_rows_out: Optional[torch.Tensor] = None):
     """One decoder pass over packed rows. embeds (operand dtype) [sum(q_lens), H]: the new tokens of every sequence, sequence by
     sequence. Appends their K/V to the cache, returns fp32 logits for `logit_rows` (default: last row of each
     sequence). positions default to cache position (length + i). Prefill and decode are the same call.
     return_hidden: also the fp32 residual stream behind the last layer [rows, H]; return_all_hidden: also the stream in front of
     every layer, fp32 [L, rows, H] (vt_llama_model.hidden_trace) -- returns (logits, hidden, trace).
-    embeds_lo (precise level 2): the low half of `embeds` when the caller carries them as an operand pair (same shape and dtype)."""
+    embeds_lo (precise level 2): the low half of `embeds` when the caller carries them as an operand pair (same shape and dtype).
+    trace_rows_layers: layer indices in [0, L); the INPUT stream of those layers at the logit rows, rounded once to the operand format,
+    is returned as the LAST element of the result: operand dtype [L, n_logit_rows, H] (vt_llama_model.logit_row_trace; the entries of
+    the other layers are not written). trace_rows_out: a contiguous buffer of that shape and dtype to write into (default: a fresh one)."""
     lib = llama.lib
     dev = llama.device
     rows = int(sum(q_lens))
@@ -672,6 +676,8 @@ def llama_forward(llama: PackedLlama, kv: PagedKVCache, seqs: Sequence[SequenceS
         if tuple(embeds_lo.shape) != tuple(embeds.shape):
             raise _lib.VitronHipError(f"llama_forward: embeds_lo {tuple(embeds_lo.shape)} vs embeds {tuple(embeds.shape)}")
         embeds_lo = embeds_lo.to(llama.dtype).contiguous()
+    # (checked before any page is taken)
+    row_trace, row_flags = logit_row_trace_args(llama, len(seqs) if logit_rows is None else len(logit_rows), trace_rows_layers, trace_rows_out)
     desc, table, pos_host = [], [], []
     row0 = 0
     max_new_tiles = 1
@@ -712,17 +718,42 @@ def llama_forward(llama: PackedLlama, kv: PagedKVCache, seqs: Sequence[SequenceS
     call_model = _lib.VtLlamaModel.from_buffer_copy(llama.model)
     call_model.hidden_trace = trace.data_ptr() if trace is not None else None
     call_model.embeds_lo = embeds_lo.data_ptr() if embeds_lo is not None else None
+    if row_trace is not None:
+        call_model.logit_row_trace = row_trace.data_ptr()
+        call_model.logit_row_trace_layers = C.addressof(row_flags)
     _llama_call(lib, call_model, kv, embeds, rows, pos_t, desc_t, len(desc), int(max(q_lens)), int(max_new_tiles), int(max_kv), table_t, lr_t,
                 n_logit, logits, hidden, ws)
     for s, q in zip(seqs, q_lens):
         s.length += q
     if logits is not None and llama.V_pad != llama.V:
         logits = logits[:, :llama.V]               # rows keep the padded stride; the kernels take (V, row stride)
-    if return_all_hidden:
-        return logits, hidden, trace
-    if return_hidden:
-        return logits, hidden
-    return logits
+    res = (logits, hidden, trace) if return_all_hidden else (logits, hidden) if return_hidden else (logits,)
+    if trace_rows_layers is not None:
+        res += (row_trace,)
+    return res if len(res) > 1 else res[0]
+
+
+def logit_row_trace_args(llama: "PackedLlama", n_logit: int, layers: Optional[Sequence[int]], out: Optional[torch.Tensor]):
+    """(buffer, host flag array) of a pass that traces `layers` at its logit rows (vt_llama_model.logit_row_trace /
+    logit_row_trace_layers), or (None, None) when layers is None. The caller keeps both alive until the C call has returned."""
+    if layers is None:
+        if out is not None:
+            raise _lib.VitronHipError("llama_forward: trace_rows_out without trace_rows_layers")
+        return None, None
+    layers = [int(l) for l in layers]
+    if not layers or min(layers) < 0 or max(layers) >= llama.L:
+        raise _lib.VitronHipError(f"llama_forward: trace_rows_layers {layers} must name layers in [0, {llama.L})")
+    if n_logit <= 0:
+        raise _lib.VitronHipError("llama_forward: trace_rows_layers needs at least one logit row")
+    shape = (llama.L, n_logit, llama.H)
+    if out is None:
+        out = torch.empty(shape, dtype=llama.dtype, device=llama.device)
+    elif out.dtype != llama.dtype or tuple(out.shape) != shape or not out.is_contiguous() or out.device != llama.embed.device:
+        raise _lib.VitronHipError(f"llama_forward: trace_rows_out must be a contiguous {llama.dtype} {list(shape)} tensor on the model's device")
+    flags = (C.c_uint8 * llama.L)()
+    for l in layers:
+        flags[l] = 1
+    return out, flags
 
 
 def _llama_call(lib, model_struct, kv, embeds, rows, pos_t, desc_t, nseq, max_q, max_new_tiles, max_kv, table_t, lr_t, n_logit, logits, hidden, ws):
@@ -890,10 +921,13 @@ class DecodeState:
         t = self.tok_pin[slot].tolist()
         return t[0], [bool(f) for f in t[1]]
 
-    def forward(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward(self, out: Optional[torch.Tensor] = None, trace_rows_layers: Optional[Sequence[int]] = None,
+                trace_rows_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One decoder pass over the rows feed() just wrote; fp32 logits [B, V]. No host -> device traffic. out: a contiguous fp32
         [B, V_pad] buffer of the caller's to write the logits to (a caller that has handed its address to the device, as guided
-        generate() does); the default is a fresh tensor per pass."""
+        generate() does); the default is a fresh tensor per pass. trace_rows_layers / trace_rows_out: llama_forward's -- the traced
+        layers' input streams at the B rows are written to trace_rows_out (operand dtype [L, B, H], required with trace_rows_layers);
+        the return value stays the logits."""
         if self.passes >= self.fed:
             raise _lib.VitronHipError("DecodeState.forward: feed() the sampled tokens first")
         llama, B = self.llama, self.B
@@ -909,16 +943,24 @@ class DecodeState:
             if out.dtype != torch.float32 or tuple(out.shape) != (B, llama.V_pad) or not out.is_contiguous() or out.device != self.x.device:
                 raise _lib.VitronHipError(f"DecodeState.forward: out must be a contiguous fp32 [{B}, {llama.V_pad}] tensor on the model's device")
             logits = out
+        model = llama.model
+        if trace_rows_layers is not None:           # the per-call pointers travel in a copy of the struct, as in llama_forward
+            if trace_rows_out is None:
+                raise _lib.VitronHipError("DecodeState.forward: trace_rows_layers needs trace_rows_out")
+            row_trace, row_flags = logit_row_trace_args(llama, B, trace_rows_layers, trace_rows_out)
+            model = _lib.VtLlamaModel.from_buffer_copy(llama.model)
+            model.logit_row_trace = row_trace.data_ptr()
+            model.logit_row_trace_layers = C.addressof(row_flags)
         if getattr(self.kv, "kv_dtype", "16bit") == "fp8":
             nt = int(self.table.numel())
             ws = llama.ws.get(lib.vt_llama_workspace_bytes_kv8(C.byref(llama.model), B, B, B, self.max_len, nt))
-            _lib.check(lib.vt_llama_forward_kv8(C.byref(llama.model), C.byref(self.kv.struct), self.x.data_ptr(), B, self.pos.data_ptr(),
+            _lib.check(lib.vt_llama_forward_kv8(C.byref(model), C.byref(self.kv.struct), self.x.data_ptr(), B, self.pos.data_ptr(),
                                                 self.desc.data_ptr(), B, 1, 1, int(self.max_len), self.table.data_ptr(), nt,
                                                 self.rows.data_ptr(), B, logits.data_ptr(), None, ws.data_ptr(), ws.numel(), _stream()),
                        "vt_llama_forward_kv8", lib)
         else:
             ws = llama.ws.get(lib.vt_llama_workspace_bytes(C.byref(llama.model), B, B, B, self.max_len))
-            _lib.check(lib.vt_llama_forward(C.byref(llama.model), C.byref(self.kv.struct), self.x.data_ptr(), B, self.pos.data_ptr(),
+            _lib.check(lib.vt_llama_forward(C.byref(model), C.byref(self.kv.struct), self.x.data_ptr(), B, self.pos.data_ptr(),
                                             self.desc.data_ptr(), B, 1, 1, int(self.max_len), self.table.data_ptr(),
                                             self.rows.data_ptr(), B, logits.data_ptr(), None, ws.data_ptr(), ws.numel(), _stream()),
                        "vt_llama_forward", lib)

@@ -105,6 +105,27 @@ class LlavaLlamaModel(LlavaMetaModel):
         return ops.embed_splice(self.llama.embed, None, None, plan).view(*ids.shape, -1)
 
 
+class _DolaHead:
+    """The candidate rows of a DoLa call: `trace` is the operand-dtype [L, B, H] buffer a decoder pass writes the
+    candidate layers' streams into (vt_llama_model.logit_row_trace); head(out) gathers the n_cand * B candidate rows (candidate-major)
+    and runs the bare lm_head over them into out, fp32 [n_cand, B, V_pad], in launches of at most 16 rows: the weight-streaming GEMM a
+    decode step's lm_head runs. Nothing is allocated per step."""
+    ROWS = 16
+
+    def __init__(self, llama, layers, B: int, trace: torch.Tensor):
+        self.llama, self.trace = llama, trace
+        self.idx = torch.tensor([l * B + b for l in layers for b in range(B)], dtype=torch.long).to(trace.device)
+        self.rows = torch.empty((len(layers) * B, llama.H), dtype=trace.dtype, device=trace.device)
+
+    def head(self, out: torch.Tensor) -> torch.Tensor:
+        from ... import ops
+        torch.index_select(self.trace.view(-1, self.llama.H), 0, self.idx, out=self.rows)
+        flat = out.view(-1, out.shape[-1])
+        for r0 in range(0, self.rows.shape[0], self.ROWS):
+            ops.gemm(self.rows[r0:r0 + self.ROWS], self.llama.lm_head, None, ops.EPI_F32, out=flat[r0:r0 + self.ROWS])
+        return out
+
+
 class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
     config_class = LlavaConfig
 
@@ -564,11 +585,25 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         is served. ValueError before any device work: penalty_alpha not a finite number in [0, 1], or > 0 with do_sample=True. Refused
         with NotImplementedError, naming the argument: top_k left at its default or outside [2, 16] (1 is off), num_beams > 1,
         padded_batch, repetition_penalty != 1, every optional processor argument (suppress_tokens ... automaton), return_logits,
-        return_logprobs, top_logprobs, guidance_scale."""
+        return_logprobs, top_logprobs, guidance_scale.
+        DoLa (transformers 4.4x' dola_layers, Chuang et al. 2023), dola_layers and dola_relative_top (default 0.1) taken
+        from **kwargs: dola_layers "low" / "high" / a list of layer indices names the candidate layers (index i = the INPUT stream of
+        decoder layer i, sampling.dola_candidate_layers); None is off and the call runs the launches it always ran. Per step: the decoder
+        pass also writes the candidate layers' streams at the B logit rows (vt_llama_model.logit_row_trace: one small launch per
+        candidate layer), the bare lm_head runs over those n_cand * B rows in launches of at most 16 rows (the weight-streaming kernel of
+        a decode step's lm_head) into a buffer the call owns, and ONE vt_dola_rows launch picks, per row, the candidate furthest from
+        the final layer and writes log_softmax(final) - log_softmax(candidate) in place over the row, -inf outside the tokens with
+        p_final >= dola_relative_top * max p_final, plus the mask of those tokens. Everything behind it -- penalties, bias, the other
+        masks, the per-row sampler (greedy or sampling), return_logprobs, top_logprobs -- sees the contrasted row; return_logits are the
+        model's final rows. Every row chooses its own layer (transformers averages the divergences over the batch): a row gets what it
+        gets alone. self.last_dola_layers: int64 [B, n] -- the layer chosen for every emitted token. ValueError before any device work:
+        a bad dola_layers, dola_relative_top outside (0, 1]. Refused with NotImplementedError, naming the argument: num_beams > 1,
+        penalty_alpha > 0, guidance_scale, padded_batch."""
         from ...picker import StepPicker, negative_prompt, resolve_generate_args
         guide = {k: kwargs.pop(k, None) for k in ("guidance_scale", "negative_prompt_ids", "negative_attention_mask", "negative_images",
                                                   "negative_regions", "guidance_plausibility")}
         penalty_alpha = kwargs.pop("penalty_alpha", None)
+        dola_layers, dola_relative_top = kwargs.pop("dola_layers", None), kwargs.pop("dola_relative_top", 0.1)
         a = resolve_generate_args(
             self.config, input_ids.shape[1], do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k,
             max_new_tokens=max_new_tokens, max_length=max_length, stopping_criteria=stopping_criteria, eos_token_id=eos_token_id,
@@ -579,7 +614,9 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
             early_stopping=early_stopping, no_repeat_ngram_size=no_repeat_ngram_size, sequence_bias=sequence_bias,
             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p, typical_p=typical_p,
             epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, top_logprobs=top_logprobs, automaton=automaton, choices=choices,
-            batch_size=input_ids.shape[0], penalty_alpha=penalty_alpha, **guide)
+            batch_size=input_ids.shape[0], penalty_alpha=penalty_alpha, dola_layers=dola_layers, dola_relative_top=dola_relative_top,
+            **guide)
+        self.last_dola_layers = None
         dev = self.device
         neg_ids = neg_mask = None
         if a.guided and a.num_beams == 1:
@@ -626,7 +663,12 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         all_logits = []
         state = None
         try:   # (the prefill is inside: pages it took before a failure go back to the pool / the kept prefix below)
-            logits = llama_forward(llama, self.kv, seqs, flat, lens, embeds_lo=flat_lo)     # [B, V]: last position of every sequence
+            dola = None
+            if a.dola:       # the prefill also leaves the candidate layers' streams at its B logit rows
+                logits, trace0 = llama_forward(llama, self.kv, seqs, flat, lens, embeds_lo=flat_lo, trace_rows_layers=a.dola_layers)
+                dola = _DolaHead(llama, a.dola_layers, B, trace0)
+            else:
+                logits = llama_forward(llama, self.kv, seqs, flat, lens, embeds_lo=flat_lo) # [B, V]: last position of every sequence
             picker.check_width(logits)
             if pad_mode:
                 from ...engine import padded_batch_fixup
@@ -641,6 +683,12 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                 if max_new_tokens > 1:
                     bufs = [torch.empty((2 * B, llama.V_pad), dtype=torch.float32, device=dev) for _ in range(2)]
                 picker.attach_guidance(logits, ulogits, bufs)
+            if dola is not None:     # the candidates of step 0; the steps' vt_dola_row arrays name these rows and the decode buffers: one upload
+                prem0 = dola.head(torch.empty((len(a.dola_layers), B, llama.V_pad), dtype=torch.float32, device=dev))
+                if max_new_tokens > 1:
+                    bufs = [torch.empty((B, llama.V_pad), dtype=torch.float32, device=dev) for _ in range(2)]
+                    pbufs = [torch.empty_like(prem0) for _ in range(2)]
+                picker.attach_dola(logits, prem0, bufs, pbufs if max_new_tokens > 1 else None)
             for step in range(max_new_tokens):
                 if a.return_logits:
                     all_logits.append(logits.clone())
@@ -655,7 +703,11 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
                         state = DecodeState(llama, self.kv, seqs + nseqs, max_new_tokens, eos_ids, a.pad)
                     slot = state.feed(torch.cat((nxt, nxt)) if a.guided else nxt)
                     if not last:                          # speculative: rolled back below if this token ends the run
-                        logits = state.forward(bufs[(step + 1) & 1])[:B] if a.guided else state.forward()
+                        if dola is not None:
+                            logits = state.forward(bufs[(step + 1) & 1], trace_rows_layers=a.dola_layers, trace_rows_out=dola.trace)
+                            dola.head(pbufs[(step + 1) & 1])
+                        else:
+                            logits = state.forward(bufs[(step + 1) & 1])[:B] if a.guided else state.forward()
                     toks, fin = state.read(slot)
                     toks, fin = toks[:B], fin[:B]
                 out_host[:, n_out] = torch.tensor(toks, dtype=torch.long)
@@ -672,6 +724,8 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
             for s in nseqs:
                 self.kv.release(s.pages)
         out = out_host[:, :n_out].to(dev)
+        if picker.dola_choice is not None:
+            self.last_dola_layers = torch.tensor(a.dola_layers, dtype=torch.long, device=dev)[picker.dola_choice[:n_out - L0].long().t()]
         res = (out,) + ((all_logits,) if a.return_logits else ()) + ((picker.logprobs(n_out - L0),) if a.return_logprobs else ()) \
             + ((picker.top(n_out - L0),) if a.top_logprobs else ())
         return res if len(res) > 1 else out

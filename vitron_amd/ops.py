@@ -760,6 +760,24 @@ def cfg_rows(rows_dev: Optional[torch.Tensor], n_rows: int, V: int) -> None:
     _lib.check(lib.vt_cfg_rows(_p(rows_dev) if rows_dev is not None else None, n_rows, int(V), _stream()), "vt_cfg_rows", lib)
 
 
+def dola_rows(rows_dev: Optional[torch.Tensor], n_rows: int, V: int) -> None:
+    """DoLa over n_rows logit rows on the device: per row the candidate layer furthest from the final one and out = log_softmax(final) -
+    log_softmax(candidate) over the tokens final >= max(final) + log_relative_top, -inf elsewhere; optionally the mask of the kept tokens,
+    the chosen index, the divergences and the lse values; see vt_dola_rows in include/vitron_hip.h. rows_dev: the device array of
+    vt_dola_row that sampling.pack_dola_rows builds (contiguous uint8, n_rows x 80 bytes). Every pointer inside it is dereferenced on the
+    device as it is: the caller keeps the buffers alive until the launch has run; `out` may be `final` itself and nothing else that the
+    launch reads."""
+    from .sampling import DOLA_ROW_BYTES
+    lib = _lib.load_any()
+    n_rows = int(n_rows)
+    if rows_dev is not None and n_rows > 0:
+        _chk(rows_dev, torch.uint8, "dola_rows.rows_dev")
+        if rows_dev.numel() != n_rows * DOLA_ROW_BYTES:
+            raise _lib.VitronHipError(f"dola_rows.rows_dev: expected {n_rows} x {DOLA_ROW_BYTES} bytes (sampling.pack_dola_rows), got "
+                                      f"{rows_dev.numel()}")
+    _lib.check(lib.vt_dola_rows(_p(rows_dev) if rows_dev is not None else None, n_rows, int(V), _stream()), "vt_dola_rows", lib)
+
+
 def bias_rows(rows_dev: torch.Tensor, n_rows: int, V: int) -> None:
     """Build the additive adjustments of n_rows rows on the device (logit bias, presence and frequency penalties over the generated
     ids); see vt_bias_rows in include/vitron_hip.h. rows_dev: the device array of vt_bias_row that sampling.pack_bias_rows builds

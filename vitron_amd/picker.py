@@ -23,9 +23,9 @@ import torch
 
 from . import ops
 from .engine import parse_kv_cache_dtype
-from .sampling import (BAN_ROW_BYTES, BIAS_ROW_BYTES, BIAS_ROWS_MAX_V, CFG_ROW_BYTES, FSM_ROW_BYTES, ROW_BYTES, allow_mask, check_penalties,
+from .sampling import (BAN_ROW_BYTES, BIAS_ROW_BYTES, BIAS_ROWS_MAX_V, CFG_ROW_BYTES, DOLA_ROW_BYTES, FSM_ROW_BYTES, ROW_BYTES, allow_mask, check_penalties,
                        check_sampling_values, check_top_logprobs, check_truncation_values, log_beta, mask_words, normalise_bias, pack_ban_rows,
-                       pack_bias_rows, pack_cfg_rows, pack_fsm_rows, pack_sample_rows, pack_trunc_rows, truncation_active)
+                       pack_bias_rows, pack_cfg_rows, pack_dola_rows, pack_fsm_rows, pack_sample_rows, pack_trunc_rows, truncation_active, check_dola)
 
 
 @dataclass(frozen=True, eq=False)
@@ -64,10 +64,16 @@ class GenerateArgs:
     guidance_scale: Optional[float] = None       # classifier-free guidance (vt_cfg_rows); None is off (a scale of 1 resolves to it)
     guidance_plausibility: float = 0.0           # beta of the adaptive plausibility cut; 0 is off
     penalty_alpha: float = 0.0                   # contrastive search (vt_contrast_rows); 0 is off
+    dola_layers: Optional[Tuple[int, ...]] = None   # DoLa (vt_dola_rows): the candidate layers, resolved; None is off
+    dola_relative_top: float = 0.1               # a token stays iff p_final >= relative_top * max p_final
 
     @property
     def guided(self) -> bool:
         return self.guidance_scale is not None
+
+    @property
+    def dola(self) -> bool:
+        return self.dola_layers is not None
 
     @property
     def contrastive(self) -> bool:
@@ -96,7 +102,8 @@ class GenerateArgs:
     def per_row(self) -> bool:
         """Does a step need the per-row sampler (vt_sample_rows) instead of vt_argmax / vt_sample_top_p?"""
         return (float(self.repetition_penalty) != 1.0 or bool(self.return_logprobs) or self.constrained or self.ngram > 0
-                or self.adjusted or self.truncated or self.automaton is not None or self.guidance_plausibility > 0)
+                or self.adjusted or self.truncated or self.automaton is not None or self.guidance_plausibility > 0
+                or self.dola)
 
 
 def static_mask_schedule(V: int, steps: int, banned_always, banned_begin, min_new: int, eos, allowed_ids):
@@ -128,7 +135,7 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
                           frequency_penalty=0.0, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None,
                           top_logprobs=0, automaton=None, choices=None, guidance_scale=None, negative_prompt_ids=None,
                           negative_attention_mask=None, negative_images=None, negative_regions=None, guidance_plausibility=0.0,
-                          batch_size=None, penalty_alpha=None) -> GenerateArgs:
+                          batch_size=None, penalty_alpha=None, dola_layers=None, dola_relative_top=0.1) -> GenerateArgs:
     """generate()'s keyword arguments as a GenerateArgs. Raises, in this order and before any device work: the argument errors of
     num_beams / no_repeat_ngram_size, everything a beam call refuses, the padded_batch refusals that depend on arguments alone, the
     sampling values, the constraint arguments, a step the constraints leave no token for, constraints with padded_batch, the values of
@@ -143,13 +150,18 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
     arguments). guidance_scale None or 1 is off and resolves to None. Contrastive search: the VALUE of penalty_alpha
     (ValueError: not a finite number in [0, 1]; > 0 together with do_sample=True) is checked right behind num_beams; a beam call refuses
     penalty_alpha > 0 with its other optional arguments; everything else the mode refuses comes last, behind the guidance arguments, in
-    check_contrastive's order. penalty_alpha None or 0, or top_k == 1, is off. The sample seed
+    check_contrastive's order. penalty_alpha None or 0, or top_k == 1, is off. DoLa: the VALUES of dola_layers and
+    dola_relative_top (sampling.check_dola: ValueError) are checked right behind penalty_alpha's; a beam call refuses dola_layers with its
+    other optional arguments; padded_batch, guidance_scale and penalty_alpha > 0 are refused with it (NotImplementedError) at the very end.
+    dola_layers None is off. The sample seed
     is drawn from torch's global CPU generator (so torch.manual_seed makes sampling reproducible, as with GenerationMixin.sample) and
     only when sampling without `seed`, after the beam refusals: greedy and refused calls leave the RNG state alone."""
     num_beams = int(num_beams)
     if num_beams < 1:
         raise ValueError(f"generate: num_beams must be >= 1, got {num_beams}")
     alpha = check_penalty_alpha(penalty_alpha, do_sample)
+    dola, dola_rt = check_dola(dola_layers, dola_relative_top, 0 if dola_layers is None else int(config.num_hidden_layers),
+                               bool(getattr(config, "tie_word_embeddings", False)))
     top_k_given = top_k
     if no_repeat_ngram_size is None:
         no_repeat_ngram_size = 0
@@ -188,7 +200,8 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
                 if value is not None and value != off)
         + (("top_logprobs=...",) if top_logprobs else ()) + (("automaton=...",) if automaton is not None else ())
         + (("guidance_scale=...",) if guidance_scale is not None and guidance_scale != 1 else ())
-        + (("penalty_alpha=...",) if alpha > 0 else ()))
+        + (("penalty_alpha=...",) if alpha > 0 else ())
+        + (("dola_layers=...",) if dola is not None else ()))
     if num_beams > 1:
         check_beam_arguments(a, int(config.vocab_size))
     elif a.num_return_sequences != 1:
@@ -259,6 +272,14 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
     if alpha > 0 and num_beams == 1:
         check_contrastive(a, top_k_given)
         a = dataclasses.replace(a, penalty_alpha=alpha)
+    if dola is not None and num_beams == 1:
+        if padded_batch:
+            raise NotImplementedError("generate(dola_layers=..., padded_batch=True) is not implemented; use the default packed batch")
+        if a.guided:
+            raise NotImplementedError("generate(dola_layers=..., guidance_scale=...) is not implemented: one contrast per call")
+        if alpha > 0:
+            raise NotImplementedError("generate(dola_layers=..., penalty_alpha > 0) is not implemented: one contrast per call")
+        a = dataclasses.replace(a, dola_layers=dola, dola_relative_top=dola_rt)
     return a
 
 
@@ -292,7 +313,7 @@ def check_contrastive(a: GenerateArgs, top_k_given) -> None:
         raise NotImplementedError("generate(penalty_alpha > 0, padded_batch=True) is not implemented: the candidates run in the packed batch")
     if float(a.repetition_penalty) != 1.0:
         raise NotImplementedError("generate(penalty_alpha > 0, repetition_penalty != 1) is not implemented")
-    given = [g for g in a.given if g not in ("stopping_criteria=...", "penalty_alpha=...")]
+    given = [g for g in a.given if g not in ("stopping_criteria=...", "penalty_alpha=...", "dola_layers=...")]
     if given:
         raise NotImplementedError(f"generate(penalty_alpha > 0, {given[0]}) is not implemented")
 
@@ -454,7 +475,12 @@ class StepPicker:
     place over the conditional ones. Everything behind it -- penalties and bias, masks, the sampler, return_logprobs, top_logprobs --
     sees the guided row. With guidance_plausibility > 0 the mode is per-row: the launch also writes the B working masks
     (base = the step's static mask or NULL), which take the static mask's place as the `base` of the vt_fsm_row array, or of the
-    vt_ban_row array when there is no automaton, or as the sampler's allow pointers when there is neither."""
+    vt_ban_row array when there is no automaton, or as the sampler's allow pointers when there is neither.
+    With dola_layers (the mode is per-row): `attach_dola`, called once between the prefill and the loop, uploads the
+    [steps, B] vt_dola_row array over the addresses the steps' logits and candidate rows will have, and every pick starts with ONE
+    ops.dola_rows launch that writes the contrasted rows in place over the final ones, the chosen candidate of step `step` into
+    `dola_choice[step]`, and the B working masks of the kept tokens (base = the step's static mask or NULL) -- the same working masks,
+    in the same three places, as guidance_plausibility's (the two modes exclude each other)."""
 
     def __init__(self, a: GenerateArgs, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], V: int):
         self.a = a
@@ -469,6 +495,7 @@ class StepPicker:
             self.top_lp = torch.empty((n, B, a.top_logprobs), dtype=torch.float32, device=self.device)
             self.top_rank = torch.empty((n, B), dtype=torch.int32, device=self.device)
         self.cfg_rows = self.cfg_ptrs = self.cfg_mask_ptr = None
+        self.dola_rows = self.dola_choice = None
         self.step_base: List[int] = [0] * max(a.max_new_tokens, 0)
         if self.mode != "rows":
             return
@@ -487,7 +514,7 @@ class StepPicker:
              for st in range(steps) for b in range(B)], dev).view(steps, B, ROW_BYTES)
         self.step_base = step_base
         cfg_ptr = None
-        if a.guidance_plausibility > 0:          # the plausibility masks vt_cfg_rows writes stand where the static masks stood
+        if a.guidance_plausibility > 0 or a.dola:   # the masks vt_cfg_rows / vt_dola_rows write stand where the static masks stood
             self.cfg_work = cw = torch.empty((B, mask_words(self.V)), dtype=torch.int32, device=dev)
             cfg_ptr = [cw.data_ptr() + 4 * b * cw.stride(0) for b in range(B)]
             self.cfg_ptrs = torch.tensor(cfg_ptr, dtype=torch.int64).to(dev)
@@ -563,6 +590,32 @@ class StepPicker:
         self._cfg_keep = (cond0, uncond0, bufs)
         self.cfg_rows = pack_cfg_rows(rows, self.device).view(a.max_new_tokens, B, CFG_ROW_BYTES)
 
+    def attach_dola(self, final0: torch.Tensor, prem0: torch.Tensor, final_bufs, prem_bufs) -> None:
+        """Upload every step's vt_dola_row array, once. final0: the fp32 [B, V] logits of the prefill (step 0); prem0: its candidate rows,
+        fp32 [n_cand, B, V_pad]. final_bufs / prem_bufs: the two contiguous fp32 [B, V_pad] / [n_cand, B, V_pad] buffers the decode passes and
+        their candidate lm_head launches write in turn -- step st >= 1 reads index st & 1. The contrasted row goes in place over the final
+        one; candidate j of row b is prem[j, b]."""
+        a, B = self.a, self.B
+        if not a.dola or a.max_new_tokens <= 0:
+            return
+        if final0.shape[1] != self.V:
+            raise RuntimeError(f"generate: DoLa was set up for V = {self.V}, the logits have {final0.shape[1]} columns")
+        n_cand, steps = len(a.dola_layers), a.max_new_tokens
+        lrt = math.log(a.dola_relative_top)
+        self.dola_choice = ch = torch.zeros((steps, B), dtype=torch.int32, device=self.device)
+
+        def row_ptr(t, r):
+            return t.data_ptr() + 4 * r * t.stride(0)
+
+        rows = []
+        for st in range(steps):
+            f, p = (final0, prem0) if st == 0 else (final_bufs[st & 1], prem_bufs[st & 1])
+            for b in range(B):
+                rows.append((row_ptr(f, b), p.data_ptr() + 4 * b * p.stride(1), p.stride(0), n_cand, row_ptr(f, b), self.step_base[st],
+                             self.cfg_mask_ptr[b], ch.data_ptr() + 4 * (st * B + b), 0, 0, lrt))
+        self._dola_keep = (final0, prem0, final_bufs, prem_bufs)
+        self.dola_rows = pack_dola_rows(rows, self.device).view(steps, B, DOLA_ROW_BYTES)
+
     def check_width(self, logits: torch.Tensor) -> None:
         if self.mode == "rows" and (self.a.constrained or self.a.ngram or self.a.automaton is not None) and logits.shape[1] != self.V:
             raise RuntimeError(f"generate: the allow masks were built for V = {self.V}, the logits have {logits.shape[1]} columns")
@@ -572,6 +625,8 @@ class StepPicker:
     def pick(self, step: int, logits: torch.Tensor) -> torch.Tensor:
         if self.cfg_rows is not None:            # the guided rows, in place over the conditional ones `logits` names: one launch
             ops.cfg_rows(self.cfg_rows[step], self.B, self.V)
+        if self.dola_rows is not None:           # the contrasted rows, in place over the final ones `logits` names: one launch
+            ops.dola_rows(self.dola_rows[step], self.B, self.V)
         nxt = self._pick_ids(step, logits)
         if self.a.top_logprobs:                  # the distribution behind the pick: RAW logits, the picked ids as targets
             ops.logprob_rows(logits, nxt, self.a.top_logprobs, out={"rank": self.top_rank[step], "top_ids": self.top_ids[step],

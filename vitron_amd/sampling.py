@@ -27,6 +27,10 @@ Classifier-free guidance: `SamplingParams(guidance_scale=s, neg
 those of a second sequence that runs its negative prompt, in front of everything above: struct vt_cfg_row (`pack_cfg_rows`,
 ops.cfg_rows); `log_beta` is the field of generate()'s plausibility cut.
 
+DoLa: `SamplingParams(dola_layers=, dola_relative_top=)` contrasts the request's final logits with those of an early layer
+it chooses per step (`dola_candidate_layers`, `check_dola`), in front of everything above: struct vt_dola_row (`pack_dola_rows`,
+ops.dola_rows).
+
 Top-N log-probabilities: `SamplingParams(top_logprobs=N)` asks for the N most likely tokens and the chosen token's rank
 at every generated token; they come from one vt_logprob_rows launch behind the pick and need no struct here.
 """
@@ -74,6 +78,15 @@ CFG_ROW_DTYPE = np.dtype({
     "itemsize": 56,
 })
 CFG_ROW_BYTES = CFG_ROW_DTYPE.itemsize
+# struct vt_dola_row: the offsets are part of the ABI (tests/test_dola_ref_host.py checks them against the header's table)
+DOLA_ROW_DTYPE = np.dtype({
+    "names": ["final", "prem", "out", "base", "mask_out", "layer_out", "div_out", "lse_out", "prem_stride", "n_cand", "log_relative_top"],
+    "formats": ["<u8", "<u8", "<u8", "<u8", "<u8", "<u8", "<u8", "<u8", "<i8", "<i4", "<f4"],
+    "offsets": [0, 8, 16, 24, 32, 40, 48, 56, 64, 72, 76],
+    "itemsize": 80,
+})
+DOLA_ROW_BYTES = DOLA_ROW_DTYPE.itemsize
+DOLA_MAX_LAYERS = 16               # VT_DOLA_MAX_LAYERS
 # struct vt_bias_row: the offsets are part of the ABI (tests/test_bias_ref_host.py checks them against the header's table)
 BIAS_ROW_DTYPE = np.dtype({
     "names": ["history", "bias_ids", "bias_vals", "out", "history_len", "n_bias", "presence", "frequency"],
@@ -232,14 +245,19 @@ class SamplingParams(_SamplingFields):
     guidance_scale and negative_prompt_ids are of the same kind: classifier-free guidance against a TEXT-ONLY negative
     prompt (a sequence of ids >= 0, stored as a tuple; None: the last token of the request's prompt). None or 1 is off. A guided request
     owns a second sequence and two decode rows; its logits are blended by vt_cfg_rows in front of everything else the request asks for.
-    guidance_plausibility and negative_images exist to be refused (NotImplementedError): the engine runs neither. repr shows them when set."""
+    guidance_plausibility and negative_images exist to be refused (NotImplementedError): the engine runs neither. repr shows them when set.
+    dola_layers and dola_relative_top are of the same kind: DoLa decoding, generate(dola_layers=...)'s arguments --
+    "low", "high" or a sequence of layer indices (stored as a tuple; resolved against the model at submit()), None is off;
+    dola_relative_top in (0, 1], 0.1 by default. A DoLa request takes one decode row. Refused together with guidance_scale
+    (NotImplementedError). repr shows them when dola_layers is set."""
+    DOLA_NAMES = ("dola_layers", "dola_relative_top")
     GUIDE_NAMES = ("guidance_scale", "negative_prompt_ids", "guidance_plausibility", "negative_images")
     TRUNC_NAMES = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
     TOP_LOGPROBS_MAX = 20                        # VT_LOGPROB_MAX_TOP
 
     def __init__(self, *args, min_p: float = 0.0, typical_p: float = 1.0, epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0,
                  top_logprobs: int = 0, automaton=None, guidance_scale=None, negative_prompt_ids=None, guidance_plausibility=0.0,
-                 negative_images=None, **kw):
+                 negative_images=None, dola_layers=None, dola_relative_top=0.1, **kw):
         for name, value in zip(self.TRUNC_NAMES, (min_p, typical_p, epsilon_cutoff, eta_cutoff)):
             object.__setattr__(self, name, value)
         object.__setattr__(self, "top_logprobs", top_logprobs)
@@ -251,6 +269,8 @@ class SamplingParams(_SamplingFields):
             negative_prompt_ids = tuple(flat.tolist()) if flat.ndim == 1 else flat
         for name, value in zip(self.GUIDE_NAMES, (guidance_scale, negative_prompt_ids, guidance_plausibility, negative_images)):
             object.__setattr__(self, name, value)
+        object.__setattr__(self, "dola_layers", tuple(dola_layers) if isinstance(dola_layers, list) else dola_layers)
+        object.__setattr__(self, "dola_relative_top", dola_relative_top)
         super().__init__(*args, **kw)            # (its __post_init__ validates: the four are set by then)
 
     def __setattr__(self, name, value):          # (the frozen base guards its own fields only once it is subclassed)
@@ -286,6 +306,16 @@ class SamplingParams(_SamplingFields):
                 raise ValueError("SamplingParams: negative_prompt_ids is text-only here: every entry must be a token id >= 0 (no image / "
                                  "region sentinels)")
 
+        # (the layer indices are checked against the model at submit(): 2 ** 30 stands for "any depth" here)
+        check_dola(self.dola_layers, self.dola_relative_top, 2 ** 30, what="SamplingParams")
+        if self.dola and self.guided:
+            raise NotImplementedError("SamplingParams: dola_layers together with guidance_scale is not implemented: one contrast per request")
+
+    @property
+    def dola(self) -> bool:
+        """Does the request run DoLa (vt_dola_rows in front of its pick)?"""
+        return self.dola_layers is not None
+
     @property
     def guided(self) -> bool:
         """Does the request run classifier-free guidance (a second sequence, vt_cfg_rows in front of its pick)?"""
@@ -306,7 +336,8 @@ class SamplingParams(_SamplingFields):
     def _key(self) -> tuple:
         return tuple(getattr(self, n) for n in self.__dataclass_fields__) + self.trunc_row_raw() + (int(self.top_logprobs),) \
             + (None if self.automaton is None else id(self.automaton),) \
-            + ((self.guidance_scale, self.negative_prompt_ids) if self.guidance_scale is not None or self.negative_prompt_ids is not None else ())
+            + ((self.guidance_scale, self.negative_prompt_ids) if self.guidance_scale is not None or self.negative_prompt_ids is not None else ()) \
+            + (("dola", self.dola_layers, self.dola_relative_top) if self.dola_layers is not None else ())
 
     def __eq__(self, other):
         return self._key() == other._key() if other.__class__ is self.__class__ else NotImplemented
@@ -321,12 +352,14 @@ class SamplingParams(_SamplingFields):
         if self.automaton is not None:
             names.append("automaton")
         names += [n for n, off in zip(self.GUIDE_NAMES, (None, None, 0.0, None)) if getattr(self, n) is not off and getattr(self, n) != off]
+        if self.dola_layers is not None:
+            names += list(self.DOLA_NAMES)
         return "SamplingParams(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in names) + ")"
 
     def replace(self, **changes) -> "SamplingParams":
         """A copy with some settings changed (dataclasses.replace knows only the dataclass fields)."""
         kw = {n: getattr(self, n) for n in list(self.__dataclass_fields__) + list(self.TRUNC_NAMES) + ["top_logprobs", "automaton"]
-              + list(self.GUIDE_NAMES)}
+              + list(self.GUIDE_NAMES) + list(self.DOLA_NAMES)}
         kw.update(changes)
         return SamplingParams(**kw)
 
@@ -620,6 +653,75 @@ def pack_cfg_rows(rows: Sequence[tuple], device):
     import torch
     arr = cfg_rows_array(rows)
     return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), CFG_ROW_BYTES)).to(device)
+
+
+# ---- DoLa: struct vt_dola_row (the host statement of the contract is tests/dola_ref.py) ------------------------------------------------
+def dola_candidate_layers(dola_layers, num_hidden_layers: int, tie_word_embeddings: bool = False) -> Tuple[int, ...]:
+    """The candidate (premature) layers of generate(dola_layers=...), transformers 4.4x' rule: index i is hidden_states[i], the INPUT
+    stream of decoder layer i (0 = the embeddings). "low" / "high" are every second layer of the lower / upper half (N <= 40), or of the
+    first / last 20 layers (N > 40), starting at 2 when the embeddings are tied (layer 0 is then the lm_head's own transpose). A list:
+    distinct ints in [0, N), kept in the given order. At most DOLA_MAX_LAYERS candidates; anything else, or an empty result, is a
+    ValueError."""
+    N = int(num_hidden_layers)
+    start = 2 if tie_word_embeddings else 0
+    if isinstance(dola_layers, str):
+        if dola_layers not in ("low", "high"):
+            raise ValueError(f"dola_layers must be 'low', 'high' or a list of layer indices, got {dola_layers!r}")
+        if N <= 40:
+            cand = range(start, N // 2, 2) if dola_layers == "low" else range(N // 2, N, 2)
+        else:
+            cand = range(start, 20, 2) if dola_layers == "low" else range(N - 20, N, 2)
+        cand = tuple(cand)
+    elif isinstance(dola_layers, (list, tuple)):
+        for t in dola_layers:
+            if not isinstance(t, numbers.Integral) or isinstance(t, bool) or not 0 <= t < N:
+                raise ValueError(f"dola_layers: every entry must be an int in [0, {N}), got {t!r}")
+        cand = tuple(int(t) for t in dola_layers)
+        if len(set(cand)) != len(cand):
+            raise ValueError(f"dola_layers: a layer is named twice in {list(cand)!r}")
+    else:
+        raise ValueError(f"dola_layers must be 'low', 'high' or a list of layer indices, got {dola_layers!r}")
+    if not cand:
+        raise ValueError(f"dola_layers={dola_layers!r} names no layer of a {N}-layer model")
+    if len(cand) > DOLA_MAX_LAYERS:
+        raise ValueError(f"dola_layers={dola_layers!r} names {len(cand)} layers, more than {DOLA_MAX_LAYERS}")
+    return cand
+
+
+def check_dola(dola_layers, relative_top, num_hidden_layers: int, tie_word_embeddings: bool = False, what: str = "generate"):
+    """(candidate layers, relative_top) of a DoLa request, or (None, relative_top) when dola_layers is None (off). relative_top is a
+    finite number in (0, 1] (transformers fixes it at 0.1)."""
+    if not isinstance(relative_top, numbers.Real) or isinstance(relative_top, bool) or not 0 < relative_top <= 1:
+        raise ValueError(f"{what}: dola_relative_top must be a number in (0, 1], got {relative_top!r}")
+    if dola_layers is None:
+        return None, float(relative_top)
+    try:
+        return dola_candidate_layers(dola_layers, num_hidden_layers, tie_word_embeddings), float(relative_top)
+    except ValueError as e:
+        raise ValueError(f"{what}: {e}") from None
+
+
+def dola_rows_array(rows: Sequence[tuple]) -> np.ndarray:
+    """Host array of vt_dola_row from one tuple per row:
+        (final_ptr, prem_ptr, prem_stride, n_cand, out_ptr, base_ptr, mask_out_ptr, layer_out_ptr, div_out_ptr, lse_out_ptr, log_relative_top)
+    final_ptr == 0 makes the row one the kernel skips. The pointers are DEVICE addresses (tensor.data_ptr(), 0 for NULL) whose owners the
+    caller keeps alive until the launch has run; out_ptr may equal final_ptr (in place)."""
+    arr = np.zeros((len(rows),), dtype=DOLA_ROW_DTYPE)
+    for i, (final, prem, stride, n_cand, out, base, mask_out, layer_out, div_out, lse_out, lrt) in enumerate(rows):
+        ptrs = [int(x) for x in (final, prem, out, base, mask_out, layer_out, div_out, lse_out)]
+        if min(ptrs) < 0 or (ptrs[0] and not (ptrs[1] and ptrs[2])):
+            raise ValueError(f"dola row {i}: a negative address, or a final row without its candidates and out")
+        if ptrs[0] and ptrs[4] and ptrs[4] == ptrs[3]:
+            raise ValueError(f"dola row {i}: mask_out must not alias base")
+        arr[i] = (*ptrs, int(stride), int(n_cand), float(lrt))
+    return arr
+
+
+def pack_dola_rows(rows: Sequence[tuple], device):
+    """Device form of `dola_rows_array(rows)`: a uint8 tensor [len(rows), 80] for ops.dola_rows."""
+    import torch
+    arr = dola_rows_array(rows)
+    return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), DOLA_ROW_BYTES)).to(device)
 
 
 # ---- additive adjustments: struct vt_bias_row and the host statement of vt_bias_rows' contract --------------------------------------

@@ -28,6 +28,7 @@ cannot fit even an empty pool of that size fails instead of blocking the queue f
 from __future__ import annotations
 
 import collections
+import math
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 
@@ -38,7 +39,7 @@ from . import ops
 from .engine import PagedKVCache, SequenceState, llama_forward, pair_lo, parse_kv_cache_dtype
 from .picker import device_history
 from .sampling import (BIAS_ROWS_MAX_V, LogitAdjust, SamplingParams, check_constraints, flatten_ban_seqs, mask_words, pack_ban_rows,
-                       pack_bias_rows, pack_cfg_rows, pack_fsm_rows, pack_sample_rows, pack_trunc_rows, step_allow_mask)
+                       pack_bias_rows, pack_cfg_rows, pack_dola_rows, check_dola, pack_fsm_rows, pack_sample_rows, pack_trunc_rows, step_allow_mask)
 
 
 @dataclass
@@ -85,6 +86,7 @@ class _Request:
     neg_ids: Optional[torch.Tensor] = None           # device ids [1, Ln] of the negative prompt (text only)
     neg_flat: Optional[torch.Tensor] = None          # its embedded rows [Ln, H] (kept while the request waits for pages)
     need_neg: int = 0                                # the part of `need` that is the second sequence's
+    dola: Optional[tuple] = None                     # a DoLa request's candidate layers, resolved against the model
 
     @property
     def rows(self) -> int:
@@ -132,7 +134,10 @@ class ServingEngine:
         its legacy row parameters.
         sampling.guidance_scale (None or 1 is off): classifier-free guidance against sampling.negative_prompt_ids (text
         only; None: the prompt's last token, a ValueError when that is a sentinel). The request owns a second sequence and takes two of
-        max_batch's rows; its tokens equal generate(guidance_scale=, negative_prompt_ids=) for the request alone."""
+        max_batch's rows; its tokens equal generate(guidance_scale=, negative_prompt_ids=) for the request alone.
+        sampling.dola_layers (None is off): DoLa decoding with sampling.dola_relative_top. The request takes one decode
+        row; its tokens equal generate(dola_layers=, dola_relative_top=) for the request alone. ValueError here when the layers do not
+        fit the model."""
         ids = input_ids if input_ids.dim() == 2 else input_ids.unsqueeze(0)
         if ids.shape[0] != 1:
             raise ValueError("submit() takes one sequence per request")
@@ -146,6 +151,10 @@ class ServingEngine:
             check_constraints(sampling, eos_set, int(self.model.config.vocab_size))     # ValueError: nothing is queued
             if sampling.automaton is not None:
                 sampling.automaton.check(int(self.model.config.vocab_size), sorted(eos_set))
+        dola = None
+        if sampling is not None and sampling.dola:
+            dola, _ = check_dola(sampling.dola_layers, sampling.dola_relative_top, int(self.model.config.num_hidden_layers),
+                                 bool(getattr(self.model.config, "tie_word_embeddings", False)), what="submit(sampling=SamplingParams(...))")
         neg = None
         if sampling is not None and sampling.guided:
             if self.max_batch < 2:
@@ -168,7 +177,7 @@ class ServingEngine:
             if not adjust.active:
                 adjust = None
         r = _Request(self._next_id, ids.to(self.model.device), images, regions, int(max_new_tokens), eos_set, sampling=sampling,
-                     adjust=adjust)
+                     adjust=adjust, dola=dola)
         if neg is not None:
             r.nseq, r.neg_ids = SequenceState(), neg.to(self.model.device)
         self._next_id += 1
@@ -217,6 +226,48 @@ class ServingEngine:
             else:
                 rows.append((0, 0, 0, 0, 0, 0, 1.0, -float("inf")))
         ops.cfg_rows(pack_cfg_rows(rows, logits.device), len(rows), V)
+
+    @staticmethod
+    def _dola_layers(reqs: List[_Request]) -> Optional[List[int]]:
+        """The union of the candidate layers of the DoLa requests among `reqs` -- what their decoder pass traces -- or None."""
+        layers = sorted({l for r in reqs if r.dola for l in r.dola})
+        return layers or None
+
+    def _forward(self, llama, seqs, x, lens, reqs: List[_Request], embeds_lo=None):
+        """llama_forward over `seqs` (the sequences of `reqs` first); with a DoLa request among `reqs` the pass also traces the union of
+        their candidate layers at its logit rows and _dola contrasts those requests' rows before the logits are returned. Without
+        one it is the call it always was."""
+        layers = self._dola_layers(reqs)
+        if layers is None:
+            return llama_forward(llama, self.model.kv, seqs, x, lens, embeds_lo=embeds_lo)
+        logits, trace = llama_forward(llama, self.model.kv, seqs, x, lens, embeds_lo=embeds_lo, trace_rows_layers=layers)
+        self._dola(llama, logits, reqs, trace)
+        return logits
+
+    def _dola(self, llama, logits: torch.Tensor, reqs: List[_Request], trace: torch.Tensor) -> None:
+        """DoLa in front of _pick. trace: the operand-dtype [L, rows, H] logit-row trace of the pass that produced
+        `logits` (row i belongs to reqs[i]). ONE gather of the DoLa requests' candidate rows, the bare lm_head over them in launches of
+        at most 16 rows (the weight-streaming GEMM of a decode step's lm_head), and ONE vt_dola_rows launch over the rows of `logits`
+        that writes the contrasted row in place over the final row of every DoLa request; every other row carries final = NULL and is
+        untouched. The filtered tokens are -inf in the row, which no later stage can raise."""
+        V, n_rows = int(logits.shape[1]), int(trace.shape[1])
+        idx, first = [], {}
+        for i, r in enumerate(reqs):
+            if r.dola:
+                first[i] = len(idx)
+                idx += [l * n_rows + i for l in r.dola]
+        gathered = trace.view(-1, llama.H).index_select(0, torch.tensor(idx, dtype=torch.long).to(trace.device))
+        prem = torch.empty((len(idx), llama.V_pad), dtype=torch.float32, device=trace.device)
+        for r0 in range(0, len(idx), 16):
+            ops.gemm(gathered[r0:r0 + 16], llama.lm_head, None, ops.EPI_F32, out=prem[r0:r0 + 16])
+        rows = []
+        for i, r in enumerate(reqs):
+            if i in first:
+                f = logits[i].data_ptr()
+                rows.append((f, prem[first[i]].data_ptr(), llama.V_pad, len(r.dola), f, 0, 0, 0, 0, 0, math.log(r.sampling.dola_relative_top)))
+            else:
+                rows.append((0,) * 10 + (0.0,))
+        ops.dola_rows(pack_dola_rows(rows, logits.device), len(rows), V)
 
     @staticmethod
     def _is_device_error(exc: BaseException) -> bool:
@@ -473,7 +524,7 @@ class ServingEngine:
 
         def prefill_one(r):
             try:
-                logits = llama_forward(llama, m.kv, [r.seq], r.flat, [r.flat.shape[0]], embeds_lo=getattr(r, "flat_lo", None))
+                logits = self._forward(llama, [r.seq], r.flat, [r.flat.shape[0]], [r], embeds_lo=getattr(r, "flat_lo", None))
                 if r.nseq is not None:
                     self._guide(logits, [r], {0: prefill_neg(r)})
                 r.last = self._pick(logits, [r])
@@ -501,7 +552,8 @@ class ServingEngine:
                     lo_cat = None
                     if any(l is not None for l in los):      # (requests without visual rows have an exact 16-bit embedding: low half zero)
                         lo_cat = torch.cat([l if l is not None else torch.zeros_like(f) for l, f in zip(los, flats)], 0)
-                    logits = llama_forward(llama, m.kv, [r.seq for r in admitted], torch.cat(flats, 0), [f.shape[0] for f in flats], embeds_lo=lo_cat)
+                    logits = self._forward(llama, [r.seq for r in admitted], torch.cat(flats, 0), [f.shape[0] for f in flats], admitted,
+                                           embeds_lo=lo_cat)
                     unc = {i: prefill_neg(r) for i, r in enumerate(admitted) if r.nseq is not None}
                     if unc:
                         self._guide(logits, admitted, unc)
@@ -603,7 +655,7 @@ class ServingEngine:
             ids = torch.cat([r.last for r in self.active] + [self.active[i].last for i in guided]).to(torch.int32)
             plan = torch.stack([torch.zeros_like(ids), ids], dim=1).contiguous()
             x = ops.embed_splice(llama.embed, None, None, plan)
-            logits = llama_forward(llama, m.kv, seqs, x, [1] * len(seqs))
+            logits = self._forward(llama, seqs, x, [1] * len(seqs), self.active)
             if guided:
                 n = len(self.active)
                 unc = {i: logits[n + j] for j, i in enumerate(guided)}
