@@ -3,58 +3,24 @@
 // beam's hypothesis gets that beam's generated tail.
 //
 // vt_beam_step, two launches:
-//   stage 1 (one 1024-thread block per row): the row's log-sum-exp -- the same expression as the sampler's logprob in vt_llama.hip,
-//     restated here so that file keeps its code: m = max, z = sum expf(x - m), lse = m + logf(z) -- then the candidate score
-//     s = (x - lse) + beam_score of every token and the row's own n_out best by repeated block arg-max. No candidate outside a row's
-//     own n_out best can be among the group's n_out best, so this loses nothing.
+//   stage 1 (one 1024-thread block per row): the row's log-sum-exp -- vt_rows.h's expression and reductions, the streamed form in its
+//     vec order: m = max, z = sum expf(x - m), lse = m + logf(z) -- then the candidate score s = (x - lse) + beam_score of every token
+//     and the row's own n_out best by repeated block arg-max. No candidate outside a row's own n_out best can be among the group's
+//     n_out best, so this loses nothing.
 //   stage 2 (one wave per group): merges the beams_in * n_out survivors.
 // Order everywhere: larger score first, exact ties by the lower flat index b * V + t. A pass never marks what it took: pass p takes
 // the best candidate strictly AFTER pass p - 1's pick in that order, so the selection needs no mask and the logits are only read.
 // A NaN score is never taken; a row needs a finite maximum.
 #include "vt_common.h"
 #include "vt_kernels.h"
+#include "vt_rows.h"
 
 namespace {
 
-constexpr int kNone = 0x7fffffff;
-
-// (score, index) pairs ordered by larger score, then lower index
-__device__ __forceinline__ void beam_take(float& best, int& bi, float v, int i) {
-  if (v > best || (v == best && i < bi)) {
-    best = v;
-    bi = i;
-  }
-}
-// is (v, i) strictly after (ls, li) in that order?
+// vt_rows.h's (value, index) order in its branch form (see there why), and the after test spelled to match (with row_after's & and |
+// beam_merge_kernel allocates 32 VGPRs instead of 33)
+constexpr RowTakeIf beam_take{};
 __device__ __forceinline__ bool beam_after(float v, int i, float ls, int li) { return v < ls || (v == ls && i > li); }
-
-__device__ __forceinline__ void wave_beam_max(float& best, int& bi) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    beam_take(best, bi, ov, oi);
-  }
-}
-
-__device__ __forceinline__ float beam_block_sum(float v, float* sh) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-  for (int i = 0; i < 16; ++i) t += sh[i];
-  return t;
-}
-__device__ __forceinline__ float beam_block_max(float v, float* sh) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = sh[0];
-  for (int i = 1; i < 16; ++i) t = fmaxf(t, sh[i]);
-  return t;
-}
 
 // Stage 1. kReg (V <= 32 * 1024): the row is read ONCE, 32 values per thread, and the n_out arg-max passes run over registers;
 // otherwise a thread streams its part of the row again (L2) whenever it looks for its next candidate. vec: 16-byte loads (row
@@ -75,8 +41,10 @@ __global__ __launch_bounds__(1024) void beam_rows_kernel(const float* __restrict
   const float bs = beam_scores[r];
   float x[kReg ? 32 : 1];
   auto slot_index = [&](int j, int k) { return vec ? 4 * (tid + 1024 * j) + k : tid + 1024 * (4 * j + k); };
-  float mx = -INFINITY;
+  float mx, z;
   if constexpr (kReg) {
+    // vt_rows.h's row_load32 with beam's second slot layout, for rows that 16-byte loads cannot reach, folded into its tail branch
+    // (two loaders behind one test of `vec` are 24 more loads and 25 more branches in the kernel, and 0.04 us at 4 rows)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       if (vec && 4 * (tid + 1024 * j) + 3 < V) {
@@ -91,29 +59,13 @@ __global__ __launch_bounds__(1024) void beam_rows_kernel(const float* __restrict
         }
       }
     }
-#pragma unroll
-    for (int s = 0; s < 32; ++s) mx = fmaxf(mx, x[s]);
+    mx = row_block_max(row_max32(x), sh);
+    z = row_sumexp32(x, mx);
   } else {
-    for (int i = tid; i < V4; i += 1024) {
-      const f32x4 v = *(const f32x4*)(row + 4 * i);
-      mx = fmaxf(fmaxf(mx, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
-    }
-    for (int i = 4 * V4 + tid; i < V; i += 1024) mx = fmaxf(mx, row[i]);
+    mx = row_block_max(row_stream_max_vec(row, V, V4, tid), sh);
+    z = row_stream_sumexp_vec(row, V, V4, tid, mx);
   }
-  mx = beam_block_max(mx, sh);
-  float z = 0.f;
-  if constexpr (kReg) {
-#pragma unroll
-    for (int s = 0; s < 32; ++s) z += expf(x[s] - mx);       // (a slot past V holds -inf: expf gives 0)
-  } else {
-    for (int i = tid; i < V4; i += 1024) {
-      const f32x4 v = *(const f32x4*)(row + 4 * i);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) z += expf(v[k] - mx);
-    }
-    for (int i = 4 * V4 + tid; i < V; i += 1024) z += expf(row[i] - mx);
-  }
-  z = beam_block_sum(z, sh);
+  z = row_block_sum(z, sh);
   const float lse = mx + logf(z);
   if constexpr (kReg) {
 #pragma unroll
@@ -122,7 +74,7 @@ __global__ __launch_bounds__(1024) void beam_rows_kernel(const float* __restrict
   // the best of this thread's own candidates strictly after (ls, li)
   auto scan = [&](float ls, int li, float& best, int& bi) {
     best = -INFINITY;
-    bi = kNone;
+    bi = kRowNone;
     if constexpr (kReg) {
 #pragma unroll
       for (int j = 0; j < 8; ++j)
@@ -133,18 +85,10 @@ __global__ __launch_bounds__(1024) void beam_rows_kernel(const float* __restrict
           if (i < V && beam_after(s, i, ls, li)) beam_take(best, bi, s, i);
         }
     } else {
-      for (int i4 = tid; i4 < V4; i4 += 1024) {
-        const f32x4 v = *(const f32x4*)(row + 4 * i4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float s = (v[k] - lse) + bs;
-          if (beam_after(s, 4 * i4 + k, ls, li)) beam_take(best, bi, s, 4 * i4 + k);
-        }
-      }
-      for (int i = 4 * V4 + tid; i < V; i += 1024) {
-        const float s = (row[i] - lse) + bs;
+      row_for_each_vec(row, V, V4, tid, [&](float v, int i) {
+        const float s = (v - lse) + bs;
         if (beam_after(s, i, ls, li)) beam_take(best, bi, s, i);
-      }
+      });
     }
   };
   // Every thread keeps the best of its own candidates that no pass has taken (mb, mi). A pass is a block arg-max over those; only the
@@ -155,7 +99,7 @@ __global__ __launch_bounds__(1024) void beam_rows_kernel(const float* __restrict
   for (int p = 0; p < n_out; ++p) {
     float best = mb;
     int bi = mi;
-    wave_beam_max(best, bi);
+    row_wave_argmax(best, bi, beam_take);
     // two LDS buffers in turn: a wave that writes pass p + 2's has passed pass p + 1's barrier, behind which nobody reads pass p's
     if (lane == 0) {
       sv[p & 1][wave] = best;
@@ -167,9 +111,9 @@ __global__ __launch_bounds__(1024) void beam_rows_kernel(const float* __restrict
     for (int w = 1; w < 16; ++w) beam_take(best, bi, sv[p & 1][w], si[p & 1][w]);
     if (tid == 0) {
       cand_s[(size_t)r * n_out + p] = best;
-      cand_t[(size_t)r * n_out + p] = bi == kNone ? -1 : bi;
+      cand_t[(size_t)r * n_out + p] = bi == kRowNone ? -1 : bi;
     }
-    if (bi == mi && bi != kNone) scan(best, bi, mb, mi);     // (kNone: nothing is left, the remaining passes write (-inf, -1))
+    if (bi == mi && bi != kRowNone) scan(best, bi, mb, mi);     // (kRowNone: nothing is left, the remaining passes write (-inf, -1))
   }
 }
 
@@ -185,7 +129,7 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const float* __restrict_
   for (int j = 0; j < 8; ++j) {
     const int c = lane + 64 * j;
     s[j] = -INFINITY;
-    f[j] = kNone;
+    f[j] = kRowNone;
     if (c < C) {
       const int t = cand_t[(size_t)g * C + c];
       if (t >= 0) {
@@ -198,15 +142,15 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const float* __restrict_
   int li = -1;
   for (int p = 0; p < n_out; ++p) {
     float best = -INFINITY;
-    int bi = kNone;
+    int bi = kRowNone;
 #pragma unroll
     for (int j = 0; j < 8; ++j)
-      if (f[j] != kNone && beam_after(s[j], f[j], ls, li)) beam_take(best, bi, s[j], f[j]);
-    wave_beam_max(best, bi);
+      if (f[j] != kRowNone && beam_after(s[j], f[j], ls, li)) beam_take(best, bi, s[j], f[j]);
+    row_wave_argmax(best, bi, beam_take);
     if (lane == 0) {
       out_scores[(size_t)g * n_out + p] = best;
-      out_tokens[(size_t)g * n_out + p] = bi == kNone ? -1 : bi % V;
-      out_beams[(size_t)g * n_out + p] = bi == kNone ? -1 : bi / V;
+      out_tokens[(size_t)g * n_out + p] = bi == kRowNone ? -1 : bi % V;
+      out_beams[(size_t)g * n_out + p] = bi == kRowNone ? -1 : bi / V;
     }
     ls = best;
     li = bi;

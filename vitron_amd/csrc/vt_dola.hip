@@ -1,14 +1,14 @@
 // vt_dola.hip -- vt_dola_rows: DoLa, "Decoding by Contrasting Layers" (Chuang et al. 2023), over logit rows -- the
 // arithmetic of transformers 4.4x' _dola_decoding / _dola_select_contrast / _relative_top_filter. A row names the final layer's logit row
 // and n_cand rows of early ("premature") layers' streams put through the lm_head. Per row, everything in fp32:
-//     lse_x  = m + logf(sum_i expf(x_i - m)),  m = max x                                  (vt_logprob_rows' expression)
+//     lse_x  = m + logf(sum_i expf(x_i - m)),  m = max x                                  (vt_rows.h; vt_logprob_rows' too)
 //     div_j  = 0.5 * sum_i [ M (log M - lpf) + M (log M - lpj) ],  lpf = f_i - lse_f,  lpj = x_i - lse_j,  M = 0.5 (expf(lpf) + expf(lpj)),
 //              a term with M == 0 counting 0                                              (F.kl_div(log_softmax, average): KL(M || p))
 //     j*     = 0;  for j = 1 .. n_cand - 1:  if div_j > div_j*:  j* = j                    (the largest, ties and NaNs to the lower j)
 //     out_i  = f_i >= m_f + log_relative_top  ?  (f_i - lse_f) - (x_i - lse_j*)  :  -inf   (x = candidate j*)
 // with each of the three subtractions of out rounded on its own, so that `out` follows bit for bit from the inputs, two lse values and
-// j*. mask_out bit i = base bit i AND (f_i >= m_f + log_relative_top), vt_cfg_rows' layout and tail-bit rule. One candidate: j* = 0 and
-// no divergence is computed (div_out[0] = 0).
+// j*. mask_out bit i = base bit i AND (f_i >= m_f + log_relative_top), vt_rows.h's layout and tail-bit rule, as vt_cfg_rows'. One
+// candidate: j* = 0 and no divergence is computed (div_out[0] = 0).
 // One launch, one 1024-thread block per row; no workspace, no atomics, plain vector stores only. Two forms, chosen per ROW:
 //   register form (V <= 32 * 1024; final, prem and out 16-byte aligned, prem_stride % 4 == 0): the final row is read ONCE and stays in
 //     registers (thread t owns the floats 4 (t + 1024 j) + k); every candidate is read once into a second set of 32 registers, where its
@@ -20,6 +20,7 @@
 // NaN and +-inf propagate by IEEE rules (fmaxf skips a NaN, the sums do not); a NaN div is never chosen over an earlier candidate.
 #include "vt_common.h"
 #include "vt_kernels.h"
+#include "vt_rows.h"
 
 static_assert(sizeof(vt_dola_row) == 80 && alignof(vt_dola_row) == 8, "vt_dola_row is 80 bytes, 8-byte aligned (ABI)");
 static_assert(offsetof(vt_dola_row, final) == 0 && offsetof(vt_dola_row, prem) == 8 && offsetof(vt_dola_row, out) == 16 &&
@@ -30,27 +31,6 @@ static_assert(offsetof(vt_dola_row, final) == 0 && offsetof(vt_dola_row, prem) =
 
 namespace {
 
-constexpr int kDolaThreads = 1024;
-
-// vt_logprob_rows' block reductions: 6 shuffle levels, then the 16 wave totals serially
-__device__ __forceinline__ float dola_block_max(float v, float* sh) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = sh[0];
-  for (int i = 1; i < 16; ++i) t = fmaxf(t, sh[i]);
-  return t;
-}
-__device__ __forceinline__ float dola_block_sum(float v, float* sh) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-  for (int i = 0; i < 16; ++i) t += sh[i];
-  return t;
-}
 // one term of the divergence; every operation rounded on its own (tests/dola_ref.py restates it in numpy float32)
 __device__ __forceinline__ float dola_term(float f, float x, float lse_f, float lse_j) {
 #pragma clang fp contract(off)
@@ -69,58 +49,19 @@ __device__ __forceinline__ float dola_out(float f, float x, float lse_f, float l
   const float r = a - b;
   return f >= thr ? r : -INFINITY;
 }
-__device__ __forceinline__ uint32_t dola_base_word(const uint32_t* base, int w, int W, int V) {
-  if (base != nullptr) return base[w];
-  return (w == W - 1 && (V & 31)) ? (1u << (V & 31)) - 1u : 0xffffffffu;
-}
-// 32 floats of a row into registers: thread t owns 4 (t + 1024 j) + k; slots past V hold -inf
-__device__ __forceinline__ void dola_load32(const float* row, int V, int tid, float (&x)[32]) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int i0 = 4 * (tid + 1024 * j);
-    if (i0 + 3 < V) {
-      const f32x4 v = *(const f32x4*)(row + i0);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) x[4 * j + k] = v[k];
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) x[4 * j + k] = i0 + k < V ? row[i0 + k] : -INFINITY;
-    }
-  }
-}
-__device__ __forceinline__ float dola_lse32(const float (&x)[32], float* sh, float& mx) {
-  mx = -INFINITY;
-#pragma unroll
-  for (int s = 0; s < 32; ++s) mx = fmaxf(mx, x[s]);
-  mx = dola_block_max(mx, sh);
-  float z = 0.f;
-#pragma unroll
-  for (int s = 0; s < 32; ++s) z += expf(x[s] - mx);       // (a slot past V holds -inf: expf gives 0)
-  z = dola_block_sum(z, sh);
-  return mx + logf(z);
-}
-__device__ __forceinline__ float dola_lse_stream(const float* row, int V, int tid, float* sh, float& mx) {
-  mx = -INFINITY;
-  for (int i = tid; i < V; i += kDolaThreads) mx = fmaxf(mx, row[i]);
-  mx = dola_block_max(mx, sh);
-  float z = 0.f;
-  for (int i = tid; i < V; i += kDolaThreads) z += expf(row[i] - mx);
-  z = dola_block_sum(z, sh);
-  return mx + logf(z);
-}
-
+// The lse, the mask's starting word and the two mask builders are vt_rows.h's. (tests/test_dola_ref_host.py reads dola_out's body as
+// the text up to "__device__ __forceinline__ uint32_t dola_base_word", the function that stood here: it is row_base_word now.)
 template <bool kReg>
-__global__ __launch_bounds__(kDolaThreads) void dola_rows_kernel(const vt_dola_row* __restrict__ rows, int V) {
+__global__ __launch_bounds__(kRowThreads) void dola_rows_kernel(const vt_dola_row* __restrict__ rows, int V) {
   __shared__ float sh[16];
   const vt_dola_row row = rows[blockIdx.x];
   if (row.final == nullptr) return;      // block-uniform, before any barrier: the row is skipped entirely
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int n_cand = row.n_cand;
   if (n_cand < 1 || n_cand > VT_DOLA_MAX_LAYERS) {     // bad row content: nothing is read or written but layer_out = -1
     if (tid == 0 && row.layer_out != nullptr) *row.layer_out = -1;
     return;
   }
-  const int W = (V + 31) >> 5;
   const float* fin = row.final;          // (no __restrict__: out may alias final)
   const float* prem = row.prem;
   const long long stride = row.prem_stride;
@@ -129,16 +70,16 @@ __global__ __launch_bounds__(kDolaThreads) void dola_rows_kernel(const vt_dola_r
 
   if (kReg && aligned) {
     float f[32], x[32];
-    dola_load32(fin, V, tid, f);
+    row_load32(fin, V, tid, f);
     float mf;
-    const float lse_f = dola_lse32(f, sh, mf);
+    const float lse_f = row_lse32(f, sh, mf);
     if (tid == 0 && row.lse_out != nullptr) row.lse_out[0] = lse_f;
     int jb = 0;
     float db = 0.f, lse_b = 0.f;
     for (int j = 0; j < n_cand; ++j) {
-      dola_load32(prem + j * stride, V, tid, x);
+      row_load32(prem + j * stride, V, tid, x);
       float mj;
-      const float lse_j = dola_lse32(x, sh, mj);
+      const float lse_j = row_lse32(x, sh, mj);
       float d = 0.f;
       if (n_cand > 1) {                  // block-uniform
         // lse_f through an empty asm: otherwise the compiler hoists the 32 f_i - lse_f and their expf out of the candidate loop, 64
@@ -148,7 +89,7 @@ __global__ __launch_bounds__(kDolaThreads) void dola_rows_kernel(const vt_dola_r
         asm volatile("" : "+v"(lf));
 #pragma unroll
         for (int s = 0; s < 32; ++s) d += dola_term(f[s], x[s], lf, lse_j);
-        d = 0.5f * dola_block_sum(d, sh);
+        d = 0.5f * row_block_sum(d, sh);
       }
       if (tid == 0) {
         if (row.lse_out != nullptr) row.lse_out[1 + j] = lse_j;
@@ -161,53 +102,27 @@ __global__ __launch_bounds__(kDolaThreads) void dola_rows_kernel(const vt_dola_r
       }
     }
     if (tid == 0 && row.layer_out != nullptr) *row.layer_out = jb;
-    if (jb != n_cand - 1) dola_load32(prem + jb * stride, V, tid, x);
+    if (jb != n_cand - 1) row_load32(prem + jb * stride, V, tid, x);
     const float thr = mf + row.log_relative_top;
-    if (row.mask_out != nullptr) {       // block-uniform: every lane takes part in the shuffles
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int i0 = 4 * (tid + 1024 * j);
-        uint32_t nib = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) nib |= ((i0 + k >= V) | (f[4 * j + k] >= thr)) ? (1u << k) : 0u;
-        uint32_t word = nib << (4 * (tid & 7));
-        word |= __shfl_xor(word, 1, 64);
-        word |= __shfl_xor(word, 2, 64);
-        word |= __shfl_xor(word, 4, 64);
-        const int w = (tid >> 3) + 128 * j;
-        if ((tid & 7) == 0 && w < W) row.mask_out[w] = word & dola_base_word(row.base, w, W, V);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int i0 = 4 * (tid + 1024 * j);
-      f32x4 o;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) o[k] = dola_out(f[4 * j + k], x[4 * j + k], lse_f, lse_b, thr);
-      if (i0 + 3 < V) {
-        *(f32x4*)(out + i0) = o;
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if (i0 + k < V) out[i0 + k] = o[k];
-      }
-    }
+    if (row.mask_out != nullptr)         // block-uniform: every lane takes part in the shuffles
+      row_mask32(row.mask_out, row.base, V, tid, [&](int s) { return f[s] >= thr; });
+    row_store32(out, V, tid, [&](int s) { return dola_out(f[s], x[s], lse_f, lse_b, thr); });
     return;
   }
 
   float mf;
-  const float lse_f = dola_lse_stream(fin, V, tid, sh, mf);
+  const float lse_f = row_lse_stream(fin, V, tid, sh, mf);
   if (tid == 0 && row.lse_out != nullptr) row.lse_out[0] = lse_f;
   int jb = 0;
   float db = 0.f, lse_b = 0.f;
   for (int j = 0; j < n_cand; ++j) {
     const float* xr = prem + j * stride;
     float mj;
-    const float lse_j = dola_lse_stream(xr, V, tid, sh, mj);
+    const float lse_j = row_lse_stream(xr, V, tid, sh, mj);
     float d = 0.f;
     if (n_cand > 1) {
-      for (int i = tid; i < V; i += kDolaThreads) d += dola_term(fin[i], xr[i], lse_f, lse_j);
-      d = 0.5f * dola_block_sum(d, sh);
+      for (int i = tid; i < V; i += kRowThreads) d += dola_term(fin[i], xr[i], lse_f, lse_j);
+      d = 0.5f * row_block_sum(d, sh);
     }
     if (tid == 0) {
       if (row.lse_out != nullptr) row.lse_out[1 + j] = lse_j;
@@ -223,16 +138,12 @@ __global__ __launch_bounds__(kDolaThreads) void dola_rows_kernel(const vt_dola_r
   const float* xb = prem + jb * stride;
   const float thr = mf + row.log_relative_top;
   const bool want_mask = row.mask_out != nullptr;
-  for (int b0 = 0; b0 < V; b0 += kDolaThreads) {    // a block-uniform trip count: every lane reaches the ballot
+  for (int b0 = 0; b0 < V; b0 += kRowThreads) {     // a block-uniform trip count: every lane reaches the ballot
     const int i = b0 + tid;
     const bool in = i < V;
     const float fi = in ? fin[i] : 0.f;
     const float xi = in ? xb[i] : 0.f;
-    if (want_mask) {
-      const unsigned long long bal = __ballot((!in) | (fi >= thr));
-      const int w = ((b0 + 64 * wave) >> 5) + (lane >> 5);
-      if ((lane & 31) == 0 && w < W) row.mask_out[w] = (uint32_t)(bal >> (lane & 32)) & dola_base_word(row.base, w, W, V);
-    }
+    if (want_mask) row_mask_ballot(row.mask_out, row.base, V, b0, tid, (!in) | (fi >= thr));
     if (in) out[i] = dola_out(fi, xi, lse_f, lse_b, thr);
   }
 }
@@ -245,9 +156,9 @@ int vt_dola_rows_launch(const vt_dola_row* rows, int n_rows, int V, hipStream_t 
   VT_REQUIRE(V > 0 && V <= VT_LOGPROB_MAX_V, "vt_dola_rows: V=%d (0 < V <= %d)", V, VT_LOGPROB_MAX_V);
   VT_REQUIRE(((uintptr_t)rows % 8) == 0, "vt_dola_rows: rows must be 8-byte aligned");
   if (V <= 32 * 1024)
-    hipLaunchKernelGGL(dola_rows_kernel<true>, dim3(n_rows), dim3(kDolaThreads), 0, s, rows, V);
+    hipLaunchKernelGGL(dola_rows_kernel<true>, dim3(n_rows), dim3(kRowThreads), 0, s, rows, V);
   else
-    hipLaunchKernelGGL(dola_rows_kernel<false>, dim3(n_rows), dim3(kDolaThreads), 0, s, rows, V);
+    hipLaunchKernelGGL(dola_rows_kernel<false>, dim3(n_rows), dim3(kRowThreads), 0, s, rows, V);
   VT_LAUNCH_CHECK();
   return VT_OK;
 }

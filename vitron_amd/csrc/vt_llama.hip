@@ -9,6 +9,7 @@
 // logic; this kernel only moves rows.
 #include "vt_common.h"
 #include "vt_kernels.h"
+#include "vt_rows.h"
 
 namespace {
 
@@ -61,31 +62,8 @@ __global__ __launch_bounds__(256) void decode_feed_kernel(const bf16_t* __restri
   for (int c = threadIdx.x; c < (H >> 3); c += 256) *(u32x4*)(dst + c * 8) = *(const u32x4*)(src + c * 8);
 }
 
-// first-index arg-max bookkeeping of the greedy rows of vt_sample_rows, argmax_kernel's rule: (value, index) pairs ordered by larger
-// value, then lower index; a NaN is never taken.
-__device__ __forceinline__ void argmax_take(float& best, int& bi, float v, int i) {
-  if (v > best || (v == best && i < bi)) {
-    best = v;
-    bi = i;
-  }
-}
-// block-wide result in thread 0 (1024 threads); sv / si: 16 LDS slots each
-__device__ __forceinline__ void block_argmax_1024(float& best, int& bi, float* sv, int* si) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    argmax_take(best, bi, ov, oi);
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    sv[wave] = best;
-    si[wave] = bi;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int w = 1; w < 16; ++w) argmax_take(best, bi, sv[w], si[w]);
-}
+// vt_rows.h's (value, index) order in its branch form (see there why): argmax_kernel's rule, and the greedy rows of vt_sample_rows'
+constexpr RowTakeIf take{};       // (a NaN is never taken)
 
 // first index of the maximum of each row (torch.argmax tie rule on CPU: lowest index). 1024 threads per row, 16-B loads,
 // every request of the row in flight at once (a 32000-float row is 8 loads per thread).
@@ -95,38 +73,18 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ 
   __shared__ int si[16];
   const float* row = logits + (size_t)blockIdx.x * ldl;
   float best = -INFINITY;
-  int bi = 0x7fffffff;
-  auto take = [&](float v, int i) {
-    if (v > best || (v == best && i < bi)) {
-      best = v;
-      bi = i;
-    }
-  };
+  int bi = kRowNone;
   const bool vec = (ldl % 4) == 0 && ((uintptr_t)logits % 16) == 0;
   const int V4 = vec ? (V >> 2) : 0;
 #pragma unroll 8
   for (int i = threadIdx.x; i < V4; i += 1024) {
     const f32x4 v = *(const f32x4*)(row + 4 * i);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) take(v[k], 4 * i + k);
+    for (int k = 0; k < 4; ++k) take(best, bi, v[k], 4 * i + k);
   }
-  for (int i = 4 * V4 + threadIdx.x; i < V; i += 1024) take(row[i], i);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    take(ov, oi);
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    sv[wave] = best;
-    si[wave] = bi;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 16; ++w) take(sv[w], si[w]);
-    out[blockIdx.x] = bi;
-  }
+  for (int i = 4 * V4 + threadIdx.x; i < V; i += 1024) take(best, bi, row[i], i);
+  row_block_argmax(best, bi, sv, si, take);
+  if (threadIdx.x == 0) out[blockIdx.x] = bi;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -141,24 +99,6 @@ __global__ __launch_bounds__(1024) void argmax_kernel(const float* __restrict__ 
 // vt_sample_rows kernels from the row's vt_sample_row; their kRows instantiation adds the repetition penalty
 // (RepetitionPenaltyLogitsProcessor), greedy rows and the chosen token's log-probability.
 // ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_sum_1024(float v, float* sh) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = 0.f;
-  for (int i = 0; i < 16; ++i) t += sh[i];
-  return t;
-}
-__device__ __forceinline__ float block_max_1024(float v, float* sh) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = sh[0];
-  for (int i = 1; i < 16; ++i) t = fmaxf(t, sh[i]);
-  return t;
-}
 __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
   x += 0x9e3779b97f4a7c15ull;
   x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
@@ -256,14 +196,9 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
   float lse = 0.f;
   bool pen = false;
   if constexpr (kRows) {
-    if (logprob) {       // log-sum-exp of the RAW row (before penalty and temperature), expf / logf as cross_entropy_rows_kernel
-      float rmx = -INFINITY;
-      for (int i = tid; i < V; i += 1024) rmx = fmaxf(rmx, row[i]);
-      rmx = block_max_1024(rmx, sh);
-      float rz = 0.f;
-      for (int i = tid; i < V; i += 1024) rz += expf(row[i] - rmx);
-      rz = block_sum_1024(rz, sh);
-      lse = rmx + logf(rz);
+    if (logprob) {       // log-sum-exp of the RAW row (before penalty and temperature): vt_rows.h's, as cross_entropy_rows_kernel
+      float rmx;
+      lse = row_lse_stream(row, V, tid, sh, rmx);
     }
     pen = fill_seen_mask(seen, V, a);
   }
@@ -289,10 +224,10 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
     if (a.greedy) {      // block-uniform
       __shared__ int si[16];
       float best = -INFINITY;
-      int bi = 0x7fffffff;
-      for (int i = tid; i < V; i += 1024) argmax_take(best, bi, val(i), i);
+      int bi = kRowNone;
+      for (int i = tid; i < V; i += 1024) take(best, bi, val(i), i);
       __syncthreads();
-      block_argmax_1024(best, bi, sh, si);
+      row_block_argmax(best, bi, sh, si, take);
       if (tid == 0) {
         *out_id = bi;
         if (kept_out) *kept_out = 1;
@@ -303,7 +238,7 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
   }
   float mx = -INFINITY;
   for (int i = tid; i < V; i += 1024) mx = fmaxf(mx, val(i) * inv_temp);
-  mx = block_max_1024(mx, sh);
+  mx = row_block_max(mx, sh);
   float floor_logit = -INFINITY;   // scaled logits below this are outside the top-k set
   if (top_k > 0 && top_k < V) {
     uint64_t lo = 0, hi = 0x100000000ull;   // invariant: count(key >= lo) >= k, count(key >= hi) < k
@@ -311,7 +246,7 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
       const uint64_t mid = lo + ((hi - lo) >> 1);
       float c = 0.f;
       for (int i = tid; i < V; i += 1024) c += ((uint64_t)order_key(val(i) * inv_temp) >= mid) ? 1.f : 0.f;
-      c = block_sum_1024(c, sh);
+      c = row_block_sum(c, sh);
       if (c >= (float)top_k) lo = mid; else hi = mid;
     }
     const uint32_t k32 = (uint32_t)lo;
@@ -320,7 +255,7 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
 #define VT_P_OF(i) ((val(i) * inv_temp >= floor_logit) ? __expf(val(i) * inv_temp - mx) : 0.f)
   float z = 0.f;
   for (int i = tid; i < V; i += 1024) z += VT_P_OF(i);
-  z = block_sum_1024(z, sh);
+  z = row_block_sum(z, sh);
   const float inv_z = 1.f / z;
   // bisection on the threshold t in (0, 1]: mass(t) = sum of p_i with p_i >= t is non-increasing in t.
   // keep-set of the warper = {i : mass of tokens strictly above p_i < top_p}  <=>  largest t with mass(t) >= top_p.
@@ -332,7 +267,7 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
       const float p = VT_P_OF(i) * inv_z;
       if (p >= mid) m += p;
     }
-    m = block_sum_1024(m, sh);
+    m = row_block_sum(m, sh);
     if (m >= top_p) lo = mid; else hi = mid;
   }
   const float thr = (top_p >= 1.f) ? 0.f : fminf(lo, inv_z);   // inv_z = probability of the arg-max token: always kept
@@ -344,8 +279,8 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
       cnt += 1.f;
     }
   }
-  kept = block_sum_1024(kept, sh);
-  cnt = block_sum_1024(cnt, sh);
+  kept = row_block_sum(kept, sh);
+  cnt = row_block_sum(cnt, sh);
   float plo = 0.f, typ_c = 0.f;      // (kTrunc) what the stages leave: p >= plo, and with `typ` the key of |typ_c - log p| <= typ_key
   uint32_t typ_key = 0x7fffffffu;
   bool typ = false;
@@ -366,9 +301,9 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
             if (want_T) t += trunc_plogp(p);
           }
         }
-        S = block_sum_1024(s, sh);
-        top = block_max_1024(m, sh);
-        if (want_T) T = block_sum_1024(t, sh);
+        S = row_block_sum(s, sh);
+        top = row_block_max(m, sh);
+        if (want_T) T = row_block_sum(t, sh);
       };
       // "p < t leaves unless it ties with the maximum" is p >= min(t, top) for those who stay (a NaN t: only the maximum stays)
       if (on_min) {
@@ -388,7 +323,7 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
             const float p = VT_P_OF(i) * inv_z;
             if (p >= thr && val(i) * inv_temp >= floor_logit && VT_ALIVE(p) && trunc_d_key(p, c) <= mid) m += p;
           }
-          m = block_sum_1024(m, sh);
+          m = row_block_sum(m, sh);
           if (m >= need) hi = mid; else lo = mid + 1u;
         }
         typ_c = c;
@@ -412,8 +347,8 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
           cnt += 1.f;
         }
       }
-      kept = block_sum_1024(kept, sh);
-      cnt = block_sum_1024(cnt, sh);
+      kept = row_block_sum(kept, sh);
+      cnt = row_block_sum(cnt, sh);
     }
   }
   if (tid == 0 && kept_out) *kept_out = (int)cnt;
@@ -601,12 +536,12 @@ __device__ __forceinline__ void sample_reg_body(const float* __restrict__ row, i
     if (a.greedy) {      // block-uniform
       __shared__ int si[16];
       float best = -INFINITY;
-      int bi = 0x7fffffff;
+      int bi = kRowNone;
 #pragma unroll
       for (int j = 0; j < NPT; ++j)
-        if (i0 + j < V) argmax_take(best, bi, p[j], i0 + j);
+        if (i0 + j < V) take(best, bi, p[j], i0 + j);
       __syncthreads();
-      block_argmax_1024(best, bi, sh[0], si);
+      row_block_argmax(best, bi, sh[0], si, take);
       if (tid == 0) {
         *out_id = bi;
         if (kept_out) *kept_out = 1;
@@ -914,13 +849,9 @@ __global__ __launch_bounds__(1024) void cross_entropy_rows_kernel(const float* _
     return;
   }
   const float* row = logits + (size_t)r * ldl;
-  float mx = -INFINITY;
-  for (int i = threadIdx.x; i < V; i += 1024) mx = fmaxf(mx, row[i]);
-  mx = block_max_1024(mx, sh);
-  float z = 0.f;
-  for (int i = threadIdx.x; i < V; i += 1024) z += expf(row[i] - mx);
-  z = block_sum_1024(z, sh);
-  if (threadIdx.x == 0) nll[r] = fmaxf(logf(z) + mx - row[lab], 0.f);
+  float mx;
+  const float lse = row_lse_stream(row, V, threadIdx.x, sh, mx);
+  if (threadIdx.x == 0) nll[r] = fmaxf(lse - row[lab], 0.f);
 }
 __global__ __launch_bounds__(1024) void cross_entropy_mean_kernel(const float* __restrict__ nll, int rows, float* __restrict__ loss) {
   __shared__ float sh[16];
@@ -932,8 +863,8 @@ __global__ __launch_bounds__(1024) void cross_entropy_mean_kernel(const float* _
       c += 1.f;
     }
   }
-  s = block_sum_1024(s, sh);
-  c = block_sum_1024(c, sh);
+  s = row_block_sum(s, sh);
+  c = row_block_sum(c, sh);
   if (threadIdx.x == 0) loss[0] = s / c;                // no valid row: 0/0 = NaN, as torch's mean over nothing
 }
 

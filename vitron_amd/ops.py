@@ -710,20 +710,28 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = 
     return res if len(res) > 1 else out
 
 
+def _launch_rows(name: str, row_bytes: int, rows_dev: Optional[torch.Tensor], n_rows: int, V: int, none_ok: bool = False) -> None:
+    """The launch behind ban_rows, fsm_rows, cfg_rows, dola_rows and bias_rows: vt_<name>_rows over the device array of vt_<name>_row that
+    sampling.pack_<name>_rows builds. rows_dev reaches the library as NULL when n_rows <= 0, or (none_ok: the cfg / dola rule) exactly
+    when it is None, so that the library states what is wrong with the call."""
+    lib = _lib.load_any()
+    n_rows = int(n_rows)
+    given = rows_dev is not None if none_ok else n_rows > 0
+    if given and n_rows > 0:
+        _chk(rows_dev, torch.uint8, f"{name}_rows.rows_dev")
+        if rows_dev.numel() != n_rows * row_bytes:
+            raise _lib.VitronHipError(f"{name}_rows.rows_dev: expected {n_rows} x {row_bytes} bytes (sampling.pack_{name}_rows), got "
+                                      f"{rows_dev.numel()}")
+    _lib.check(getattr(lib, f"vt_{name}_rows")(_p(rows_dev) if given else None, n_rows, int(V), _stream()), f"vt_{name}_rows", lib)
+
+
 def ban_rows(rows_dev: torch.Tensor, n_rows: int, V: int) -> None:
     """Build the allow masks of n_rows rows on the device from their histories (n-gram and word-sequence bans); see vt_ban_rows in
     include/vitron_hip.h. rows_dev: the device array of vt_ban_row that sampling.pack_ban_rows builds (contiguous uint8, n_rows x 48
     bytes). Every pointer inside it is dereferenced on the device as it is: the caller keeps the buffers alive until the launch has
     run, sizes every `out` and `base` for ceil(V / 32) words, and lets no `out` alias a `base` or another `out`."""
     from .sampling import BAN_ROW_BYTES
-    lib = _lib.load_any()
-    n_rows = int(n_rows)
-    if n_rows > 0:
-        _chk(rows_dev, torch.uint8, "ban_rows.rows_dev")
-        if rows_dev.numel() != n_rows * BAN_ROW_BYTES:
-            raise _lib.VitronHipError(f"ban_rows.rows_dev: expected {n_rows} x {BAN_ROW_BYTES} bytes (sampling.pack_ban_rows), got "
-                                      f"{rows_dev.numel()}")
-    _lib.check(lib.vt_ban_rows(_p(rows_dev) if n_rows > 0 else None, n_rows, int(V), _stream()), "vt_ban_rows", lib)
+    _launch_rows("ban", BAN_ROW_BYTES, rows_dev, n_rows, V)
 
 
 def fsm_rows(rows_dev: torch.Tensor, n_rows: int, V: int) -> None:
@@ -733,14 +741,7 @@ def fsm_rows(rows_dev: torch.Tensor, n_rows: int, V: int) -> None:
     alive until the launch has run, sizes every `out` and `base` for ceil(V / 32) words, gives every row its own two-int cell and lets
     no `out` alias a `base` or another `out`."""
     from .sampling import FSM_ROW_BYTES
-    lib = _lib.load_any()
-    n_rows = int(n_rows)
-    if n_rows > 0:
-        _chk(rows_dev, torch.uint8, "fsm_rows.rows_dev")
-        if rows_dev.numel() != n_rows * FSM_ROW_BYTES:
-            raise _lib.VitronHipError(f"fsm_rows.rows_dev: expected {n_rows} x {FSM_ROW_BYTES} bytes (sampling.pack_fsm_rows), got "
-                                      f"{rows_dev.numel()}")
-    _lib.check(lib.vt_fsm_rows(_p(rows_dev) if n_rows > 0 else None, n_rows, int(V), _stream()), "vt_fsm_rows", lib)
+    _launch_rows("fsm", FSM_ROW_BYTES, rows_dev, n_rows, V)
 
 
 def cfg_rows(rows_dev: Optional[torch.Tensor], n_rows: int, V: int) -> None:
@@ -750,14 +751,7 @@ def cfg_rows(rows_dev: Optional[torch.Tensor], n_rows: int, V: int) -> None:
     dereferenced on the device as it is: the caller keeps the buffers alive until the launch has run, sizes `cond`, `uncond` and `out`
     for V floats and `base` / `mask_out` for ceil(V / 32) words; `out` may be `cond` itself and nothing else that the launch reads."""
     from .sampling import CFG_ROW_BYTES
-    lib = _lib.load_any()
-    n_rows = int(n_rows)
-    if rows_dev is not None and n_rows > 0:
-        _chk(rows_dev, torch.uint8, "cfg_rows.rows_dev")
-        if rows_dev.numel() != n_rows * CFG_ROW_BYTES:
-            raise _lib.VitronHipError(f"cfg_rows.rows_dev: expected {n_rows} x {CFG_ROW_BYTES} bytes (sampling.pack_cfg_rows), got "
-                                      f"{rows_dev.numel()}")
-    _lib.check(lib.vt_cfg_rows(_p(rows_dev) if rows_dev is not None else None, n_rows, int(V), _stream()), "vt_cfg_rows", lib)
+    _launch_rows("cfg", CFG_ROW_BYTES, rows_dev, n_rows, V, none_ok=True)
 
 
 def dola_rows(rows_dev: Optional[torch.Tensor], n_rows: int, V: int) -> None:
@@ -768,14 +762,7 @@ def dola_rows(rows_dev: Optional[torch.Tensor], n_rows: int, V: int) -> None:
     device as it is: the caller keeps the buffers alive until the launch has run; `out` may be `final` itself and nothing else that the
     launch reads."""
     from .sampling import DOLA_ROW_BYTES
-    lib = _lib.load_any()
-    n_rows = int(n_rows)
-    if rows_dev is not None and n_rows > 0:
-        _chk(rows_dev, torch.uint8, "dola_rows.rows_dev")
-        if rows_dev.numel() != n_rows * DOLA_ROW_BYTES:
-            raise _lib.VitronHipError(f"dola_rows.rows_dev: expected {n_rows} x {DOLA_ROW_BYTES} bytes (sampling.pack_dola_rows), got "
-                                      f"{rows_dev.numel()}")
-    _lib.check(lib.vt_dola_rows(_p(rows_dev) if rows_dev is not None else None, n_rows, int(V), _stream()), "vt_dola_rows", lib)
+    _launch_rows("dola", DOLA_ROW_BYTES, rows_dev, n_rows, V, none_ok=True)
 
 
 def bias_rows(rows_dev: torch.Tensor, n_rows: int, V: int) -> None:
@@ -784,14 +771,7 @@ def bias_rows(rows_dev: torch.Tensor, n_rows: int, V: int) -> None:
     (contiguous uint8, n_rows x 48 bytes). Every pointer inside it is dereferenced on the device as it is: the caller keeps the
     buffers alive until the launch has run, sizes every `out` for 2 * V floats and lets no `out` alias another."""
     from .sampling import BIAS_ROW_BYTES
-    lib = _lib.load_any()
-    n_rows = int(n_rows)
-    if n_rows > 0:
-        _chk(rows_dev, torch.uint8, "bias_rows.rows_dev")
-        if rows_dev.numel() != n_rows * BIAS_ROW_BYTES:
-            raise _lib.VitronHipError(f"bias_rows.rows_dev: expected {n_rows} x {BIAS_ROW_BYTES} bytes (sampling.pack_bias_rows), got "
-                                      f"{rows_dev.numel()}")
-    _lib.check(lib.vt_bias_rows(_p(rows_dev) if n_rows > 0 else None, n_rows, int(V), _stream()), "vt_bias_rows", lib)
+    _launch_rows("bias", BIAS_ROW_BYTES, rows_dev, n_rows, V)
 
 
 def beam_step(logits: torch.Tensor, beam_scores: torch.Tensor, groups: int, beams_in: int, n_out: int, packed: bool = False):

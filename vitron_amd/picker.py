@@ -428,6 +428,18 @@ def device_history(input_ids: torch.Tensor, room: int, attention_mask: Optional[
     return buf, lens
 
 
+def row_ptr(t: torch.Tensor, r: int) -> int:
+    """The device address of row r of a tensor of 4-byte elements."""
+    return t.data_ptr() + 4 * r * t.stride(0)
+
+
+def row_buffer(buf: torch.Tensor):
+    """(buf, the host list of its rows' addresses, the int64 device tensor of them) for a [B, ...] device buffer of 4-byte elements: what
+    a launch that writes one row per sample gets, and what the launch that reads the rows gets."""
+    ptr = [row_ptr(buf, b) for b in range(buf.shape[0])]
+    return buf, ptr, torch.tensor(ptr, dtype=torch.int64).to(buf.device)
+
+
 class _History:
     """A device_history that grows on the device: `append` writes one id per row behind what the row holds, with no host wait."""
 
@@ -436,7 +448,7 @@ class _History:
         self._pos = torch.tensor(self.lens, dtype=torch.long, device=self.buf.device).unsqueeze(1)
 
     def row_ptr(self, b: int) -> int:
-        return self.buf.data_ptr() + 4 * b * self.buf.stride(0)
+        return row_ptr(self.buf, b)
 
     def append(self, ids: torch.Tensor) -> None:
         self.buf.scatter_(1, self._pos, ids.unsqueeze(1))
@@ -515,53 +527,47 @@ class StepPicker:
         self.step_base = step_base
         cfg_ptr = None
         if a.guidance_plausibility > 0 or a.dola:   # the masks vt_cfg_rows / vt_dola_rows write stand where the static masks stood
-            self.cfg_work = cw = torch.empty((B, mask_words(self.V)), dtype=torch.int32, device=dev)
-            cfg_ptr = [cw.data_ptr() + 4 * b * cw.stride(0) for b in range(B)]
-            self.cfg_ptrs = torch.tensor(cfg_ptr, dtype=torch.int64).to(dev)
+            self.cfg_work, cfg_ptr, self.cfg_ptrs = row_buffer(torch.empty((B, mask_words(self.V)), dtype=torch.int32, device=dev))
         self.cfg_mask_ptr = cfg_ptr
         self.fsm_rows = None
         ban_base = step_base
         if a.automaton is not None:
-            self.fsm_work = fw = torch.empty((B, mask_words(self.V)), dtype=torch.int32, device=dev)
-            fsm_ptr = [fw.data_ptr() + 4 * b * fw.stride(0) for b in range(B)]
-            self.fsm_ptrs = torch.tensor(fsm_ptr, dtype=torch.int64).to(dev)
+            self.fsm_work, fsm_ptr, self.fsm_ptrs = row_buffer(torch.empty((B, mask_words(self.V)), dtype=torch.int32, device=dev))
             ban_base = None                      # the ban's base is the row's automaton mask, whatever the step
         self.ban_rows = None
         if a.ngram:
             self.ban_hist = h = _History(input_ids, steps, attention_mask)
             self.ban_work = w = torch.empty((B, mask_words(self.V)), dtype=torch.int32, device=dev)
-            work_ptr = [w.data_ptr() + 4 * b * w.stride(0) for b in range(B)]
-            self.ban_rows = pack_ban_rows([(h.row_ptr(b), h.lens[b] + st, fsm_ptr[b] if ban_base is None else (ban_base[st] if cfg_ptr is None else cfg_ptr[b]), work_ptr[b],
-                                            a.ngram, 0, 0, 0)
+            self.ban_rows = pack_ban_rows([(h.row_ptr(b), h.lens[b] + st, fsm_ptr[b] if ban_base is None else (ban_base[st] if cfg_ptr is None else cfg_ptr[b]),
+                                            row_ptr(w, b), a.ngram, 0, 0, 0)
                                            for st in range(steps) for b in range(B)], dev).view(steps, B, BAN_ROW_BYTES)
-            self.ban_ptrs = torch.tensor(work_ptr, dtype=torch.int64).to(dev)
+            self.ban_ptrs = row_buffer(w)[2]     # (uploaded behind the rows that name the same addresses)
         self.trunc = pack_trunc_rows([a.trunc] * B, dev) if a.truncated else None
         self.adj_ptrs = self.bias_rows = self.gen_hist = None
+        gen_ptr = None
+
+        def generated_ptrs():                    # where every row's GENERATED ids stand
+            if self.hist is not None:            # the tail of the penalty history
+                return [self.hist.row_ptr(b) + 4 * self.hist.lens[b] for b in range(B)]
+            if self.gen_hist is None:
+                self.gen_hist = _History(input_ids[:, :0], steps)
+            return [self.gen_hist.row_ptr(b) for b in range(B)]
+
         if a.adjusted and steps > 0:
-            self.adj = adj = torch.zeros((B, self.V, 2), dtype=torch.float32, device=dev)
-            adj_ptr = [adj.data_ptr() + 4 * b * adj.stride(0) for b in range(B)]
-            self.adj_ptrs = torch.tensor(adj_ptr, dtype=torch.int64).to(dev)
+            self.adj, adj_ptr, self.adj_ptrs = row_buffer(torch.zeros((B, self.V, 2), dtype=torch.float32, device=dev))
             self.bias_ids = torch.tensor([t for t, _ in a.bias], dtype=torch.int32).to(dev)
             self.bias_vals = torch.tensor([v for _, v in a.bias], dtype=torch.float32).to(dev)
             ids_ptr, vals_ptr = (self.bias_ids.data_ptr(), self.bias_vals.data_ptr()) if a.bias else (0, 0)
             if not a.count_penalties:            # the rows never change: one launch, here
                 ops.bias_rows(pack_bias_rows([(0, 0, ids_ptr, vals_ptr, len(a.bias), adj_ptr[b], 0.0, 0.0) for b in range(B)], dev), B, self.V)
             else:
-                if self.hist is not None:        # the generated ids are the tail of the penalty history
-                    gen_ptr = [self.hist.row_ptr(b) + 4 * self.hist.lens[b] for b in range(B)]
-                else:
-                    self.gen_hist = _History(input_ids[:, :0], steps)
-                    gen_ptr = [self.gen_hist.row_ptr(b) for b in range(B)]
+                gen_ptr = generated_ptrs()
                 self.bias_rows = pack_bias_rows(
                     [(gen_ptr[b] if st else 0, st, ids_ptr, vals_ptr, len(a.bias), adj_ptr[b], a.presence_penalty, a.frequency_penalty)
                      for st in range(steps) for b in range(B)], dev).view(steps, B, BIAS_ROW_BYTES)
         if a.automaton is not None:
-            if self.hist is not None:            # the generated ids are the tail of the penalty history
-                gen_ptr = [self.hist.row_ptr(b) + 4 * self.hist.lens[b] for b in range(B)]
-            else:
-                if self.gen_hist is None:
-                    self.gen_hist = _History(input_ids[:, :0], steps)
-                gen_ptr = [self.gen_hist.row_ptr(b) for b in range(B)]
+            if gen_ptr is None:
+                gen_ptr = generated_ptrs()
             self.fsm_cell = c = torch.tensor([[a.automaton.start, 0]] * B, dtype=torch.int32).to(dev)
             cell_ptr = [c.data_ptr() + 8 * b for b in range(B)]
             tables, eos = a.automaton.row_fields(dev), sorted(a.eos)
@@ -578,9 +584,6 @@ class StepPicker:
         if cond0.shape[1] != self.V or uncond0.shape[1] != self.V:
             raise RuntimeError(f"generate: guidance was set up for V = {self.V}, the logits have {cond0.shape[1]} columns")
         lb = log_beta(a.guidance_plausibility)
-
-        def row_ptr(t, r):
-            return t.data_ptr() + 4 * r * t.stride(0)
 
         rows = []
         for st in range(a.max_new_tokens):
@@ -603,9 +606,6 @@ class StepPicker:
         n_cand, steps = len(a.dola_layers), a.max_new_tokens
         lrt = math.log(a.dola_relative_top)
         self.dola_choice = ch = torch.zeros((steps, B), dtype=torch.int32, device=self.device)
-
-        def row_ptr(t, r):
-            return t.data_ptr() + 4 * r * t.stride(0)
 
         rows = []
         for st in range(steps):

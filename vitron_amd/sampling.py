@@ -499,6 +499,12 @@ def check_constraints(sampling: Optional[SamplingParams], eos: Iterable[int], V:
         step_allow_mask(sp.replace(choices=None), sp.min_new_tokens, [], eos, V, {})
 
 
+def _upload_rows(arr: np.ndarray, device):
+    """A host array of row structs as a uint8 device tensor [len(arr), bytes per struct]: the form every ops.*_rows launcher takes."""
+    import torch
+    return torch.from_numpy(arr.view(np.uint8).reshape(len(arr), arr.dtype.itemsize)).to(device)
+
+
 def sample_rows_array(rows: Sequence[tuple]) -> np.ndarray:
     """Host array of vt_sample_row from one tuple per row:
         (temperature, top_k, top_p, repetition_penalty, seed, counter, stream, history_ptr, history_len)
@@ -515,9 +521,7 @@ def sample_rows_array(rows: Sequence[tuple]) -> np.ndarray:
 
 def pack_sample_rows(rows: Sequence[tuple], device):
     """Device form of `sample_rows_array(rows)`: a uint8 tensor [len(rows), 48] for ops.sample_rows."""
-    import torch
-    arr = sample_rows_array(rows)
-    return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), ROW_BYTES)).to(device)
+    return _upload_rows(sample_rows_array(rows), device)
 
 
 # ---- truncation: struct vt_trunc_row ---------------------------------------------------------------------------------------------------
@@ -536,9 +540,7 @@ def trunc_rows_array(rows: Sequence[Optional[tuple]]) -> np.ndarray:
 
 def pack_trunc_rows(rows: Sequence[Optional[tuple]], device):
     """Device form of `trunc_rows_array(rows)`: a uint8 tensor [len(rows), 16] for ops.sample_rows(..., trunc=)."""
-    import torch
-    arr = trunc_rows_array(rows)
-    return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), TRUNC_ROW_BYTES)).to(device)
+    return _upload_rows(trunc_rows_array(rows), device)
 
 
 # ---- history-dependent bans: struct vt_ban_row and the host statement of vt_ban_rows' contract --------------------------------------
@@ -592,9 +594,7 @@ def ban_rows_array(rows: Sequence[tuple]) -> np.ndarray:
 
 def pack_ban_rows(rows: Sequence[tuple], device):
     """Device form of `ban_rows_array(rows)`: a uint8 tensor [len(rows), 48] for ops.ban_rows."""
-    import torch
-    arr = ban_rows_array(rows)
-    return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), BAN_ROW_BYTES)).to(device)
+    return _upload_rows(ban_rows_array(rows), device)
 
 
 # ---- token automata: struct vt_fsm_row (the host statement of the contract is vitron_amd.automaton.TokenAutomaton) ---------------------
@@ -619,9 +619,7 @@ def fsm_rows_array(rows: Sequence[tuple]) -> np.ndarray:
 
 def pack_fsm_rows(rows: Sequence[tuple], device):
     """Device form of `fsm_rows_array(rows)`: a uint8 tensor [len(rows), 96] for ops.fsm_rows."""
-    import torch
-    arr = fsm_rows_array(rows)
-    return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), FSM_ROW_BYTES)).to(device)
+    return _upload_rows(fsm_rows_array(rows), device)
 
 
 # ---- classifier-free guidance: struct vt_cfg_row (the host statement of the contract is tests/cfg_ref.py) -----------------------------
@@ -650,9 +648,7 @@ def cfg_rows_array(rows: Sequence[tuple]) -> np.ndarray:
 
 def pack_cfg_rows(rows: Sequence[tuple], device):
     """Device form of `cfg_rows_array(rows)`: a uint8 tensor [len(rows), 56] for ops.cfg_rows."""
-    import torch
-    arr = cfg_rows_array(rows)
-    return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), CFG_ROW_BYTES)).to(device)
+    return _upload_rows(cfg_rows_array(rows), device)
 
 
 # ---- DoLa: struct vt_dola_row (the host statement of the contract is tests/dola_ref.py) ------------------------------------------------
@@ -719,9 +715,7 @@ def dola_rows_array(rows: Sequence[tuple]) -> np.ndarray:
 
 def pack_dola_rows(rows: Sequence[tuple], device):
     """Device form of `dola_rows_array(rows)`: a uint8 tensor [len(rows), 80] for ops.dola_rows."""
-    import torch
-    arr = dola_rows_array(rows)
-    return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), DOLA_ROW_BYTES)).to(device)
+    return _upload_rows(dola_rows_array(rows), device)
 
 
 # ---- additive adjustments: struct vt_bias_row and the host statement of vt_bias_rows' contract --------------------------------------
@@ -831,6 +825,4 @@ def bias_rows_array(rows: Sequence[tuple]) -> np.ndarray:
 
 def pack_bias_rows(rows: Sequence[tuple], device):
     """Device form of `bias_rows_array(rows)`: a uint8 tensor [len(rows), 48] for ops.bias_rows."""
-    import torch
-    arr = bias_rows_array(rows)
-    return torch.from_numpy(arr.view(np.uint8).reshape(len(rows), BIAS_ROW_BYTES)).to(device)
+    return _upload_rows(bias_rows_array(rows), device)
