@@ -109,6 +109,8 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
 /* 114 also carries vt_dola_rows and struct vt_dola_row WITHOUT a bump: one new symbol and one new struct; and two fields appended to the
  * END of struct vt_llama_model (logit_row_trace, logit_row_trace_layers), as hidden_trace was: a caller that zero-initialises the struct
  * gets the launches it got. */
+/* 114 also carries vt_gemm_plan_query3 and vt_gemm_bf16_colsplit WITHOUT a bump: two new symbols, no struct and no existing signature
+ * changes; vt_gemm_plan_query and vt_gemm_plan_query2 return what they returned, and vt_gemm_bf16 stores what it stored, bit for bit. */
 #define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
@@ -139,6 +141,19 @@ int vt_gemm_plan_query(int M, int N, int K, int epi, int* cfg, int* rows_first);
 /* the same with the column split of round 5: *cols_first > 0 means columns [0, *cols_first) run on *cfg (whole rounds of 256-row tiles) and the
  * remaining columns are planned again (a few row blocks x many column tiles that spill just over whole rounds: 768 x 22016) */
 int vt_gemm_plan_query2(int M, int N, int K, int epi, int* cfg, int* rows_first, int* cols_first);
+/* the plan the dispatcher RUNS, with the mixed-height column split: *cols_first > 0 means columns [0, *cols_first) run on *cfg -- any of the
+ * 256-, 320- or 224-row four-wave configurations, whole rounds of it -- and the remaining columns on *cfg_rest (the first configuration of
+ * their own plan). *cfg_rest = VT_GEMM_CFG_AUTO without a column split. vt_gemm_plan_query and _query2 keep reporting the plan without that
+ * split, whose first launch is always on 256-row tiles: on the shapes where it applies (gate/up at 5120, 2560 and 768 rows) they name the
+ * plan that ran before, this query names the two launches that run now. */
+int vt_gemm_plan_query3(int M, int N, int K, int epi, int* cfg, int* rows_first, int* cols_first, int* cfg_rest);
+
+/* vt_gemm_bf16 (row_scale = NULL) as two launches over column ranges, whatever the planner would do: columns [0, cols_first) on cfg_first,
+ * columns [cols_first, N) on cfg_rest (VT_GEMM_CFG_AUTO: planned as a GEMM of their own). cols_first: a multiple of 256 inside (0, N); each
+ * range must be legal for its configuration (the four-wave tiles: K % 128 == 0, K >= 256, N % 32 == 0). The result is the single launch's
+ * bit for bit. The dispatcher's own column splits run through the same code; exported for tests and tools. */
+int vt_gemm_bf16_colsplit(const uint16_t* A, int lda, const uint16_t* W, int ldw, void* C, int ldc, const float* bias, int M, int N, int K,
+                          int epi, int cfg_first, int cols_first, int cfg_rest, void* stream);
 
 /* y_bf16[rows][D] = LayerNorm(x_f32) * gamma + beta. If temb != NULL first x[row] += temb[(row / tokens_per_frame) % T]
  * (written back): the video tower's temporal_embedding add (reference modeling_video.py:110-114) fused with

@@ -97,6 +97,8 @@ SIGNATURES = {
     "vt_attn_decode": (_i, [vp, _i, vp, vp, vp, vp, _i, vp, _i, _i, _i, _f, _i, vp, _sz, vp]),
     "vt_gemm_plan_query": (_i, [_i, _i, _i, _i, vp, vp]),
     "vt_gemm_plan_query2": (_i, [_i, _i, _i, _i, vp, vp, vp]),
+    "vt_gemm_plan_query3": (_i, [_i, _i, _i, _i, vp, vp, vp, vp]),
+    "vt_gemm_bf16_colsplit": (_i, [vp, _i, vp, _i, vp, _i, vp, _i, _i, _i, _i, _i, _i, _i, vp]),
     "vt_gemm_bf16_resid_splitk": (_i, [vp, _i, vp, _i, vp, _i, vp, _i, _i, _i, _i, vp, _sz, vp]),
     "vt_gemm_bf16_norm": (_i, [vp, _i, vp, _i, vp, _i, _i, _i, _i, _i, vp, _i, _f, _f, vp, vp, _i, vp, vp]),
     "vt_gemm_bf16_resid_norm": (_i, [vp, _i, vp, _i, vp, _i, vp, _i, _i, _i, _i, _i, vp, _sz, vp, vp, _i, vp, _i, _i, vp]),

@@ -220,6 +220,15 @@ int vt_gemm_plan_query(int M, int N, int K, int epi, int* cfg, int* rows_first) 
 int vt_gemm_plan_query2(int M, int N, int K, int epi, int* cfg, int* rows_first, int* cols_first) {
   return vt_gemm_plan_describe(M, N, K, epi, cfg, rows_first, cols_first);
 }
+int vt_gemm_plan_query3(int M, int N, int K, int epi, int* cfg, int* rows_first, int* cols_first, int* cfg_rest) {
+  VT_REQUIRE(cols_first && cfg_rest, "vt_gemm_plan_query3: bad arguments");
+  return vt_gemm_plan_describe(M, N, K, epi, cfg, rows_first, cols_first, cfg_rest);
+}
+
+int vt_gemm_bf16_colsplit(const uint16_t* A, int lda, const uint16_t* W, int ldw, void* C, int ldc, const float* bias, int M, int N, int K,
+                          int epi, int cfg_first, int cols_first, int cfg_rest, void* stream) {
+  return vt_gemm_colsplit_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, epi, cfg_first, cols_first, cfg_rest, S(stream));
+}
 
 int vt_layernorm(float* x, const float* temb, int T, int tokens_per_frame, const float* gamma, const float* beta,
                  uint16_t* y, int rows, int D, float eps, void* stream) {

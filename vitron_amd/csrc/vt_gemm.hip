@@ -748,7 +748,9 @@ int vt_gemm_pick_cfg(int M, int N, int K) {
 //   320-row tiles   ceil(tiles320 / 256) x 1.25 x 1.04      four-wave kernel, 160x128 per wave: 5120 x 4096 is ONE round of 256 tiles
 //                                                            instead of 1.25 (o_proj 1245 vs 1075 TFLOP/s for whole rounds + small-tile
 //                                                            remainder, down_proj 1341 vs 1173, projector 4608x4096x4096 1329 vs 1131);
-//                                                            on multi-round grids the tile itself is ~4 % slower (qkv 1420 vs 1405)
+//                                                            the x 1.04 is round 2's qkv A/B (1420 vs 1405); re-measured, a round costs
+//                                                            1.21-1.25 rounds of 256-row tiles (VT_PRICE_320_ROUND below), but the single-grid
+//                                                            price stays: see there
 //   small tiles     ceil(tiles64x128 / 512) x 0.4545        two workgroups per CU at ~0.55 of the big tiles' rate (remainders of 512 /
 //                                                            1024 rows x 4096: 0.40 / 0.39 of a big round measured; 2560 x 4096 x 4096: 827
 //                                                            TFLOP/s on small tiles vs 1005 on 160 big tiles)
@@ -758,11 +760,14 @@ int vt_gemm_pick_cfg(int M, int N, int K) {
 //                                                            round of them costs 0.41 of a big round (4616 x 1024 x 4096: 41 us, 935 TFLOP/s
 //                                                            against 692 on 64x128 tiles; 1088 x 4096 x 4096: 906 vs 637)
 //   M-split         whole rounds of 256-row tiles + the plan of the remaining rows (only with a long K loop)
+//   column split    whole rounds of 256-row tiles + the plan of a tail of at most 2048 columns (round 5), or whole rounds of ANY of the three
+//                   four-wave heights + the single grid of the remaining columns (mixed heights: measured shapes only, see below)
 // and takes the cheapest. VtGemmPlan.M1 > 0: rows [0, M1) go to cfg, the rest is planned again by the caller.
 struct VtGemmPlan {
   int cfg;
   int M1;
   int N1 = 0;   // > 0: COLUMNS [0, N1) go to cfg (whole rounds of big tiles), the remaining columns are planned again (round 5)
+  int cfg_rest = VT_GEMM_CFG_AUTO;   // N1 > 0: the configuration of the remaining columns (AUTO: planned again at the launch)
 };
 
 static bool vt_epi_plain(int epi) { return epi == VT_EPI_BF16 || epi == VT_EPI_F32_RESID || epi == VT_EPI_F32 || epi == VT_EPI_SWIGLU_BF16; }
@@ -771,7 +776,40 @@ static int vt_gemm_256_variant(int epi, const VtGemmNormFuse* nf) {
   return (vt_epi_plain(epi) && !nf) ? VT_GEMM_CFG_256x256_W4 : VT_GEMM_CFG_256x256_P4;
 }
 
-static double vt_gemm_plan_cost(int M, int N, int K, int epi, const VtGemmNormFuse* nf, VtGemmPlan* plan, bool allow_split) {
+// Round prices of the four-wave tiles against a round of 256-row tiles, re-measured on whole three-round grids (16 row blocks x 48 column
+// tiles, cold weights, tools/cfg_ab.py; profiles/colsplit_round_prices.jsonl), us per round at K = 4096 / 11008:
+//              bf16 store        SwiGLU            fp32 residual
+//   256 rows   103.7 / 261.8     95.4 / 258.9      114.5 / 278.6
+//   320 rows   125.0 / 320.9    117.2 / 318.3      143.1 / 341.5     x 1.205 .. 1.249 (mean 1.227): at or BELOW the 1.25 of its height
+//   224 rows    92.5 / 232.7     85.1 / 229.2      101.4 / 248.0     x 0.885 .. 0.892 (mean 0.889)
+// The 224-row price (0.875 x 1.02 = 0.8925, profiles/r3_gemm_tile224_ab.jsonl) holds. The 320-row round is cheaper than the 1.25 x 1.04 = 1.30
+// the single-grid candidate carries (round 2, before the LDS-staged store epilogue, the tile groups of 4 and the round-by-round walk): the
+// mixed-height split below prices it at the measured 1.23. The SINGLE-GRID price stays at 1.30: at 1.23 the only shapes of the benchmark's
+// configurations that change are the seven decoder GEMMs at 40960 rows (C4's packed batch: 30 rounds of 256-row tiles against 24 x 1.23 =
+// 29.5), and the A/B of those (profiles/colsplit_gemm_ab.jsonl, old / new / old) has the 320-row grid below both old arms in every round on
+// four (bf16 qkv 2800 -> 2750 us, o_proj 1098 -> 1085, SwiGLU gate/up 5180 -> 5023, down_proj 2697 -> 2676) and NOT on three (k|v 1880 ->
+// 1859 with rounds inside the noise; the fp32 stores of the precise modes SLOWER: qkv 2944 -> 2987, gate/up 5574 -> 5829) -- a 1.6 % model
+// margin is not a measured win, so the 0.07 stays as hysteresis and those plans stay.
+static constexpr double VT_PRICE_320 = 1.25 * 1.04;
+static constexpr double VT_PRICE_320_ROUND = 1.23;
+static constexpr double VT_PRICE_224 = 0.875 * 1.02;
+
+// The (M, N, K, epilogue) on which the mixed-height column split was measured against the plan it replaces -- old plan / split / old plan for
+// seven rounds on cold weights, both launches inside the timed window -- and came out below BOTH old arms in EVERY round (tools/colsplit_ab.py,
+// profiles/colsplit_gemm_ab.jsonl, profiles/colsplit_plans.json; DESIGN.md 3, "Mixed-height column split"), us per call:
+//   5120 x 22016 x 4096 SwiGLU   646.1 on 1720 tiles of 256 rows       -> 635.5 as 48 column tiles x 320 rows + 38 x 256 rows
+//   2560 x 22016 x 4096 SwiGLU   348.0 on 688 tiles of 320 rows        -> 333.1 as 64 column tiles x 320 rows + 22 x 256 rows
+//    768 x 22016 x 4096 SwiGLU   139.7 as 85 x 256 rows + ring tail    -> 131.5 as 64 column tiles x 224 rows + 22 on the 160x128 ring
+//    768 x 22016 x 4096 fp32     147.5                                 -> 137.9 (the same two plans)
+// Everything else the model would switch among the shapes of C2, C2-224, C3, C3-224, C4 and the towers was measured too and stays: the fp32
+// store at 5120 rows (729 -> 692) and at 2560 rows (379 -> 370) was faster on the median but not below both old arms in every round.
+static bool vt_gemm_mixed_split_measured(int M, int N, int K, int epi) {
+  if (N != 22016 || K != 4096) return false;
+  if (M == 5120 || M == 2560) return epi == VT_EPI_SWIGLU_BF16;            // gate/up of C3 at 336 px and at 224 px
+  return M == 768 && (epi == VT_EPI_SWIGLU_BF16 || epi == VT_EPI_F32);     // gate/up of C2 at 224 px, standard and precise modes
+}
+
+static double vt_gemm_plan_cost(int M, int N, int K, int epi, const VtGemmNormFuse* nf, VtGemmPlan* plan, bool allow_split, bool allow_mixed) {
   // 64x128 tiles: two workgroups per CU = 512 slots; a round of them moves 512 x 64 x 128 outputs at ~0.55 of the big tiles' rate
   const double small = (double)(((long)cdiv(M, 64) * cdiv(N, 128) + 511) / 512) * (512.0 * 64 * 128 / 65536.0 / 256.0 / 0.55);
   double best = small;
@@ -785,7 +823,7 @@ static double vt_gemm_plan_cost(int M, int N, int K, int epi, const VtGemmNormFu
     *plan = VtGemmPlan{vt_gemm_256_variant(epi, nf), 0};
   }
   if (!nf) {
-    const double c320 = (double)((cdiv(M, 320) * (long)tiles_n + 255) / 256) * 1.25 * 1.04;
+    const double c320 = (double)((cdiv(M, 320) * (long)tiles_n + 255) / 256) * VT_PRICE_320;
     if (c320 < best) {
       best = c320;
       *plan = VtGemmPlan{VT_GEMM_CFG_320x256_W4, 0};
@@ -793,7 +831,7 @@ static double vt_gemm_plan_cost(int M, int N, int K, int epi, const VtGemmNormFu
     // 224-row tiles (112x128 per wave): a round of them costs 7/8 of a 256-row round; wins where 256-row tiles pad the last tile row
     // heavily and the tile COUNT stays inside the same number of rounds (1088 rows: 5 tile rows either way; 4616 x 3072: 252 vs 228 tiles)
     const long t224 = cdiv(M, 224) * (long)tiles_n;
-    const double c224 = (double)((t224 + 255) / 256) * 0.875 * 1.02;
+    const double c224 = (double)((t224 + 255) / 256) * VT_PRICE_224;
     // Only where it PADS FEWER ROWS than the 256-row tile (1088 -> 1120 vs 1280; 4616 -> 4704 vs 4864): the 0.875 x 1.02 price was
     // measured on exactly those shapes (profiles/r3_gemm_tile224_ab.jsonl). A multiple of 256 (2048 rows: 160 tiles instead of 128,
     // 9 % padding) would otherwise switch kernels on an extrapolated model -- unmeasured shapes stay on the 256-row tile.
@@ -841,7 +879,7 @@ static double vt_gemm_plan_cost(int M, int N, int K, int epi, const VtGemmNormFu
     const long M1 = (M / unit) * unit;
     if (M1 >= unit && M1 < M) {
       VtGemmPlan rest;
-      const double c = (double)(M1 / 256 * tiles_n / 256) + vt_gemm_plan_cost(M - (int)M1, N, K, epi, nf, &rest, false) + 0.02;   // + a launch
+      const double c = (double)(M1 / 256 * tiles_n / 256) + vt_gemm_plan_cost(M - (int)M1, N, K, epi, nf, &rest, false, false) + 0.02;   // + a launch
       if (c < best) {
         best = c;
         *plan = VtGemmPlan{vt_gemm_256_variant(epi, nf), (int)M1};
@@ -859,7 +897,7 @@ static double vt_gemm_plan_cost(int M, int N, int K, int epi, const VtGemmNormFu
       const long N1 = n1_tiles * 256;
       if (n1_tiles >= 1 && N1 < N && N - N1 <= 2048) {       // only a SMALL tail is worth a second launch
         VtGemmPlan rest;
-        const double c = (double)whole + vt_gemm_plan_cost(M, N - (int)N1, K, epi, nf, &rest, false) + 0.02;
+        const double c = (double)whole + vt_gemm_plan_cost(M, N - (int)N1, K, epi, nf, &rest, false, false) + 0.02;
         if (c < best - 0.05) {
           best = c;
           *plan = VtGemmPlan{VT_GEMM_CFG_256x256_W4, 0, (int)N1};
@@ -867,27 +905,69 @@ static double vt_gemm_plan_cost(int M, int N, int K, int epi, const VtGemmNormFu
       }
     }
   }
+  // Mixed-height column split: the first launch may run on ANY of the three four-wave tile heights, so that its columns fill whole rounds
+  // where no single height does -- gate/up at 5120 rows: 20 x 86 = 1720 tiles of 256 rows are 6.72 rounds and cost 7; 48 column tiles on 16 row
+  // blocks of 320 rows are exactly 3 rounds, and the other 38 column tiles on 20 row blocks of 256 rows are 760 tiles = 2.97 rounds. The
+  // remaining columns are priced, and launched, on the single grid the planner picks for them (no further split). Every output element is
+  // the same bit for bit: tile height changes neither the K order nor the epilogue. Like the 224-row tile above, a shape changes plans only
+  // where the split was MEASURED against the plan it replaces (vt_gemm_mixed_split_measured): the model proposes, the table disposes.
+  if (allow_split && allow_mixed && !nf && K >= 2048 && vt_epi_plain(epi) && vt_gemm_mixed_split_measured(M, N, K, epi)) {
+    static const struct { int rows, cfg; double price; } heights[] = {
+        {320, VT_GEMM_CFG_320x256_W4, VT_PRICE_320_ROUND}, {256, VT_GEMM_CFG_256x256_W4, 1.0}, {224, VT_GEMM_CFG_224x256_W4, VT_PRICE_224}};
+    double cm = best;
+    VtGemmPlan pm = *plan;
+    for (const auto& h : heights) {
+      const long rb = cdiv(M, h.rows);
+      if (rb > 256) continue;
+      int g = (int)rb, b = 256;
+      while (b) {   // gcd(rb, 256)
+        const int t = g % b;
+        g = b;
+        b = t;
+      }
+      const long step = 256 / g;   // column tiles per whole number of rounds
+      for (long n1_tiles = step; n1_tiles < tiles_n; n1_tiles += step) {
+        const long N1 = n1_tiles * 256;
+        VtGemmPlan rest;
+        const double c = (double)(rb * n1_tiles / 256) * h.price + vt_gemm_plan_cost(M, N - (int)N1, K, epi, nf, &rest, false, false) + 0.02;
+        if (c < cm) {
+          cm = c;
+          pm = VtGemmPlan{h.cfg, 0, (int)N1, rest.cfg};
+        }
+      }
+    }
+    if (cm < best - 0.05) {
+      best = cm;
+      *plan = pm;
+    }
+  }
   return best;
 }
 
-static VtGemmPlan vt_gemm_plan(int M, int N, int K, int epi, const VtGemmNormFuse* nf) {
+static VtGemmPlan vt_gemm_plan(int M, int N, int K, int epi, const VtGemmNormFuse* nf, bool allow_mixed = true) {
   VtGemmPlan plan;
-  vt_gemm_plan_cost(M, N, K, epi, nf, &plan, true);
+  vt_gemm_plan_cost(M, N, K, epi, nf, &plan, true, allow_mixed);
   return plan;
 }
 
-int vt_gemm_plan_describe(int M, int N, int K, int epi, int* cfg, int* rows_first, int* cols_first) {
+// vt_gemm_plan_query / _query2 (cfg_rest == nullptr) report the plan WITHOUT the mixed-height column split: their three outputs cannot name a
+// second configuration, and a caller that reads cols_first as "whole rounds of 256-row tiles" keeps reading the truth. vt_gemm_plan_query3
+// reports the plan the dispatcher runs.
+int vt_gemm_plan_describe(int M, int N, int K, int epi, int* cfg, int* rows_first, int* cols_first, int* cfg_rest) {
   VT_REQUIRE(M > 0 && N > 0 && K > 0 && cfg && rows_first, "vt_gemm_plan_query: bad arguments");
   if (cols_first) *cols_first = 0;
+  if (cfg_rest) *cfg_rest = VT_GEMM_CFG_AUTO;
   if (M <= 64 || (K % 64) != 0) {   // the weight-streaming kernels / the ragged-K fallback, not a tile configuration
     *cfg = VT_GEMM_CFG_SKINNY;
     *rows_first = 0;
     return VT_OK;
   }
-  const VtGemmPlan plan = vt_gemm_plan(M, N, K, epi, nullptr);
+  const VtGemmPlan plan = vt_gemm_plan(M, N, K, epi, nullptr, cfg_rest != nullptr);
   *cfg = plan.cfg;
   *rows_first = plan.M1;
   if (cols_first) *cols_first = plan.N1;
+  if (cfg_rest && plan.N1 > 0)   // (the same-height split plans its tail again at the launch: report that plan's first configuration)
+    *cfg_rest = plan.cfg_rest != VT_GEMM_CFG_AUTO ? plan.cfg_rest : vt_gemm_plan(M, N - plan.N1, K, epi, nullptr).cfg;
   return VT_OK;
 }
 
@@ -942,12 +1022,8 @@ int vt_gemm_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, 
       // remaining rows again (small tiles fill the CUs at any size). Both launches are plain row ranges of the same GEMM.
       const VtGemmPlan plan = vt_gemm_plan(M, N, K, epi, nf);
       cfg = plan.cfg;
-      if (plan.N1 > 0) {   // column split: whole rounds of big tiles over the first N1 columns, the tail columns planned again
-        const size_t c_off = (epi == VT_EPI_SWIGLU_BF16 ? plan.N1 / 2 : plan.N1) * esz;     // SwiGLU: one output column per gate/up pair
-        VT_TRY(vt_gemm_launch(A, lda, W, ldw, C, ldc, bias, M, plan.N1, K, epi, plan.cfg, s, nullptr));
-        return vt_gemm_launch(A, lda, W + (size_t)plan.N1 * ldw, ldw, (char*)C + c_off, ldc, bias ? bias + plan.N1 : nullptr, M, N - plan.N1, K,
-                              epi, VT_GEMM_CFG_AUTO, s, nullptr);
-      }
+      if (plan.N1 > 0)   // column split: whole rounds of big tiles over the first N1 columns, the remaining columns on their own plan
+        return vt_gemm_colsplit_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, epi, plan.cfg, plan.N1, plan.cfg_rest, s);
       if (plan.M1 > 0) {
         VT_TRY(vt_gemm_launch(A, lda, W, ldw, C, ldc, bias, plan.M1, N, K, epi, plan.cfg, s, nf));
         const VtGemmNormFuse rest = nf ? vt_nf_rows(*nf, plan.M1) : VtGemmNormFuse{};
@@ -980,6 +1056,22 @@ int vt_gemm_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, 
   if (cfg >= 301 && cfg <= 303) return vt_gemm_rp_launch(A, lda, W, ldw, C, ldc, bias, M, N, K, VT_EPI_BF16, s, cfg - 300);
 #endif
   return vt_with_epi<VtEpisPublic>(epi, "vt_gemm", [&](auto e) { return launch_cfg<decltype(e)::value>(p, cfg, s); });
+}
+
+// One GEMM as two launches over column ranges: columns [0, N1) on cfg_first, the remaining columns on cfg_rest (AUTO: planned as a GEMM of their
+// own). Both are plain column ranges of the same problem -- W rows from N1 on, the bias from N1 on, C from output column N1 on (SwiGLU: N1 / 2,
+// one output column per gate/up pair) with the same ldc -- so every element is what the single launch stores. The planner's column splits
+// run through here; vt_gemm_bf16_colsplit forces one at any shape.
+int vt_gemm_colsplit_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, int ldc, const float* bias, int M, int N, int K,
+                            int epi, int cfg_first, int N1, int cfg_rest, hipStream_t s) {
+  VT_REQUIRE(A && W && C, "vt_gemm(colsplit): null pointer");
+  VT_REQUIRE(N1 > 0 && N1 < N && (N1 % 256) == 0, "vt_gemm(colsplit): N1=%d must be a multiple of 256 inside (0, N=%d)", N1, N);
+  VT_REQUIRE(VtEpisPublic::has(epi), "vt_gemm(colsplit): unknown epilogue %d", epi);
+  const size_t esz = (epi == VT_EPI_F32 || epi == VT_EPI_F32_RESID) ? 4 : 2;   // bytes per element of C
+  const size_t c_off = (size_t)(epi == VT_EPI_SWIGLU_BF16 ? N1 / 2 : N1) * esz;
+  VT_TRY(vt_gemm_launch(A, lda, W, ldw, C, ldc, bias, M, N1, K, epi, cfg_first, s, nullptr));
+  return vt_gemm_launch(A, lda, W + (size_t)N1 * ldw, ldw, (char*)C + c_off, ldc, bias ? bias + N1 : nullptr, M, N - N1, K, epi, cfg_rest, s,
+                        nullptr);
 }
 
 int vt_gemm_skinny_norm_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, int ldc, int M, int N, int K, int epi,

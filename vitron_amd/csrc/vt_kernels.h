@@ -15,11 +15,15 @@ struct VtAttnSeq {  // device-side view of one row of seq_desc (int32 x 4)
 
 // ---- vt_gemm.hip ----------------------------------------------------------------------------------
 int vt_gemm_pick_cfg(int M, int N, int K);
-int vt_gemm_plan_describe(int M, int N, int K, int epi, int* cfg, int* rows_first, int* cols_first = nullptr);   // vt_gemm.hip: the planner's verdict, no launch
+int vt_gemm_plan_describe(int M, int N, int K, int epi, int* cfg, int* rows_first, int* cols_first = nullptr,
+                          int* cfg_rest = nullptr);   // vt_gemm.hip: the planner's verdict, no launch (cfg_rest: with the mixed-height column split)
 struct VtGemmNormFuse;
 int vt_gemm_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, int ldc, const float* bias,
                    int M, int N, int K, int epi, int cfg, hipStream_t s,
                    const VtGemmNormFuse* nf = nullptr);
+// columns [0, N1) on cfg_first, the remaining columns on cfg_rest (VT_GEMM_CFG_AUTO: planned again): the planner's column splits, and a forced one
+int vt_gemm_colsplit_launch(const bf16_t* A, int lda, const bf16_t* W, int ldw, void* C, int ldc, const float* bias, int M, int N, int K,
+                            int epi, int cfg_first, int N1, int cfg_rest, hipStream_t s);
 // RMSNorm folded into the M <= 16 weight-streaming GEMMs of a decode step (no separate norm launches):
 //   producer side (VT_EPI_F32_RESID): after x += A W^T the epilogue also stores out_xw = bf16(x * out_w[n]) and, per row and
 //   16-column block, the partial sum of x^2 (out_partials[m][N/16]);

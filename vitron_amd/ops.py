@@ -73,9 +73,22 @@ def gemm_plan_cols(M: int, N: int, K: int, epi: int = EPI_BF16):
     return cfg.value, rows.value, cols.value
 
 
+def gemm_plan_split(M: int, N: int, K: int, epi: int = EPI_BF16):
+    """(cfg, rows_first, cols_first, cfg_rest) of the plan the dispatcher runs (vt_gemm_plan_query3): cols_first > 0 = columns [0, cols_first)
+    on cfg -- whole rounds of 256-, 320- or 224-row tiles -- and the remaining columns on cfg_rest."""
+    import ctypes
+    lib = _lib.load_any()
+    cfg, rows, cols, rest = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(lib.vt_gemm_plan_query3(M, N, K, epi, ctypes.byref(cfg), ctypes.byref(rows), ctypes.byref(cols), ctypes.byref(rest)),
+               "vt_gemm_plan_query3", lib)
+    return cfg.value, rows.value, cols.value, rest.value
+
+
 def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, epi: int = EPI_BF16,
-         out: Optional[torch.Tensor] = None, cfg: int = CFG_AUTO, row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """out = epi(row_scale[:, None] * (a[M,K] @ w[N,K]^T) + bias). EPI_F32_RESID accumulates into `out` (fp32, required)."""
+         out: Optional[torch.Tensor] = None, cfg: int = CFG_AUTO, row_scale: Optional[torch.Tensor] = None,
+         colsplit: Optional[tuple] = None) -> torch.Tensor:
+    """out = epi(row_scale[:, None] * (a[M,K] @ w[N,K]^T) + bias). EPI_F32_RESID accumulates into `out` (fp32, required).
+    colsplit = (cols_first, cfg_rest): forced column split (vt_gemm_bf16_colsplit) -- columns [0, cols_first) on `cfg`, the rest on cfg_rest."""
     lib, dt = _op16(a, "gemm.a")
     _chk_view(a, dt, "gemm.a")
     _chk_view(w, dt, "gemm.w")
@@ -98,6 +111,13 @@ def gemm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, 
         _chk(row_scale, torch.float32, "gemm.row_scale")
         if row_scale.numel() != M:
             raise _lib.VitronHipError(f"gemm: row_scale has {row_scale.numel()} elements for M={M}")
+    if colsplit is not None:
+        if row_scale is not None:
+            raise _lib.VitronHipError("gemm: a forced column split takes no row_scale")
+        n1, cfg_rest = colsplit
+        _lib.check(lib.vt_gemm_bf16_colsplit(_p(a), a.stride(0), _p(w), w.stride(0), _p(out), out.stride(0), _p(bias), M, N, K, epi,
+                                             cfg, int(n1), int(cfg_rest), _stream()), "vt_gemm_bf16_colsplit", lib)
+        return out
     _lib.check(lib.vt_gemm_bf16(_p(a), a.stride(0), _p(w), w.stride(0), _p(out), out.stride(0), _p(bias), M, N, K, epi,
                                 cfg, _p(row_scale), _stream()), "vt_gemm_bf16", lib)
     return out
