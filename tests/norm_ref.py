@@ -80,6 +80,19 @@ def ln_bound(x, g, y64, t64, rstd64, dtype):
 
 
 # ---- the folded RMSNorm ------------------------------------------------------------------------------------------------------------------
+def rms_f32_part(y64, chain=CHAIN):
+    """the fp32 part of rms_bound (no store) for a kernel whose longest chain of additions is `chain`: |y| (rstd_rel(chain) + 2 U)"""
+    return y64.abs() * (rstd_rel(chain) + 2 * U)
+
+
+def ln_f32_part(x, g, y64, t64, rstd64, chain=CHAIN_WAVE):
+    """the fp32 part of ln_bound (no store) for a kernel whose longest chain of additions is `chain` (the mean's constant is chain + 1)"""
+    x, g = torch.as_tensor(x).double(), torch.as_tensor(g).double()
+    dm = (chain + 1) * U * x.abs().mean(-1, keepdim=True)
+    e_rstd = rstd_rel(chain, term=3) + 0.5 * (dm * rstd64) ** 2
+    return t64.abs() * (e_rstd + 3 * U) + dm * rstd64 * g.abs() + U * y64.abs()
+
+
 def fold_rstd_rel(chain, partial_chain=0):
     """rstd of a folded-norm consumer against the fp64 rstd of the SAME x: `chain` additions over the partial sums (decode flavour: in_n / 16
     per thread + 4 shuffle levels; vt_rowscale_finalize: np / 16 per thread + 16 over the block's LDS column), `partial_chain` additions

@@ -4,6 +4,7 @@ products the oracle's emulation forms (exactly, where the arithmetic is exact: s
 import pytest
 import torch
 
+from tests.mx4_ref import E2M1, _aexp_rows, _deq, _unpack  # noqa: F401
 from tests.util import rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -16,29 +17,6 @@ def dev():
     _lib.load()
     _lib.load(operand="fp16")
     return torch.device("cuda:0")
-
-
-def _unpack(codes_u8):
-    """uint8 [R][K/2] -> int codes [R][K] (even k in bits 3:0)."""
-    c = codes_u8.cpu().to(torch.int32)
-    return torch.stack([c & 15, c >> 4], dim=-1).reshape(c.shape[0], -1)
-
-
-def _aexp_rows(aexp, M, K):
-    """the GEMM-order scale array -> biased exponents [M][K/32]"""
-    KB = K // 32
-    a = aexp.cpu().to(torch.int32)[: ((M + 63) // 64) * KB * 64].view(-1, KB, 16, 4)      # [m / 64][kb][m % 16][(m % 64) / 16]
-    m = torch.arange(M)
-    return a[m // 64, :, m % 16, (m % 64) // 16]
-
-
-E2M1 = torch.tensor([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])
-
-
-def _deq(codes, exps_biased, block):
-    v = E2M1[codes & 7] * torch.where((codes & 8) != 0, -1.0, 1.0)
-    sc = torch.ldexp(torch.ones(exps_biased.shape), exps_biased - 127)
-    return (v.view(codes.shape[0], -1, block) * sc.view(codes.shape[0], -1, 1)).reshape(codes.shape)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
