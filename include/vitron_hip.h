@@ -111,6 +111,8 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
  * gets the launches it got. */
 /* 114 also carries vt_gemm_plan_query3 and vt_gemm_bf16_colsplit WITHOUT a bump: two new symbols, no struct and no existing signature
  * changes; vt_gemm_plan_query and vt_gemm_plan_query2 return what they returned, and vt_gemm_bf16 stores what it stored, bit for bit. */
+/* 114 also carries vt_sample_rows_wm and struct vt_wm_row WITHOUT a bump (with vt_wm_cell_words): two new symbols and one new struct;
+ * struct vt_sample_row, struct vt_trunc_row and the four vt_sample_rows* entry points do not change. */
 #define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
@@ -634,6 +636,65 @@ int vt_sample_rows_trunc(const float* logits, int rows, int V, int ldl, const vt
                          const float* const* adjust /* DEVICE array of `rows` device pointers to fp32 [V][2], entries and the array may be NULL */,
                          const vt_trunc_row* trunc /* DEVICE array [rows], or NULL */,
                          int* out_ids, int* kept_count, float* logprob, void* stream);
+
+/* vt_sample_rows_trunc with a PER-ROW SYNTHID TEXT WATERMARK: transformers' SynthIDTextWatermarkLogitsProcessor
+ * (SynthIDTextWatermarkingConfig; Dathathri et al., Nature 2024), which GenerationMixin runs last, behind every warper -- so it lives in
+ * the sampler, behind the truncation stages. wm: DEVICE array of `rows` vt_wm_row (48 bytes each, 8-byte aligned; the offsets are part of
+ * the ABI):
+ *   @0  uint64_t* cell              DEVICE state of this sequence, vt_wm_cell_words(history_size) words; NULL: the row is not watermarked
+ *   @8  const uint64_t* layer_add   DEVICE [depth]: k_i * M + 1 (mod 2^64) for key k_i, M = 6364136223846793005
+ *   @16 const uint32_t* table       DEVICE bit array of the sampling table, table_size / 32 words, bit t = table[t]
+ *   @24 int32_t depth               1..32 (the number of keys)
+ *   @28 int32_t table_size          a power of two, 32..65536
+ *   @32 int32_t ngram_len           2..8
+ *   @36 int32_t history_size        1..4096 (context_history_size)
+ *   @40 int32_t skip_first          skip_first_ngram_calls (0: off)
+ *   @44 int32_t reserved            0
+ * The cell, in uint64 words: [0] num_calls; [1] the head of the history ring; [2] the context hash of the last call; [3] the flags of
+ * the last call (bit 0 watermarked, bit 1 repeated context, bit 2 skipped); [4..11) the context ids, ngram_len - 1 used; [12..) the
+ * history ring. An all-zero cell is transformers' fresh SynthIDTextWatermarkState: the context holds GENERATED tokens only, zero-padded
+ * at the start. Per sampled row with a cell, where p holds the kept probabilities of vt_sample_rows_trunc and `kept` their sum:
+ *   1. num_calls += 1. With skip_first and num_calls < ngram_len the draw is vt_sample_rows_trunc's and the ring is not touched.
+ *   2. H = the hash of the context: h <- (h + id) * M + 1 from h = 1, in wrapping 64-bit arithmetic.
+ *   3. repeated = one of ALL history_size ring entries equals H (the zero entries of a fresh ring take part); then ring[head] = H,
+ *      head = (head + 1) % history_size. A repeated context is drawn as vt_sample_rows_trunc draws it.
+ *   4. otherwise q = p / kept and, for layer i in [0, depth): q_v *= 1 + g_iv - sum_v g_iv q_v, where g_iv is bit
+ *      (((H + v) * M + 1 + k_i) * M + 1) mod table_size of the table -- fp32, tree sums, a token with q = 0 stays 0.
+ *   5. the draw: vt_sample_rows' inverse CDF over q in index order, the row's uniform (seed, counter, stream) scaled by sum(q).
+ *   6. an id >= 0 is shifted into the context -- on skipped and repeated calls too.
+ * kept_count stays the truncation's survivors, logprob stays over the RAW row. A greedy row (temperature not > 0) ignores its entry and
+ * does not touch its cell; a row whose cell is NULL returns, bit for bit, what vt_sample_rows_trunc returns for it (its other fields are
+ * not read); wm == NULL is the vt_sample_rows_trunc launch itself. allow, adjust and trunc may each be NULL.
+ * The register form only: with wm != NULL a launch that vt_sample_rows would run in the streaming form (V > 32768, ldl % 4 != 0, logits
+ * not 16-byte aligned) is refused with VT_STATUS_ARG and a message. Refused likewise, before any launch: wm not 8-byte aligned, and for a
+ * row with a cell a field outside its range, a table_size that is no power of two, reserved != 0, a NULL or misaligned layer_add / table.
+ * For that the array is read back on `stream` in front of the launch (rows * 48 bytes and a wait for the copy); on a stream that is being
+ * captured it is not, and the kernel treats such an entry as a row without a watermark. Nothing a cell can hold indexes out of bounds:
+ * the head is reduced mod history_size, the context ids are data only.
+ * 114 carries vt_sample_rows_wm and struct vt_wm_row WITHOUT a bump: two new symbols and one new struct, nothing existing changes (see
+ * the note at VT_ABI_VERSION). */
+#define VT_WM_MAX_DEPTH 32
+#define VT_WM_MAX_TABLE 65536
+#define VT_WM_MAX_NGRAM 8
+#define VT_WM_MAX_HISTORY 4096
+typedef struct vt_wm_row {
+  uint64_t* cell;
+  const uint64_t* layer_add;
+  const uint32_t* table;
+  int32_t depth;
+  int32_t table_size;
+  int32_t ngram_len;
+  int32_t history_size;
+  int32_t skip_first;
+  int32_t reserved;
+} vt_wm_row;
+size_t vt_wm_cell_words(int history_size); /* 12 + history_size */
+int vt_sample_rows_wm(const float* logits, int rows, int V, int ldl, const vt_sample_row* params,
+                      const uint32_t* const* allow /* DEVICE array of `rows` device pointers, entries and the array may be NULL */,
+                      const float* const* adjust /* DEVICE array of `rows` device pointers to fp32 [V][2], entries and the array may be NULL */,
+                      const vt_trunc_row* trunc /* DEVICE array [rows], or NULL */,
+                      const vt_wm_row* wm /* DEVICE array [rows], or NULL */,
+                      int* out_ids, int* kept_count, float* logprob, void* stream);
 
 /* BEAM SEARCH (the role of transformers' GenerationMixin beam search: log_softmax + running scores + torch.topk over
  * num_beams * vocab, and the cache reorder behind it).

@@ -122,6 +122,8 @@ SIGNATURES = {
     "vt_sample_rows_allow": (_i, [vp, _i, _i, _i, vp, vp, vp, vp, vp, vp]),
     "vt_sample_rows_adj": (_i, [vp, _i, _i, _i, vp, vp, vp, vp, vp, vp, vp]),
     "vt_sample_rows_trunc": (_i, [vp, _i, _i, _i, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "vt_sample_rows_wm": (_i, [vp, _i, _i, _i, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "vt_wm_cell_words": (_sz, [_i]),
     "vt_beam_step_scratch_bytes": (_sz, [_i, _i, _i]),
     "vt_beam_step": (_i, [vp, _i, _i, _i, _i, vp, _i, vp, vp, vp, vp, _sz, vp]),
     "vt_kv_copy_pages": (_i, [vp, vp, _i, _i, _sz, vp, vp, _i, vp]),

@@ -269,7 +269,8 @@ int vt_sample_top_p_launch(const float* logits, int rows, int V, int ldl, float 
 int vt_sample_rows_launch(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, const uint32_t* const* allow,
                           int* out_ids, int* kept_count, float* logprob, hipStream_t s,    // allow == NULL: vt_sample_rows
                           const float* const* adjust = nullptr,                            // adjust != NULL: vt_sample_rows_adj
-                          const vt_trunc_row* trunc = nullptr);                            // trunc != NULL: vt_sample_rows_trunc
+                          const vt_trunc_row* trunc = nullptr,                             // trunc != NULL: vt_sample_rows_trunc
+                          const vt_wm_row* wm = nullptr);                                  // wm != NULL: vt_sample_rows_wm
 
 // ---- vt_beam.hip ----------------------------------------------------------------------------------
 size_t vt_beam_step_scratch_bytes_impl(int groups, int beams_in, int n_out);

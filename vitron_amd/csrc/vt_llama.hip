@@ -11,6 +11,8 @@
 #include "vt_kernels.h"
 #include "vt_rows.h"
 
+#include <vector>
+
 namespace {
 
 // plan[r] = {kind, index}: kind 0 = token id into tok_table, 1 = row of vis, 2 = row of reg, 3 = zeros
@@ -105,6 +107,11 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
   x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
   return x ^ (x >> 31);
 }
+
+// multiplier of transformers' accumulate_hash (h <- (h + d) * M + 1 in wrapping 64-bit arithmetic): kWm, DESIGN.md 9.16
+constexpr uint64_t kWmMul = 6364136223846793005ull;
+// words of the kWm body's LDS block: the table's bits, three uint64 of state for the write-back, the low words of layer_add
+constexpr int kWmStateWord = VT_WM_MAX_TABLE / 32, kWmLayerWord = kWmStateWord + 6, kWmLdsWords = kWmLayerWord + VT_WM_MAX_DEPTH;
 
 // monotone map float -> uint32 (a < b  <=>  key(a) < key(b)); -inf maps below every finite value
 __device__ __forceinline__ uint32_t order_key(float x) {
@@ -423,11 +430,21 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
 // slots with p > 0 and a stage zeroes what it removes, so no second array and no mask register lives across the body; the typical
 // stage recomputes a slot's d from its p in each of its 31 counting passes instead of keeping 32 keys. With every stage off nothing
 // between the top-p step and the prefix scan runs: p, mine and cnt are the kAdj body's.
-template <bool kRows, bool kAllow = false, bool kAdj = false, bool kTrunc = false>
+// kWm (vt_sample_rows_wm): transformers' SynthIDTextWatermarkLogitsProcessor, which GenerationMixin runs behind every
+// warper, so it stands behind kTrunc: where p holds the kept probabilities, q = p / kept goes through `depth` tournament rounds
+// q *= 1 + g - sum(g q) in place, and the walk draws over sum(q) with the uniform it always had. g of token v at layer i is bit
+// (A_v + layer_add[i]) & (table_size - 1) of the sampling table, A_v = ((H + v) * M + 1) * M for the context hash H: the table size is a
+// power of two <= 2^16, so only the low 32 bits of that 64-bit sum are ever looked at -- one 64-bit multiply for the thread's first
+// token, then 32-bit adds (M * M per slot, layer_add[i] per layer); no A_v is kept, and a slot whose q is 0 is not hashed. The table is
+// staged into LDS (`wm_tab`, table_size / 32 words, with the low words of layer_add behind it). The sequence's state (struct vt_wm_row's cell) is read by every thread and written
+// by thread 0 alone, behind the last barrier. cnt is not recounted: kept_count stays the truncation's survivors. wm == NULL
+// (block-uniform: a row without a cell) runs nothing of this: p, mine and cnt are the kTrunc body's.
+template <bool kRows, bool kAllow = false, bool kAdj = false, bool kTrunc = false, bool kWm = false>
 __device__ __forceinline__ void sample_reg_body(const float* __restrict__ row, int V, const SampleArgs& a, uint32_t* seen,
                                                 int* __restrict__ out_id, int* __restrict__ kept_out, float* __restrict__ logprob,
                                                 const uint32_t* __restrict__ allow = nullptr, const float* __restrict__ adj = nullptr,
-                                                vt_trunc_row tr = vt_trunc_row{}) {
+                                                vt_trunc_row tr = vt_trunc_row{}, const vt_wm_row* __restrict__ wm = nullptr,
+                                                uint32_t* wm_tab = nullptr) {
   constexpr int NPT = 32;
   __shared__ float sh[2][16];
   __shared__ float sh_scan[16];
@@ -671,6 +688,72 @@ __device__ __forceinline__ void sample_reg_body(const float* __restrict__ row, i
       }
     }
   }
+  if constexpr (kWm) {
+    if (wm) {            // block-uniform. The row's fields are re-read where they are used (scalar loads), not carried through the body
+      constexpr uint64_t M = kWmMul;
+      const uint64_t* cell = wm->cell;
+      const int hs = wm->history_size, ngram = wm->ngram_len;
+      const uint64_t calls = cell[0] + 1;
+      uint64_t H = 1;
+      for (int i = 0; i < ngram - 1; ++i) H = (H + cell[4 + i]) * M + 1;       // (the context ids are data only)
+      const bool skipped = wm->skip_first != 0 && calls < (uint64_t)ngram;
+      bool repeated = false;
+      if (!skipped) {
+        const uint32_t* __restrict__ table = wm->table;
+        for (int w = tid; w < (wm->table_size >> 5); w += 1024) wm_tab[w] = table[w];
+        if (tid < wm->depth) wm_tab[kWmLayerWord + tid] = (uint32_t)wm->layer_add[tid];     // (the low words: no global load per round)
+        float hit = 0.f;
+        for (int e = tid; e < hs; e += 1024) hit += cell[12 + e] == H ? 1.f : 0.f;     // ALL entries, the zero ones included
+        repeated = block_sum(hit) > 0.f;          // (its barrier also publishes wm_tab and ends the reads of the ring)
+      }
+      if (tid == 0) {    // what the write-back behind the draw needs, parked in LDS: nothing of it lives in a register across the walk
+        uint64_t* st = (uint64_t*)(wm_tab + kWmStateWord);
+        st[0] = calls;
+        st[1] = H;
+        st[2] = skipped ? 4u : (repeated ? 2u : 1u);
+      }
+      const float kept_p = (skipped || repeated) ? 0.f : block_sum(mine);
+      if (kept_p > 0.f) {
+        const float inv = 1.f / kept_p;
+        const uint32_t tmask = (uint32_t)wm->table_size - 1u, slot_add = (uint32_t)(M * M);
+        const uint32_t a0 = (uint32_t)(((H + (uint64_t)i0) * M + 1) * M);
+        const int depth = wm->depth;
+        uint32_t live = 0u;       // bit j: slot j had q > 0 when the rounds began (one a round zeroes stays set: its g meets a 0)
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) {
+          p[j] *= inv;
+          live |= p[j] > 0.f ? (1u << j) : 0u;
+        }
+        for (int i = 0; i < depth; ++i) {
+          const uint32_t b = a0 + wm_tab[kWmLayerWord + i];
+          uint32_t g = 0u;
+          // the table lookups eight slots at a time, skipping an eighth with nothing alive: a rolled loop over the live mask, so that
+          // the 32 gathers and their addresses are never in registers together beside p[]
+#pragma unroll 1
+          for (int j0 = 0; j0 < NPT; j0 += 8) {
+            if ((live >> j0) & 0xffu) {
+#pragma unroll
+              for (int k = 0; k < 8; ++k) {
+                const uint32_t t = (b + (uint32_t)(j0 + k) * slot_add) & tmask;
+                g |= ((wm_tab[t >> 5] >> (t & 31u)) & 1u) << (j0 + k);
+              }
+            }
+          }
+          g &= live;
+          float m = 0.f;
+#pragma unroll
+          for (int j = 0; j < NPT; ++j) m += ((g >> j) & 1u) ? p[j] : 0.f;
+          m = block_sum(m);
+          const float up = 2.f - m, down = 1.f - m;        // 1 + g - m
+#pragma unroll
+          for (int j = 0; j < NPT; ++j) p[j] *= ((g >> j) & 1u) ? up : down;
+        }
+        mine = 0.f;
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) mine += p[j];
+      }
+    }
+  }
   const float kept = block_sum(mine);
   cnt = block_sum(cnt);
   if (tid == 0) {
@@ -707,9 +790,16 @@ __device__ __forceinline__ void sample_reg_body(const float* __restrict__ row, i
   __syncthreads();
   if (chosen < 0 && mine > 0.f) {  // u landed on a rounding seam: take the last kept token of the highest owning range
     int last = -1;
+    if constexpr (kWm) {   // the slot, not the id: the 32 ids i0 + j of the loads are not kept across the body for this rare path
 #pragma unroll
-    for (int j = 0; j < NPT; ++j)
-      if (p[j] > 0.f) last = i0 + j;
+      for (int j = 0; j < NPT; ++j)
+        if (p[j] > 0.f) last = j;
+      last += tid * NPT;   // (mine > 0: a slot was found)
+    } else {
+#pragma unroll
+      for (int j = 0; j < NPT; ++j)
+        if (p[j] > 0.f) last = i0 + j;
+    }
     atomicMax(&chosen, last);
   }
   __syncthreads();
@@ -718,6 +808,27 @@ __device__ __forceinline__ void sample_reg_body(const float* __restrict__ row, i
     *out_id = id;
     if constexpr (kRows)
       if (logprob) *logprob = (unsigned)id < (unsigned)V ? row[id] - lse : NAN;
+    if constexpr (kWm) {
+      if (wm) {          // every thread's reads of the cell lie in front of the barriers above
+        const uint64_t* st = (const uint64_t*)(wm_tab + kWmStateWord);
+        uint64_t* cell = wm->cell;
+        const int hs = wm->history_size, n1 = wm->ngram_len - 1;
+        const uint64_t H = st[1], flags = st[2];
+        uint64_t head = cell[1] % (uint64_t)hs;       // (whatever the cell holds: inside the ring)
+        if (!(flags & 4u)) {                          // (a skipped call returns in front of transformers' history update)
+          cell[12 + head] = H;
+          head = head + 1 == (uint64_t)hs ? 0 : head + 1;
+        }
+        cell[0] = st[0];
+        cell[1] = head;
+        cell[2] = H;
+        cell[3] = flags;
+        if (id >= 0) {                                // the context: generated ids only, on skipped and repeated calls too
+          for (int i = 0; i + 1 < n1; ++i) cell[4 + i] = cell[5 + i];
+          cell[4 + n1 - 1] = (uint64_t)id;
+        }
+      }
+    }
   }
 }
 
@@ -834,6 +945,44 @@ __global__ __launch_bounds__(1024) void sample_rows_trunc_kernel(const float* __
     sample_stream_body<true, true, true, true>(row, V, a, seen, out_ids + r, kept, lp, mask, adj, trunc[r]);
 }
 
+// vt_sample_rows_wm: the trunc launch with row r's SynthID watermark wm[r]. A kernel of its own once more, so that the
+// four above stay the code they were; the register form only (the streaming body keeps no per-token state across the rounds). The allow,
+// adjust and trunc ARRAYS may be NULL. A greedy row takes the kAdj body and never touches its cell; an entry the launcher would have
+// refused (it reads the array in front of the launch; the array may have changed since) is a row without a watermark here, so that no
+// field value indexes outside the table, the ring or the context.
+__device__ __forceinline__ bool wm_row_ok(const vt_wm_row& w) {
+  return w.layer_add && w.table && w.depth >= 1 && w.depth <= VT_WM_MAX_DEPTH && w.table_size >= 32 && w.table_size <= VT_WM_MAX_TABLE
+         && (w.table_size & (w.table_size - 1)) == 0 && w.ngram_len >= 2 && w.ngram_len <= VT_WM_MAX_NGRAM && w.history_size >= 1
+         && w.history_size <= VT_WM_MAX_HISTORY;
+}
+__global__ __launch_bounds__(1024) void sample_rows_wm_kernel(const float* __restrict__ logits, int V, int ldl,
+                                                              const vt_sample_row* __restrict__ params,
+                                                              const uint32_t* const* __restrict__ allow,
+                                                              const float* const* __restrict__ adjust,
+                                                              const vt_trunc_row* __restrict__ trunc, const vt_wm_row* __restrict__ wm,
+                                                              int* __restrict__ out_ids, int* __restrict__ kept_count,
+                                                              float* __restrict__ logprob) {
+  __shared__ uint32_t seen[32 * 1024 / 32];
+  __shared__ __attribute__((aligned(8))) uint32_t wm_tab[kWmLdsWords];
+  const int r = blockIdx.x;
+  SampleArgs a = row_args(params[r]);
+  const float* row = logits + (size_t)r * ldl;
+  const uint32_t* mask = allow ? allow[r] : nullptr;
+  const float* adj = adjust ? adjust[r] : nullptr;
+  int* const kept = kept_count ? kept_count + r : nullptr;
+  float* const lp = logprob ? logprob + r : nullptr;
+  if (a.greedy) {        // block-uniform
+    a.greedy = true;
+    sample_reg_body<true, true, true>(row, V, a, seen, out_ids + r, kept, lp, mask, adj);
+    return;
+  }
+  a.greedy = false;
+  const vt_wm_row* w = wm + r;
+  if (!w->cell || !wm_row_ok(*w)) w = nullptr;
+  sample_reg_body<true, true, true, true, true>(row, V, a, seen, out_ids + r, kept, lp, mask, adj, trunc ? trunc[r] : vt_trunc_row{}, w,
+                                                wm_tab);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Shifted-token cross entropy of LlamaForCausalLM.forward(labels=...) (ignore_index rows skipped, mean over the rest):
 //   nll[r] = logsumexp(logits[r]) - logits[r][label[r]]    one 1024-thread block per row, then one block averages.
@@ -893,15 +1042,56 @@ int vt_sample_top_p_launch(const float* logits, int rows, int V, int ldl, float 
   return VT_OK;
 }
 
+// vt_sample_rows_wm refuses a field outside its range by name, and the array is on the device: it is read back in front of the launch,
+// rows * 48 bytes on the launch's own stream (so behind whatever uploads it) and a wait for that copy. A stream that is being captured
+// cannot wait; there sample_rows_wm_kernel's own wm_row_ok stands alone (such an entry is a row without a watermark). A row whose cell
+// is NULL is not watermarked and its other fields are not looked at.
+static int wm_rows_check(const vt_wm_row* wm, int rows, hipStream_t s) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cap) != hipSuccess) (void)hipGetLastError();
+  if (cap != hipStreamCaptureStatusNone) return VT_OK;
+  std::vector<vt_wm_row> h((size_t)rows);
+  VT_HIP(hipMemcpyAsync(h.data(), wm, (size_t)rows * sizeof(vt_wm_row), hipMemcpyDeviceToHost, s));
+  VT_HIP(hipStreamSynchronize(s));
+  for (int r = 0; r < rows; ++r) {
+    const vt_wm_row& w = h[(size_t)r];
+    if (!w.cell) continue;
+    VT_REQUIRE(((uintptr_t)w.cell % 8) == 0 && w.layer_add && ((uintptr_t)w.layer_add % 8) == 0 && w.table && ((uintptr_t)w.table % 4) == 0,
+               "vt_sample_rows_wm: wm[%d]: cell and layer_add must be 8-byte aligned, table 4-byte aligned, layer_add and table not NULL", r);
+    VT_REQUIRE(w.depth >= 1 && w.depth <= VT_WM_MAX_DEPTH, "vt_sample_rows_wm: wm[%d].depth=%d (1 <= depth <= %d)", r, w.depth,
+               VT_WM_MAX_DEPTH);
+    VT_REQUIRE(w.table_size >= 32 && w.table_size <= VT_WM_MAX_TABLE && (w.table_size & (w.table_size - 1)) == 0,
+               "vt_sample_rows_wm: wm[%d].table_size=%d (a power of two, 32 <= table_size <= %d)", r, w.table_size, VT_WM_MAX_TABLE);
+    VT_REQUIRE(w.ngram_len >= 2 && w.ngram_len <= VT_WM_MAX_NGRAM, "vt_sample_rows_wm: wm[%d].ngram_len=%d (2 <= ngram_len <= %d)", r,
+               w.ngram_len, VT_WM_MAX_NGRAM);
+    VT_REQUIRE(w.history_size >= 1 && w.history_size <= VT_WM_MAX_HISTORY,
+               "vt_sample_rows_wm: wm[%d].history_size=%d (1 <= history_size <= %d)", r, w.history_size, VT_WM_MAX_HISTORY);
+    VT_REQUIRE(w.reserved == 0, "vt_sample_rows_wm: wm[%d].reserved=%d (must be 0)", r, w.reserved);
+  }
+  return VT_OK;
+}
+
 int vt_sample_rows_launch(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, const uint32_t* const* allow,
                           int* out_ids, int* kept_count, float* logprob, hipStream_t s, const float* const* adjust,
-                          const vt_trunc_row* trunc) {
+                          const vt_trunc_row* trunc, const vt_wm_row* wm) {
   VT_REQUIRE(logits && params && out_ids, "vt_sample_rows: null pointer (logits, params and out_ids are required)");
   VT_REQUIRE(rows > 0 && V > 0 && ldl >= V, "vt_sample_rows: rows=%d V=%d ldl=%d (rows, V > 0 and ldl >= V)", rows, V, ldl);
   VT_REQUIRE(((uintptr_t)params % 8) == 0, "vt_sample_rows: params must be 8-byte aligned");
   VT_REQUIRE(((uintptr_t)allow % 8) == 0, "vt_sample_rows_allow: the allow pointer array must be 8-byte aligned");
   VT_REQUIRE(((uintptr_t)adjust % 8) == 0, "vt_sample_rows_adj: the adjust pointer array must be 8-byte aligned");
   VT_REQUIRE(((uintptr_t)trunc % 4) == 0, "vt_sample_rows_trunc: trunc must be 4-byte aligned");
+  if (wm) {
+    VT_REQUIRE(((uintptr_t)wm % 8) == 0, "vt_sample_rows_wm: wm must be 8-byte aligned");
+    VT_REQUIRE(V <= 32 * 1024 && (ldl % 4) == 0 && ((uintptr_t)logits % 16) == 0,
+               "vt_sample_rows_wm: V=%d ldl=%d: the watermark runs in the register form only (V <= 32768, ldl %% 4 == 0, logits 16-byte "
+               "aligned)", V, ldl);
+    const int st = wm_rows_check(wm, rows, s);
+    if (st != VT_OK) return st;
+    hipLaunchKernelGGL(sample_rows_wm_kernel, dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, allow, adjust, trunc, wm, out_ids,
+                       kept_count, logprob);
+    VT_LAUNCH_CHECK();
+    return VT_OK;
+  }
   if (V <= 32 * 1024 && (ldl % 4) == 0 && ((uintptr_t)logits % 16) == 0) {
     if (trunc)
       hipLaunchKernelGGL(sample_rows_trunc_kernel<true>, dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, allow, adjust, trunc,

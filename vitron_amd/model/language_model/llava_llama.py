@@ -598,12 +598,24 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         model's final rows. Every row chooses its own layer (transformers averages the divergences over the batch): a row gets what it
         gets alone. self.last_dola_layers: int64 [B, n] -- the layer chosen for every emitted token. ValueError before any device work:
         a bad dola_layers, dola_relative_top outside (0, 1]. Refused with NotImplementedError, naming the argument: num_beams > 1,
-        penalty_alpha > 0, guidance_scale, padded_batch."""
+        penalty_alpha > 0, guidance_scale, padded_batch.
+        SynthID text watermark (transformers' watermarking_config = SynthIDTextWatermarkingConfig, its
+        SynthIDTextWatermarkLogitsProcessor), taken from **kwargs: a SynthIDTextWatermarkingConfig, a dict of its fields or a
+        vitron_amd.watermark.SynthIDWatermark; None is off and the call runs the launches it always ran. transformers runs the
+        processor behind every warper, so the tournament lives in the sampler: every step's sampler launch is ONE vt_sample_rows_wm,
+        behind everything that shapes the row (guidance, DoLa, bans, automata, bias, the truncation stages). Every sample owns an
+        all-zero cell on the device (transformers' fresh state: the context holds generated tokens only); the cells and the B vt_wm_row
+        entries are uploaded once before the loop. return_logits, return_logprobs and top_logprobs stay RAW.
+        vitron_amd.watermark.SynthIDWatermark(config).mean_g(ids, generated_from=prompt length) scores a reply. ValueError /
+        NotImplementedError before any device work: what SynthIDWatermark refuses (the green-list WatermarkingConfig, debug_mode, a
+        sampling table that is no power of two in [32, 65536], ...). Refused with NotImplementedError before any page is taken:
+        do_sample=False, num_beams > 1, penalty_alpha > 0, padded_batch, vocab_size > 32768."""
         from ...picker import StepPicker, negative_prompt, resolve_generate_args
         guide = {k: kwargs.pop(k, None) for k in ("guidance_scale", "negative_prompt_ids", "negative_attention_mask", "negative_images",
                                                   "negative_regions", "guidance_plausibility")}
         penalty_alpha = kwargs.pop("penalty_alpha", None)
         dola_layers, dola_relative_top = kwargs.pop("dola_layers", None), kwargs.pop("dola_relative_top", 0.1)
+        watermarking_config = kwargs.pop("watermarking_config", None)
         a = resolve_generate_args(
             self.config, input_ids.shape[1], do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k,
             max_new_tokens=max_new_tokens, max_length=max_length, stopping_criteria=stopping_criteria, eos_token_id=eos_token_id,
@@ -615,7 +627,7 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p, typical_p=typical_p,
             epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, top_logprobs=top_logprobs, automaton=automaton, choices=choices,
             batch_size=input_ids.shape[0], penalty_alpha=penalty_alpha, dola_layers=dola_layers, dola_relative_top=dola_relative_top,
-            **guide)
+            watermarking_config=watermarking_config, **guide)
         self.last_dola_layers = None
         dev = self.device
         neg_ids = neg_mask = None

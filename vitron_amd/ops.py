@@ -661,7 +661,7 @@ def adjust_pointers(adjust, rows: int, V: int, device) -> torch.Tensor:
 
 def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = False, return_logprob: bool = False, allow=None,
                 _allow_ptrs: Optional[torch.Tensor] = None, adjust=None, _adjust_ptrs: Optional[torch.Tensor] = None,
-                trunc: Optional[torch.Tensor] = None):
+                trunc: Optional[torch.Tensor] = None, watermark: Optional[torch.Tensor] = None):
     """One token id per row (int32, on device) with PER-ROW parameters: greedy and sampled rows, penalties and the chosen token's
     log-probability in one launch; see vt_sample_rows in include/vitron_hip.h. `params`: the device array of vt_sample_row that
     sampling.pack_sample_rows builds (uint8 [rows, 48]). Returns ids, or (ids[, kept_count][, logprob]) when either is asked for.
@@ -673,8 +673,12 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = 
     2 * V elements, the (pre, post) pairs of ops.bias_rows; pre is added before the repetition penalty, post after it. _adjust_ptrs is
     its private pointer-array form, like _allow_ptrs. With neither, the launches are the ones above.
     trunc: per-row truncation (vt_sample_rows_trunc: min_p, typical_p, epsilon_cutoff, eta_cutoff after top-k and top-p) -- the device
-    array of vt_trunc_row that sampling.pack_trunc_rows builds (uint8, rows x 16 bytes). None: exactly the calls above."""
+    array of vt_trunc_row that sampling.pack_trunc_rows builds (uint8, rows x 16 bytes). None: exactly the calls above.
+    watermark: per-row SynthID text watermark (vt_sample_rows_wm, DESIGN.md 9.16: the tournament behind the truncation stages, the
+    sequences' state on the device) -- the device array of vt_wm_row that watermark.pack_wm_rows builds (uint8, rows x 48 bytes).
+    None: exactly the calls above."""
     from .sampling import ROW_BYTES, TRUNC_ROW_BYTES
+    from .watermark import WM_ROW_BYTES
     lib = _lib.load_any()
     _chk_rows(logits, torch.float32, "sample_rows.logits")
     rows, V = logits.shape
@@ -699,7 +703,12 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = 
                               or not trunc.is_contiguous() or trunc.numel() != rows * TRUNC_ROW_BYTES):
         raise _lib.VitronHipError(f"sample_rows.trunc: expected a contiguous uint8 tensor of {rows} x {TRUNC_ROW_BYTES} bytes on the logits' "
                                   "device (sampling.pack_trunc_rows)")
-    if trunc is not None or adjust is not None or _adjust_ptrs is not None:
+    if watermark is not None and (not isinstance(watermark, torch.Tensor) or watermark.device != logits.device
+                                  or watermark.dtype != torch.uint8 or not watermark.is_contiguous()
+                                  or watermark.numel() != rows * WM_ROW_BYTES):
+        raise _lib.VitronHipError(f"sample_rows.watermark: expected a contiguous uint8 tensor of {rows} x {WM_ROW_BYTES} bytes on the "
+                                  "logits' device (watermark.pack_wm_rows)")
+    if watermark is not None or trunc is not None or adjust is not None or _adjust_ptrs is not None:
         aptrs = None
         if _allow_ptrs is not None:
             aptrs = given_ptrs(_allow_ptrs, "_allow_ptrs")
@@ -710,7 +719,10 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = 
             jptrs = given_ptrs(_adjust_ptrs, "_adjust_ptrs")
         elif adjust is not None:
             jptrs = adjust_pointers(adjust, rows, V, logits.device)
-        if trunc is not None:
+        if watermark is not None:
+            _lib.check(lib.vt_sample_rows_wm(_p(logits), rows, V, logits.stride(0), _p(params), _p(aptrs), _p(jptrs), _p(trunc),
+                                             _p(watermark), _p(out), _p(kept), _p(lp), _stream()), "vt_sample_rows_wm", lib)
+        elif trunc is not None:
             _lib.check(lib.vt_sample_rows_trunc(_p(logits), rows, V, logits.stride(0), _p(params), _p(aptrs), _p(jptrs), _p(trunc), _p(out),
                                                 _p(kept), _p(lp), _stream()), "vt_sample_rows_trunc", lib)
         else:

@@ -66,6 +66,7 @@ class GenerateArgs:
     penalty_alpha: float = 0.0                   # contrastive search (vt_contrast_rows); 0 is off
     dola_layers: Optional[Tuple[int, ...]] = None   # DoLa (vt_dola_rows): the candidate layers, resolved; None is off
     dola_relative_top: float = 0.1               # a token stays iff p_final >= relative_top * max p_final
+    watermark: Any = None                        # a watermark.SynthIDWatermark (vt_sample_rows_wm); None is off
 
     @property
     def guided(self) -> bool:
@@ -103,7 +104,7 @@ class GenerateArgs:
         """Does a step need the per-row sampler (vt_sample_rows) instead of vt_argmax / vt_sample_top_p?"""
         return (float(self.repetition_penalty) != 1.0 or bool(self.return_logprobs) or self.constrained or self.ngram > 0
                 or self.adjusted or self.truncated or self.automaton is not None or self.guidance_plausibility > 0
-                or self.dola)
+                or self.dola or self.watermark is not None)
 
 
 def static_mask_schedule(V: int, steps: int, banned_always, banned_begin, min_new: int, eos, allowed_ids):
@@ -135,7 +136,8 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
                           frequency_penalty=0.0, min_p=None, typical_p=None, epsilon_cutoff=None, eta_cutoff=None,
                           top_logprobs=0, automaton=None, choices=None, guidance_scale=None, negative_prompt_ids=None,
                           negative_attention_mask=None, negative_images=None, negative_regions=None, guidance_plausibility=0.0,
-                          batch_size=None, penalty_alpha=None, dola_layers=None, dola_relative_top=0.1) -> GenerateArgs:
+                          batch_size=None, penalty_alpha=None, dola_layers=None, dola_relative_top=0.1,
+                          watermarking_config=None) -> GenerateArgs:
     """generate()'s keyword arguments as a GenerateArgs. Raises, in this order and before any device work: the argument errors of
     num_beams / no_repeat_ngram_size, everything a beam call refuses, the padded_batch refusals that depend on arguments alone, the
     sampling values, the constraint arguments, a step the constraints leave no token for, constraints with padded_batch, the values of
@@ -153,7 +155,10 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
     check_contrastive's order. penalty_alpha None or 0, or top_k == 1, is off. DoLa: the VALUES of dola_layers and
     dola_relative_top (sampling.check_dola: ValueError) are checked right behind penalty_alpha's; a beam call refuses dola_layers with its
     other optional arguments; padded_batch, guidance_scale and penalty_alpha > 0 are refused with it (NotImplementedError) at the very end.
-    dola_layers None is off. The sample seed
+    dola_layers None is off. The SynthID watermark: watermarking_config is resolved by watermark.SynthIDWatermark right
+    behind dola_layers' values (its ValueError / NotImplementedError, the green-list scheme among them); a beam call refuses it with its
+    other optional arguments; do_sample=False, penalty_alpha > 0, padded_batch and a vocabulary beyond the sampler's register form are
+    refused with it (NotImplementedError) right behind the beam refusals. None is off. The sample seed
     is drawn from torch's global CPU generator (so torch.manual_seed makes sampling reproducible, as with GenerationMixin.sample) and
     only when sampling without `seed`, after the beam refusals: greedy and refused calls leave the RNG state alone."""
     num_beams = int(num_beams)
@@ -162,6 +167,8 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
     alpha = check_penalty_alpha(penalty_alpha, do_sample)
     dola, dola_rt = check_dola(dola_layers, dola_relative_top, 0 if dola_layers is None else int(config.num_hidden_layers),
                                bool(getattr(config, "tie_word_embeddings", False)))
+    from .watermark import as_watermark
+    watermark = as_watermark(watermarking_config)
     top_k_given = top_k
     if no_repeat_ngram_size is None:
         no_repeat_ngram_size = 0
@@ -201,11 +208,23 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
         + (("top_logprobs=...",) if top_logprobs else ()) + (("automaton=...",) if automaton is not None else ())
         + (("guidance_scale=...",) if guidance_scale is not None and guidance_scale != 1 else ())
         + (("penalty_alpha=...",) if alpha > 0 else ())
-        + (("dola_layers=...",) if dola is not None else ()))
+        + (("dola_layers=...",) if dola is not None else ())
+        + (("watermarking_config=...",) if watermark is not None else ()))
     if num_beams > 1:
         check_beam_arguments(a, int(config.vocab_size))
     elif a.num_return_sequences != 1:
         raise NotImplementedError("generate(num_return_sequences=...) needs num_beams > 1")
+    if watermark is not None:
+        if not do_sample:
+            raise NotImplementedError("generate(watermarking_config=..., do_sample=False) is not implemented: the SynthID tournament "
+                                      "reshapes the distribution a token is DRAWN from; a greedy call has none")
+        if alpha > 0:
+            raise NotImplementedError("generate(watermarking_config=..., penalty_alpha > 0) is not implemented")
+        if padded_batch:
+            raise NotImplementedError("generate(watermarking_config=..., padded_batch=True) is not implemented; use the default packed "
+                                      "batch")
+        watermark.check_vocab(int(config.vocab_size), "generate(watermarking_config=...)")
+        a = dataclasses.replace(a, watermark=watermark)
     if a.ngram and padded_batch:
         raise NotImplementedError("generate(padded_batch=True) does not take no_repeat_ngram_size; use the default packed batch")
     if padded_batch and parse_kv_cache_dtype(getattr(config, "kv_cache_dtype", None)) == "fp8":
@@ -472,6 +491,9 @@ class StepPicker:
         buffers never change and are built by ONE launch here, before the prefill;
       - with min_p / typical_p / epsilon_cutoff / eta_cutoff: the B vt_trunc_row entries, the same at every step; the
         sampler launch is vt_sample_rows_trunc then.
+      - with watermarking_config: the watermark's table and layer constants (once per device, kept on the watermark), one
+        all-zero cell per sample and the B vt_wm_row entries, the same at every step; the sampler launch is vt_sample_rows_wm then and
+        the cells live and change on the device only.
       - with an automaton: its tables (once per device, kept on the automaton), the [B, 2] cells {start, 0}, the B
         working masks vt_fsm_rows writes, the ids every row has GENERATED (the tail of the penalty history, or the history the
         penalties count over, or one of its own) and the [steps, B] vt_fsm_row array (gen_len = step, base = the step's static mask or
@@ -543,6 +565,11 @@ class StepPicker:
                                            for st in range(steps) for b in range(B)], dev).view(steps, B, BAN_ROW_BYTES)
             self.ban_ptrs = row_buffer(w)[2]     # (uploaded behind the rows that name the same addresses)
         self.trunc = pack_trunc_rows([a.trunc] * B, dev) if a.truncated else None
+        self.wm_rows = self.wm_cells = None
+        if a.watermark is not None:              # one cell per sample; the array is constant over the steps
+            from .watermark import pack_wm_rows
+            self.wm_cells = [a.watermark.new_cell(dev) for _ in range(B)]
+            self.wm_rows = pack_wm_rows([(a.watermark, c) for c in self.wm_cells], dev)
         self.adj_ptrs = self.bias_rows = self.gen_hist = None
         gen_ptr = None
 
@@ -651,7 +678,7 @@ class StepPicker:
         if self.bias_rows is not None:           # the rows' adjustments for this pick, from what they have generated: one launch
             ops.bias_rows(self.bias_rows[step], self.B, self.V)
         nxt = ops.sample_rows(logits, self.rows[step], return_logprob=bool(a.return_logprobs), _allow_ptrs=ptrs, _adjust_ptrs=self.adj_ptrs,
-                              trunc=self.trunc)
+                              trunc=self.trunc, watermark=self.wm_rows)
         if a.return_logprobs:
             nxt, lp = nxt
             self._lp.append(lp)

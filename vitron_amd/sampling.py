@@ -249,7 +249,11 @@ class SamplingParams(_SamplingFields):
     dola_layers and dola_relative_top are of the same kind: DoLa decoding, generate(dola_layers=...)'s arguments --
     "low", "high" or a sequence of layer indices (stored as a tuple; resolved against the model at submit()), None is off;
     dola_relative_top in (0, 1], 0.1 by default. A DoLa request takes one decode row. Refused together with guidance_scale
-    (NotImplementedError). repr shows them when dola_layers is set."""
+    (NotImplementedError). repr shows them when dola_layers is set.
+    watermarking_config is of the same kind: a transformers SynthIDTextWatermarkingConfig, a dict of its fields or a
+    vitron_amd.watermark.SynthIDWatermark, resolved at construction and kept as `.watermark` (None is off). The request's draws go through
+    the SynthID tournament inside the sampler (vt_sample_rows_wm), its state in a cell on the device. A sampled request only: with
+    temperature 0 it is refused (NotImplementedError). Compared by the configuration's values; repr shows it when set."""
     DOLA_NAMES = ("dola_layers", "dola_relative_top")
     GUIDE_NAMES = ("guidance_scale", "negative_prompt_ids", "guidance_plausibility", "negative_images")
     TRUNC_NAMES = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
@@ -257,7 +261,7 @@ class SamplingParams(_SamplingFields):
 
     def __init__(self, *args, min_p: float = 0.0, typical_p: float = 1.0, epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0,
                  top_logprobs: int = 0, automaton=None, guidance_scale=None, negative_prompt_ids=None, guidance_plausibility=0.0,
-                 negative_images=None, dola_layers=None, dola_relative_top=0.1, **kw):
+                 negative_images=None, dola_layers=None, dola_relative_top=0.1, watermarking_config=None, **kw):
         for name, value in zip(self.TRUNC_NAMES, (min_p, typical_p, epsilon_cutoff, eta_cutoff)):
             object.__setattr__(self, name, value)
         object.__setattr__(self, "top_logprobs", top_logprobs)
@@ -271,6 +275,8 @@ class SamplingParams(_SamplingFields):
             object.__setattr__(self, name, value)
         object.__setattr__(self, "dola_layers", tuple(dola_layers) if isinstance(dola_layers, list) else dola_layers)
         object.__setattr__(self, "dola_relative_top", dola_relative_top)
+        from .watermark import as_watermark      # (its ValueError / NotImplementedError: the green-list scheme, debug_mode, ...)
+        object.__setattr__(self, "watermark", as_watermark(watermarking_config))
         super().__init__(*args, **kw)            # (its __post_init__ validates: the four are set by then)
 
     def __setattr__(self, name, value):          # (the frozen base guards its own fields only once it is subclassed)
@@ -310,6 +316,9 @@ class SamplingParams(_SamplingFields):
         check_dola(self.dola_layers, self.dola_relative_top, 2 ** 30, what="SamplingParams")
         if self.dola and self.guided:
             raise NotImplementedError("SamplingParams: dola_layers together with guidance_scale is not implemented: one contrast per request")
+        if self.watermark is not None and not self.temperature > 0:
+            raise NotImplementedError("SamplingParams: watermarking_config on a greedy request (temperature 0) is not implemented: the "
+                                      "SynthID tournament reshapes the distribution a token is DRAWN from")
 
     @property
     def dola(self) -> bool:
@@ -337,7 +346,8 @@ class SamplingParams(_SamplingFields):
         return tuple(getattr(self, n) for n in self.__dataclass_fields__) + self.trunc_row_raw() + (int(self.top_logprobs),) \
             + (None if self.automaton is None else id(self.automaton),) \
             + ((self.guidance_scale, self.negative_prompt_ids) if self.guidance_scale is not None or self.negative_prompt_ids is not None else ()) \
-            + (("dola", self.dola_layers, self.dola_relative_top) if self.dola_layers is not None else ())
+            + (("dola", self.dola_layers, self.dola_relative_top) if self.dola_layers is not None else ()) \
+            + (("watermark", self.watermark.key()) if self.watermark is not None else ())
 
     def __eq__(self, other):
         return self._key() == other._key() if other.__class__ is self.__class__ else NotImplemented
@@ -354,12 +364,14 @@ class SamplingParams(_SamplingFields):
         names += [n for n, off in zip(self.GUIDE_NAMES, (None, None, 0.0, None)) if getattr(self, n) is not off and getattr(self, n) != off]
         if self.dola_layers is not None:
             names += list(self.DOLA_NAMES)
-        return "SamplingParams(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in names) + ")"
+        wm = "" if self.watermark is None else f", watermarking_config={self.watermark.to_dict()!r}"
+        return "SamplingParams(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in names) + wm + ")"
 
     def replace(self, **changes) -> "SamplingParams":
         """A copy with some settings changed (dataclasses.replace knows only the dataclass fields)."""
         kw = {n: getattr(self, n) for n in list(self.__dataclass_fields__) + list(self.TRUNC_NAMES) + ["top_logprobs", "automaton"]
               + list(self.GUIDE_NAMES) + list(self.DOLA_NAMES)}
+        kw["watermarking_config"] = self.watermark
         kw.update(changes)
         return SamplingParams(**kw)
 

@@ -87,6 +87,8 @@ class _Request:
     neg_flat: Optional[torch.Tensor] = None          # its embedded rows [Ln, H] (kept while the request waits for pages)
     need_neg: int = 0                                # the part of `need` that is the second sequence's
     dola: Optional[tuple] = None                     # a DoLa request's candidate layers, resolved against the model
+    wm_cell: Optional[torch.Tensor] = None           # device int64: the SynthID state of sampling.watermark, taken at the
+                                                     # request's first pick (its admission), dropped with the masks when it retires
 
     @property
     def rows(self) -> int:
@@ -137,7 +139,11 @@ class ServingEngine:
         max_batch's rows; its tokens equal generate(guidance_scale=, negative_prompt_ids=) for the request alone.
         sampling.dola_layers (None is off): DoLa decoding with sampling.dola_relative_top. The request takes one decode
         row; its tokens equal generate(dola_layers=, dola_relative_top=) for the request alone. ValueError here when the layers do not
-        fit the model."""
+        fit the model.
+        sampling.watermarking_config (None is off): the SynthID text watermark of generate(watermarking_config=). The
+        request's state lives in a cell on the device from its first pick to its retirement; its tokens equal
+        generate(watermarking_config=) for the request alone, whatever else is in the batch. NotImplementedError here when the
+        vocabulary is beyond the sampler's register form."""
         ids = input_ids if input_ids.dim() == 2 else input_ids.unsqueeze(0)
         if ids.shape[0] != 1:
             raise ValueError("submit() takes one sequence per request")
@@ -151,6 +157,8 @@ class ServingEngine:
             check_constraints(sampling, eos_set, int(self.model.config.vocab_size))     # ValueError: nothing is queued
             if sampling.automaton is not None:
                 sampling.automaton.check(int(self.model.config.vocab_size), sorted(eos_set))
+        if sampling is not None and sampling.watermark is not None:
+            sampling.watermark.check_vocab(int(self.model.config.vocab_size), "submit(sampling=SamplingParams(watermarking_config=...))")
         dola = None
         if sampling is not None and sampling.dola:
             dola, _ = check_dola(sampling.dola_layers, sampling.dola_relative_top, int(self.model.config.num_hidden_layers),
@@ -280,6 +288,7 @@ class ServingEngine:
         r.ban_mask = r.ban_seqs = None
         r.adj_buf = r.adj_ids = r.adj_vals = r.gen = None
         r.fsm_cell = r.fsm_mask = None
+        r.wm_cell = None
 
     def _prepare_allow(self, r: _Request) -> None:
         """The allow mask of r's next pick: a pure host function of (r.sampling, r.tokens, r.eos) -- the host has read back
@@ -329,6 +338,9 @@ class ServingEngine:
         9.9) turns the launch into ONE vt_sample_rows_trunc: its row carries its four values, every other row an all-inactive entry,
         which the kernel treats bit for bit as vt_sample_rows_adj does. While no active request is truncated the launches are exactly
         the ones above.
+        A request with SamplingParams(watermarking_config=) turns the launch into ONE vt_sample_rows_wm: its row names
+        its cell, every other row carries cell = NULL, which the kernel treats bit for bit as vt_sample_rows_trunc does. While no active
+        request is watermarked the launches are exactly the ones above.
         A request with SamplingParams(top_logprobs=N > 0): AFTER the pick, ONE vt_logprob_rows launch over the span of
         rows from the first to the last such request, the device ids just picked as targets and the largest N asked for as n_top (a
         shorter list is a prefix of a longer one, bit for bit). Its output stays on the device (r.last_top) until step() reads it back
@@ -423,7 +435,18 @@ class ServingEngine:
         if any(r.sampling is not None and r.sampling.truncated for r in reqs):
             trunc = pack_trunc_rows([r.sampling.trunc_row if (r.sampling is not None and r.sampling.truncated) else None for r in reqs],
                                     logits.device)
-        res = ops.sample_rows(logits, pack_sample_rows(rows, logits.device), return_logprob=want_lp, allow=allow, adjust=adj, trunc=trunc)
+        wm = None
+        if any(r.sampling is not None and r.sampling.watermark is not None for r in reqs):
+            from .watermark import pack_wm_rows
+            entries = []
+            for r in reqs:
+                w = None if r.sampling is None else r.sampling.watermark
+                if w is not None and r.wm_cell is None:
+                    r.wm_cell = w.new_cell(logits.device)
+                entries.append(None if w is None else (w, r.wm_cell))
+            wm = pack_wm_rows(entries, logits.device)
+        res = ops.sample_rows(logits, pack_sample_rows(rows, logits.device), return_logprob=want_lp, allow=allow, adjust=adj, trunc=trunc,
+                              watermark=wm)
         ids, lp = res if want_lp else (res, None)
         for i, r in enumerate(reqs):
             if r.sampling is not None and r.sampling.wants_logprobs:
