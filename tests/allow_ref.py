@@ -1,4 +1,4 @@
-"""Host restatement of the allow masks of vt_sample_rows_allow (vitron_amd/csrc/vt_llama.hip) for
+"""Host restatement of the allow masks of vt_sample_rows_allow (vitron_amd/csrc/vt_sample.hip) for
 tests/test_allow_ref_host.py, tests/test_gpu_sample_allow.py and tests/test_gpu_constrained_requests.py: the word / bit layout as an
 explicit loop, the -inf edit that DEFINES the kernel's answer (out_ids and kept_count equal vt_sample_rows on the edited logits), the
 allowed set of a constrained request as plain Python sets (static ids, min_new_tokens, the choices walk, allowed_tokens_fn; all

@@ -1,4 +1,4 @@
-"""Host restatement of the per-row sampler (vt_sample_rows, vitron_amd/csrc/vt_llama.hip) for
+"""Host restatement of the per-row sampler (vt_sample_rows, vitron_amd/csrc/vt_sample.hip) for
 tests/test_sample_ref_host.py, tests/test_gpu_sample_rows.py and tests/test_gpu_sampling_requests.py: the repetition penalty in fp32
 (bit for bit what the kernel computes), the warpers' keep-sets in transformers' order (4.31: RepetitionPenaltyLogitsProcessor, then
 TemperatureLogitsWarper, TopKLogitsWarper, TopPLogitsWarper), the counter-based uniform (splitmix64 of seed, counter, stream), the

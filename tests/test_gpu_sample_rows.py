@@ -167,6 +167,60 @@ def test_logprob_inside_the_fp64_bound(dev, V, record_property):
     record_property("logprob_err_over_bound", worst)
 
 
+@pytest.mark.parametrize("V,ldl", ((1000, 1000), (1001, 1001)))          # the register form; the streaming form by misalignment
+def test_every_entry_point_without_its_arrays_is_vt_sample_rows(dev, V, ldl):
+    """The library picks the kernel by the highest array it is given, whichever entry point carries it. Four rows (greedy; sampled;
+    sampled with a 5-id history under a penalty of 1.3; greedy), once with ids alone and once with kept_count and logprob, through raw
+    ctypes: each wider entry point returns the bits of vt_sample_rows with every added array NULL, and with neutral arrays -- all-ones
+    masks, all-zero [V][2] adjustments, all-inactive vt_trunc_row, vt_wm_row without a cell -- each together with the neutral arrays
+    below it. vt_sample_rows_wm with an array keeps its refusal in the streaming form.
+    Left out, asserted elsewhere in both forms: vt_sample_rows_allow with allow == NULL (test_gpu_sample_allow.py's
+    test_allow_none_is_sample_rows); an all-inactive trunc array or a cell-less wm array ALONE, behind NULL arrays
+    (test_gpu_sample_trunc.py's and test_gpu_sample_wm.py's bit-equality tests, through ops.sample_rows)."""
+    from vitron_amd import _lib
+    from vitron_amd.sampling import pack_trunc_rows
+    from vitron_amd.watermark import pack_wm_rows
+    lib = _lib.load()
+    n = 4
+    buf = torch.zeros((n, ldl), dtype=torch.float32)
+    buf[:, :V] = _logits(V)[:n]
+    x = buf.to(dev)[:, :V]
+    hist = torch.tensor([0, 31, 32, 123, V - 1], dtype=torch.int32, device=dev)
+    pr = _pack([_row(), _row(0.7, 0, 0.9, 1.0, 5, 3, 1), _row(0.7, 20, 0.9, 1.3, 5, 3, 2, hist), _row()], dev)
+    ones = torch.full(((V + 31) // 32,), -1, dtype=torch.int32, device=dev)
+    zeros = torch.zeros((V, 2), dtype=torch.float32, device=dev)
+    allow = torch.tensor([ones.data_ptr()] * n, dtype=torch.int64, device=dev)
+    adjust = torch.tensor([zeros.data_ptr()] * n, dtype=torch.int64, device=dev)
+    trunc, wm = pack_trunc_rows([None] * n, dev), pack_wm_rows([None] * n, dev)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def call(name, *arrays, outputs):
+        out = torch.full((n,), -7, dtype=torch.int32, device=dev)
+        kept = torch.full((n,), -7, dtype=torch.int32, device=dev) if outputs else None
+        lp = torch.full((n,), 7.0, dtype=torch.float32, device=dev) if outputs else None
+        st = getattr(lib, name)(x.data_ptr(), n, V, ldl, pr.data_ptr(), *(None if a is None else a.data_ptr() for a in arrays), out.data_ptr(),
+                                None if kept is None else kept.data_ptr(), None if lp is None else lp.data_ptr(), stream)
+        assert st == 0, (name, _lib.last_error(lib))
+        return [out.cpu().tolist()] + ([kept.cpu().tolist(), lp.cpu().numpy().view(np.uint32).tolist()] if outputs else [])
+
+    wide = (("vt_sample_rows_allow", (allow,)), ("vt_sample_rows_adj", (allow, adjust)), ("vt_sample_rows_trunc", (allow, adjust, trunc)),
+            ("vt_sample_rows_wm", (allow, adjust, trunc, wm)))
+    for outputs in (False, True):
+        base = call("vt_sample_rows", outputs=outputs)
+        assert all(0 <= i < V for i in base[0]) and [base[0][0], base[0][3]] == _logits(V)[[0, 3]].argmax(-1).tolist(), base
+        for name, neutral in wide:
+            if name != "vt_sample_rows_allow":
+                assert call(name, *[None] * len(neutral), outputs=outputs) == base, (name, "NULL arrays", outputs)
+            if name == "vt_sample_rows_wm" and ldl % 4:
+                continue                                                         # refused below
+            assert call(name, *neutral, outputs=outputs) == base, (name, "neutral arrays", outputs)
+    if ldl % 4:
+        out = torch.empty((n,), dtype=torch.int32, device=dev)
+        st = lib.vt_sample_rows_wm(x.data_ptr(), n, V, ldl, pr.data_ptr(), None, None, None, wm.data_ptr(), out.data_ptr(), None, None, stream)
+        assert st < 0 and (f"vt_sample_rows_wm: V={V} ldl={ldl}: the watermark runs in the register form only (V <= 32768, ldl % 4 == 0, "
+                           "logits 16-byte aligned)") in _lib.last_error(lib), (st, _lib.last_error(lib))
+
+
 def test_bad_calls_return_errors(dev):
     from vitron_amd import _lib, ops
     lib = _lib.load()

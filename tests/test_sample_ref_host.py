@@ -202,6 +202,11 @@ def test_struct_packing_matches_the_header():
             S.sample_rows_array([bad])
 
 
+def test_the_sampler_source_is_built():
+    from vitron_amd import build
+    assert "vt_sample.hip" in build.SOURCES and os.path.exists(os.path.join(ROOT, "vitron_amd", "csrc", "vt_sample.hip"))
+
+
 def test_submit_rejects_bad_sampling_before_queueing():
     from vitron_amd import serving
     from vitron_amd.sampling import SamplingParams

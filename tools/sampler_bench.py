@@ -17,9 +17,15 @@ top-p / MinP / Typical / Epsilon / Eta warpers, a softmax and torch.multinomial 
 
 The arms are alternated inside one process over `--rounds` rounds of `--iters` launches between two device events; per arm the output
 gives every round, the median and the spread (max - min) / median -- two arms are apart only when they differ by more than the spreads.
-`--baseline-lib PATH` adds vt_argmax, vt_sample_top_p and vt_sample_rows of ANOTHER build of libvitron_hip.so (for instance the parent
-commit's) to the same alternation. `--json FILE` writes the table (profiles/sampler_rows_bench.json: the run of DESIGN.md 9.3;
-profiles/sampler_allow_bench.json: the run of 9.4, with the constrained arms).
+`--baseline-lib PATH` adds ANOTHER build of libvitron_hip.so (for instance the parent commit's) to the same alternation: its vt_argmax
+and vt_sample_top_p, and one "baseline raw ..." arm per flavour of the vt_sample_rows kernel beside a "new raw ..." arm of this build, both
+through raw ctypes on the same device arrays -- plain, allow (all rows), adj (a zero adjustment on every row), trunc (all four) and wm
+(depth 30, the array of tools/wm_bench.py; the cells are put back in front of every launch of either arm). Where PATH lies inside a
+vitron_amd package, that package's ops.sample_rows runs beside this one's as well ("baseline ops ..." / "new ops ...": the host cost of
+the Python path). Every such pair is listed under "ab" with its verdict: apart only when the medians differ by more than the largest of
+the two spreads and the spread of "baseline rows sampled (again)". `--json FILE` writes the table (profiles/sampler_rows_bench.json: the
+run of DESIGN.md 9.3; profiles/sampler_allow_bench.json: the run of 9.4, with the constrained arms; profiles/sampler_one_kernel_ab.json:
+the A/B against the parent of the one-kernel sampler, 9.3).
 
   python tools/sampler_bench.py [--rows 4,16] [--iters 200] [--rounds 3] [--baseline-lib path/libvitron_hip.so] [--json out.json]
 """
@@ -48,12 +54,34 @@ args = ap.parse_args()
 _lib.load()
 dev = torch.device("cuda:0")
 V, T, P, SEED, STEP, HIST = 32000, 0.2, 0.7, 1, 2, 2048
-base = None
+base = base_ops = None
 if args.baseline_lib:
     base = C.CDLL(os.path.abspath(args.baseline_lib))
     base.vt_argmax.argtypes = _lib.SIGNATURES["vt_argmax"][1]
     base.vt_sample_top_p.argtypes = _lib.SIGNATURES["vt_sample_top_p"][1]
-    base.vt_sample_rows.argtypes = _lib.SIGNATURES["vt_sample_rows"][1]
+    for name in ("vt_sample_rows", "vt_sample_rows_allow", "vt_sample_rows_adj", "vt_sample_rows_trunc", "vt_sample_rows_wm"):
+        getattr(base, name).argtypes = _lib.SIGNATURES[name][1]
+    pkg_dir = os.path.dirname(os.path.abspath(args.baseline_lib))
+    if os.path.exists(os.path.join(pkg_dir, "ops.py")):       # the library sits in its package: that package's Python path beside this one's
+        import importlib.util
+        spec = importlib.util.spec_from_file_location("vitron_amd_baseline", os.path.join(pkg_dir, "__init__.py"),
+                                                      submodule_search_locations=[pkg_dir])
+        sys.modules["vitron_amd_baseline"] = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(sys.modules["vitron_amd_baseline"])
+        base_ops = importlib.import_module("vitron_amd_baseline.ops")
+
+
+def wm_depth30(rows):
+    """The vt_wm_row array of tools/wm_bench.py's "wm depth 30" arm (ngram_len 5, a 65536-entry table, a history of 1024; even rows fresh,
+    odd rows repeated) and the function that puts its cells back, so that every launch does the same work"""
+    from vitron_amd.watermark import SynthIDWatermark, pack_wm_rows
+    wm = SynthIDWatermark(dict(ngram_len=5, keys=[654, 400, 836, 123, 340, 443, 597, 160, 57, 29, 590, 639, 13, 715, 468, 990, 966, 226, 324, 585,
+                                                  118, 504, 421, 521, 129, 669, 732, 225, 90, 960]))
+    cells = torch.zeros((rows, wm.cell_words), dtype=torch.int64, device=dev)
+    snap = np.zeros((rows, wm.cell_words), dtype=np.uint64)
+    snap[1::2, 12] = wm.context_hash(np.zeros((4,), np.int64))
+    snap = torch.from_numpy(snap.view(np.int64)).to(dev)
+    return pack_wm_rows([(wm, cells[r]) for r in range(rows)], dev), lambda wm=wm: cells.copy_(snap)      # (wm: its device tables stay alive)
 
 
 def time_us(fn):
@@ -70,7 +98,7 @@ def time_us(fn):
 
 
 result = {"V": V, "iters": args.iters, "rounds": args.rounds, "temperature": T, "top_p": P, "history_ids": HIST, "penalty": 1.3,
-          "baseline_lib": bool(base), "device": torch.cuda.get_device_name(0), "shapes": {}}
+          "baseline_lib": bool(base), "device": torch.cuda.get_device_name(0), "shapes": {}, "ab": {}}
 for rows in [int(r) for r in args.rows.split(",")]:
     lg = torch.randn((rows, V), device=dev) * 3
     out = torch.empty((rows,), dtype=torch.int32, device=dev)
@@ -107,9 +135,27 @@ for rows in [int(r) for r in args.rows.split(",")]:
     half_ids = np.flatnonzero(g.random(V) < 0.5)
     arms["step mask upload (16000 ids)"] = lambda: torch.from_numpy(allow_mask(V, half_ids).view(np.int32)).to(dev)
     arms["step mask upload (8 ids)"] = lambda: torch.from_numpy(allow_mask(V, [5, 31, 32, 1023, 1024, 7777, 20000, V - 1]).view(np.int32)).to(dev)
+    lib = _lib.load()
     if base is not None:      # the same parent launch a second time: the spread of repeated parent runs, measured in this run
         arms["baseline rows sampled (again)"] = arms["baseline rows sampled"]
-    lib = _lib.load()
+        # one arm per flavour of the vt_sample_rows kernel, this library against the baseline through raw ctypes on the same device arrays
+        zero_adj = torch.zeros((V, 2), device=dev)
+        all_ptrs, adj_ptrs = ops.allow_pointers(masks, rows, V, dev), ops.adjust_pointers([zero_adj] * rows, rows, V, dev)
+        tr4 = pack_trunc_rows([(0.1, 0.9, 1e-3, 1e-3)] * rows, dev)
+        wm_rows, wm_restore = wm_depth30(rows)
+        flavours = {"rows sampled": ("vt_sample_rows", ()), "allow all rows": ("vt_sample_rows_allow", (all_ptrs,)), "adj zero": ("vt_sample_rows_adj", (None, adj_ptrs)),
+                    "trunc all four": ("vt_sample_rows_trunc", (None, None, tr4)), "wm depth 30": ("vt_sample_rows_wm", (None, None, None, wm_rows))}
+        for label, (entry, arrays) in flavours.items():
+            call = (lg.data_ptr(), rows, V, V, pr_s.data_ptr(), *(a if a is None else a.data_ptr() for a in arrays), out.data_ptr(), None, None,
+                    stream)
+            before = wm_restore if entry == "vt_sample_rows_wm" else (lambda: None)      # every wm launch starts from the same cells
+            for who, l in (("new", lib), ("baseline", base)):
+                arms[f"{who} raw {label}"] = lambda fn=getattr(l, entry), call=call, before=before: (before(), fn(*call))
+        if base_ops is not None:      # ... and the Python path in front of them, this package's against the baseline's
+            for label, kw in (("rows sampled", {}), ("allow all rows", dict(_allow_ptrs=all_ptrs)), ("allow all rows +ptrs", dict(allow=masks)),
+                              ("adj zero +ptrs", dict(adjust=[zero_adj] * rows)), ("trunc all four", dict(trunc=tr4))):
+                for who, o in (("new", ops), ("baseline", base_ops)):
+                    arms[f"{who} ops {label}"] = lambda o=o, kw=kw: o.sample_rows(lg, pr_s, **kw)
     arms["trunc entry, trunc=NULL"] = lambda: lib.vt_sample_rows_trunc(lg.data_ptr(), rows, V, V, pr_s.data_ptr(), None, None, None,
                                                                        out.data_ptr(), None, None, stream)
     stages = {"all inactive": None, "min_p 0.1": (0.1, 1.0, 0.0, 0.0), "typical_p 0.9": (0.0, 0.9, 0.0, 0.0),
@@ -140,6 +186,15 @@ for rows in [int(r) for r in args.rows.split(",")]:
         shape[name] = {"us": [round(t, 2) for t in ts], "median_us": round(med, 2), "spread": round((max(ts) - min(ts)) / med, 4)}
         print(f"rows={rows:2d} {name:36s} {med:8.1f} us   rounds {[f'{t:.1f}' for t in ts]}  spread {shape[name]['spread']:.3f}")
     result["shapes"][f"{rows}x{V}"] = shape
+    # "new X" against "baseline X": apart only beyond the largest of the two spreads and the spread of the repeated parent run
+    again = shape.get("baseline rows sampled (again)", {}).get("spread", 0.0)
+    for name in [n for n in shape if n.startswith("new ") and "baseline " + n[4:] in shape]:
+        new, old = shape[name], shape["baseline " + name[4:]]
+        diff, allowed = (new["median_us"] - old["median_us"]) / old["median_us"], max(new["spread"], old["spread"], again)
+        result["ab"][f"{rows}x{V} {name[4:]}"] = {"new_us": new["median_us"], "baseline_us": old["median_us"], "diff": round(diff, 4),
+                                                  "allowed": allowed, "apart": abs(diff) > allowed}
+        print(f"rows={rows:2d} A/B {name[4:]:28s} new {new['median_us']:8.1f} baseline {old['median_us']:8.1f}  diff {diff:+.3f}  allowed "
+              f"{allowed:.3f}  {'APART' if abs(diff) > allowed else 'same'}")
 if args.json:
     with open(args.json, "w") as f:
         json.dump(result, f, indent=1)

@@ -29,7 +29,7 @@ namespace {
 // The blend, every step rounded to nearest on its own: __fsub_rn / __fmul_rn / __fadd_rn in the header's statement of the contract.
 // hipcc compiles those intrinsics as plain operators that carry its default contraction flag, so after inlining it fuses
 // ul + s * d into an fma all the same (seen in the assembly: v_fmac_f32); the operators are therefore written out under
-// fp contract(off), as vt_llama.hip's add_rounded is, which is what keeps the product and the sum apart.
+// fp contract(off), as vt_sample.hip's add_rounded is, which is what keeps the product and the sum apart.
 __device__ __forceinline__ float cfg_blend(float c, float u, float lse_c, float lse_u, float scale) {
 #pragma clang fp contract(off)
   const float cl = c - lse_c;

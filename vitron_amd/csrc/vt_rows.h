@@ -1,5 +1,5 @@
 // vt_rows.h -- the block primitives of the row kernels: kernels that run ONE 1024-thread block (16 waves) per fp32
-// logit row -- vt_argmax, the samplers and the cross entropy (vt_llama.hip), vt_beam_step's stage 1, vt_logprob_rows, vt_cfg_rows,
+// logit row -- vt_argmax and the cross entropy (vt_llama.hip), the samplers (vt_sample.hip), vt_beam_step's stage 1, vt_logprob_rows, vt_cfg_rows,
 // vt_dola_rows.
 // Device only. These kernels' outputs are pinned bit for bit and several contracts are stated in terms of one another ("the lse is
 // vt_logprob_rows' expression", "the mask follows vt_cfg_rows' layout"): this header is the one statement they all share, so the order
@@ -75,7 +75,7 @@ __device__ __forceinline__ int row_block_count(int c, int* sh) {
 //     candidate; `ok` gates the candidate. vt_logprob_rows.
 //   RowTakeIf, the branch form. vt_beam_step (with selects the compiler keeps a scan's 32 unrolled candidates live at once:
 //     beam_rows_kernel<true> 80 -> 102 VGPRs, 6 -> 4 waves per SIMD), vt_argmax (13 -> 23 VGPRs) and the samplers' greedy rows
-//     (sample_rows_adj_kernel<true>: 16 -> 20 bytes of scratch).
+//     (the register form of vt_sample_rows_adj: 16 -> 20 bytes of scratch).
 struct RowTake {
   __device__ __forceinline__ void operator()(float& best, int& bi, float v, int i, bool ok = true) const {
     const bool t = ok & ((v > best) | ((v == best) & (i < bi)));

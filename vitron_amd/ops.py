@@ -619,44 +619,36 @@ def sample_top_p(logits: torch.Tensor, temperature: float, top_p: float, seed: i
     return (out, kept) if return_kept else out
 
 
+def _row_pointers(what: str, entries, rows: int, device, kind: str, ok, want: str) -> torch.Tensor:
+    """int64 [rows] on `device`: the data pointer of each entry, 0 for None. Every other entry is a contiguous tensor on `device` that
+    passes ok(); `kind` and `want` word the two refusals. One small host -> device copy."""
+    if isinstance(entries, torch.Tensor) or not hasattr(entries, "__len__") or len(entries) != rows:
+        raise _lib.VitronHipError(f"sample_rows.{what}: expected a sequence of {rows} entries (one per row), each None or {kind}")
+    ptrs = []
+    for i, m in enumerate(entries):
+        if m is not None and not (isinstance(m, torch.Tensor) and m.device == device and m.is_contiguous() and ok(m)):
+            raise _lib.VitronHipError(f"sample_rows.{what}[{i}]: expected None or {want} on the logits' device")
+        ptrs.append(0 if m is None else m.data_ptr())
+    return torch.tensor(ptrs, dtype=torch.int64).to(device)
+
+
 def allow_pointers(allow, rows: int, V: int, device) -> torch.Tensor:
     """The device pointer array vt_sample_rows_allow reads (int64 [rows]) from one entry per row: None (NULL: everything allowed) or a
     contiguous int32 / uint32 device tensor of ceil(V / 32) mask words (sampling.allow_mask). The caller keeps the masks alive until
     the launch has run. One small host -> device copy."""
     words = (V + 31) // 32
-    if isinstance(allow, torch.Tensor) or not hasattr(allow, "__len__") or len(allow) != rows:
-        raise _lib.VitronHipError(f"sample_rows.allow: expected a sequence of {rows} entries (one per row), each None or a mask tensor")
     mask_dtypes = tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)
-    ptrs = []
-    for i, m in enumerate(allow):
-        if m is None:
-            ptrs.append(0)
-            continue
-        if not isinstance(m, torch.Tensor) or m.device != device or m.dtype not in mask_dtypes or not m.is_contiguous() \
-                or m.numel() != words:
-            raise _lib.VitronHipError(f"sample_rows.allow[{i}]: expected None or a contiguous int32 / uint32 tensor of {words} words "
-                                      f"(ceil(V / 32), V = {V}) on the logits' device")
-        ptrs.append(m.data_ptr())
-    return torch.tensor(ptrs, dtype=torch.int64).to(device)
+    return _row_pointers("allow", allow, rows, device, "a mask tensor", lambda m: m.dtype in mask_dtypes and m.numel() == words,
+                         f"a contiguous int32 / uint32 tensor of {words} words (ceil(V / 32), V = {V})")
 
 
 def adjust_pointers(adjust, rows: int, V: int, device) -> torch.Tensor:
     """The device pointer array vt_sample_rows_adj reads (int64 [rows]) from one entry per row: None (NULL: no adjustment) or a
     contiguous fp32 device tensor of 2 * V elements, the (pre, post) pairs ops.bias_rows writes. The caller keeps the buffers alive until
     the launch has run. One small host -> device copy."""
-    if isinstance(adjust, torch.Tensor) or not hasattr(adjust, "__len__") or len(adjust) != rows:
-        raise _lib.VitronHipError(f"sample_rows.adjust: expected a sequence of {rows} entries (one per row), each None or an fp32 tensor")
-    ptrs = []
-    for i, m in enumerate(adjust):
-        if m is None:
-            ptrs.append(0)
-            continue
-        if not isinstance(m, torch.Tensor) or m.device != device or m.dtype != torch.float32 or not m.is_contiguous() \
-                or m.numel() != 2 * V or m.data_ptr() % 8:
-            raise _lib.VitronHipError(f"sample_rows.adjust[{i}]: expected None or a contiguous, 8-byte aligned fp32 tensor of {2 * V} "
-                                      f"elements ([V][2], V = {V}) on the logits' device")
-        ptrs.append(m.data_ptr())
-    return torch.tensor(ptrs, dtype=torch.int64).to(device)
+    return _row_pointers("adjust", adjust, rows, device, "an fp32 tensor",
+                         lambda m: m.dtype == torch.float32 and m.numel() == 2 * V and m.data_ptr() % 8 == 0,
+                         f"a contiguous, 8-byte aligned fp32 tensor of {2 * V} elements ([V][2], V = {V})")
 
 
 def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = False, return_logprob: bool = False, allow=None,
@@ -708,36 +700,23 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = 
                                   or watermark.numel() != rows * WM_ROW_BYTES):
         raise _lib.VitronHipError(f"sample_rows.watermark: expected a contiguous uint8 tensor of {rows} x {WM_ROW_BYTES} bytes on the "
                                   "logits' device (watermark.pack_wm_rows)")
-    if watermark is not None or trunc is not None or adjust is not None or _adjust_ptrs is not None:
-        aptrs = None
-        if _allow_ptrs is not None:
-            aptrs = given_ptrs(_allow_ptrs, "_allow_ptrs")
-        elif allow is not None:
-            aptrs = allow_pointers(allow, rows, V, logits.device)
-        jptrs = None
-        if _adjust_ptrs is not None:
-            jptrs = given_ptrs(_adjust_ptrs, "_adjust_ptrs")
-        elif adjust is not None:
-            jptrs = adjust_pointers(adjust, rows, V, logits.device)
-        if watermark is not None:
-            _lib.check(lib.vt_sample_rows_wm(_p(logits), rows, V, logits.stride(0), _p(params), _p(aptrs), _p(jptrs), _p(trunc),
-                                             _p(watermark), _p(out), _p(kept), _p(lp), _stream()), "vt_sample_rows_wm", lib)
-        elif trunc is not None:
-            _lib.check(lib.vt_sample_rows_trunc(_p(logits), rows, V, logits.stride(0), _p(params), _p(aptrs), _p(jptrs), _p(trunc), _p(out),
-                                                _p(kept), _p(lp), _stream()), "vt_sample_rows_trunc", lib)
-        else:
-            _lib.check(lib.vt_sample_rows_adj(_p(logits), rows, V, logits.stride(0), _p(params), _p(aptrs), _p(jptrs), _p(out), _p(kept),
-                                              _p(lp), _stream()), "vt_sample_rows_adj", lib)
-    elif allow is None and _allow_ptrs is None:
-        _lib.check(lib.vt_sample_rows(_p(logits), rows, V, logits.stride(0), _p(params), _p(out), _p(kept), _p(lp), _stream()),
-                   "vt_sample_rows", lib)
+    aptrs = given_ptrs(_allow_ptrs, "_allow_ptrs") if _allow_ptrs is not None else \
+        None if allow is None else allow_pointers(allow, rows, V, logits.device)
+    jptrs = given_ptrs(_adjust_ptrs, "_adjust_ptrs") if _adjust_ptrs is not None else \
+        None if adjust is None else adjust_pointers(adjust, rows, V, logits.device)
+    # the narrowest entry point that carries what was given: error texts name it, and the library picks the kernel by the same rule
+    if watermark is not None:
+        name, extra = "vt_sample_rows_wm", (aptrs, jptrs, trunc, watermark)
+    elif trunc is not None:
+        name, extra = "vt_sample_rows_trunc", (aptrs, jptrs, trunc)
+    elif jptrs is not None:
+        name, extra = "vt_sample_rows_adj", (aptrs, jptrs)
+    elif aptrs is not None:
+        name, extra = "vt_sample_rows_allow", (aptrs,)
     else:
-        if _allow_ptrs is not None:
-            ptrs = given_ptrs(_allow_ptrs, "_allow_ptrs")
-        else:
-            ptrs = allow_pointers(allow, rows, V, logits.device)
-        _lib.check(lib.vt_sample_rows_allow(_p(logits), rows, V, logits.stride(0), _p(params), _p(ptrs), _p(out), _p(kept), _p(lp),
-                                            _stream()), "vt_sample_rows_allow", lib)
+        name, extra = "vt_sample_rows", ()
+    _lib.check(getattr(lib, name)(_p(logits), rows, V, logits.stride(0), _p(params), *map(_p, extra), _p(out), _p(kept), _p(lp),
+                                  _stream()), name, lib)
     res = (out,) + ((kept,) if return_kept else ()) + ((lp,) if return_logprob else ())
     return res if len(res) > 1 else out
 
