@@ -113,6 +113,8 @@ enum { VT_ACT_GELU = 0, VT_ACT_QUICK_GELU = 1 };
  * changes; vt_gemm_plan_query and vt_gemm_plan_query2 return what they returned, and vt_gemm_bf16 stores what it stored, bit for bit. */
 /* 114 also carries vt_sample_rows_wm and struct vt_wm_row WITHOUT a bump (with vt_wm_cell_words): two new symbols and one new struct;
  * struct vt_sample_row, struct vt_trunc_row and the four vt_sample_rows* entry points do not change. */
+/* 114 also carries vt_sample_rows_miro and struct vt_miro_row WITHOUT a bump: one new symbol and one new struct; struct vt_sample_row,
+ * struct vt_trunc_row, struct vt_wm_row and the five vt_sample_rows* entry points do not change. */
 #define VT_ABI_VERSION 114
 int vt_version(void); /* == VT_ABI_VERSION of the header the library was built from */
 /* operand format of THIS library (see Conventions): every uint16_t tensor argument carries these bits */
@@ -695,6 +697,50 @@ int vt_sample_rows_wm(const float* logits, int rows, int V, int ldl, const vt_sa
                       const vt_trunc_row* trunc /* DEVICE array [rows], or NULL */,
                       const vt_wm_row* wm /* DEVICE array [rows], or NULL */,
                       int* out_ids, int* kept_count, float* logprob, void* stream);
+
+/* vt_sample_rows_trunc with PER-ROW MIROSTAT v2: the adaptive truncation of Basu et al., "Mirostat: A Neural Text
+ * Decoding Algorithm that Directly Controls Perplexity" (ICLR 2021), in the form of llama.cpp's mirostat_v2 sampler (`--mirostat 2`): a
+ * cutoff mu on the surprise of a token moves after every pick so that the surprise of the emitted text stays near a target tau. It
+ * stands behind the truncation stages. miro: DEVICE array of `rows` vt_miro_row (16 bytes each, 8-byte aligned; the offsets are part of
+ * the ABI):
+ *   @0  float* cell     DEVICE state of this sequence, two fp32 words {mu, last_surprise}, 8-byte aligned; NULL: the row runs no Mirostat
+ *   @8  float tau       the target surprise in bits; <= 0 (or NaN): the row runs no Mirostat
+ *   @12 float eta       the learning rate, >= 0
+ * A fresh cell is {2 * tau, 0}, written by the host once; after that only the kernel writes it. Per sampled row with tau > 0 and a cell,
+ * where p holds the kept probabilities of vt_sample_rows_trunc (0 elsewhere) and `kept` their sum:
+ *   1. q_v = p_v / kept (p_v times the fp32 reciprocal of kept); s_v = -log2f(q_v) for q_v > 0 (the accurate log2f).
+ *   2. token v survives iff s_v <= mu. The most probable kept token always survives: when its own surprise exceeds mu (or mu is a NaN)
+ *      it is the only survivor, the first index on a tie (the (value, index) order of the greedy rows).
+ *   3. kept2 = the sum of the surviving q_v; the draw is vt_sample_rows' inverse CDF over the survivors in index order, the row's
+ *      uniform (seed, counter, stream) scaled by kept2. No new random number is drawn.
+ *   4. e = -log2f(q_x / kept2) for the drawn id x (a correctly rounded divide), mu <- mu - eta * (e - tau) with the difference, the
+ *      product and the last difference each rounded on its own (no fma); the cell becomes {mu, e}. This is the only write, by one
+ *      thread, behind every read of the cell. A row that draws nothing (id < 0: nothing was kept) leaves its cell as it is.
+ *   5. kept_count reports the survivors of step 2; logprob stays over the RAW row.
+ * `kept` and kept2 are tree sums: 32 consecutive slots of a thread serially, 6 shuffle levels over a wave, then the 16 wave totals in
+ * wave order; the maximum of step 2 is taken over the same tree. mu is data only: whatever a cell holds indexes nothing.
+ * A greedy row (temperature not > 0) ignores its entry and does not touch its cell; a row with tau <= 0 or a NULL cell returns, bit for
+ * bit, what vt_sample_rows_trunc returns for it; miro == NULL is the vt_sample_rows_trunc launch itself. allow, adjust and trunc may each
+ * be NULL. llama.cpp skips top-k and top-p when Mirostat is on; here every stage in front keeps working, and a caller who wants
+ * llama.cpp's behaviour leaves them off. Mirostat v1 and Mirostat together with the watermark (vt_sample_rows_wm) are not built.
+ * The register form only: with miro != NULL a launch that vt_sample_rows would run in the streaming form (V > 32768, ldl % 4 != 0, logits
+ * not 16-byte aligned) is refused with VT_STATUS_ARG and a message. Refused likewise, before any launch: miro not 8-byte aligned, and for
+ * a row with a cell a cell that is not 8-byte aligned, a tau or eta that is not finite, eta < 0. For that the array is read back on
+ * `stream` in front of the launch (rows * 16 bytes and a wait for the copy); on a stream that is being captured it is not, and the kernel
+ * treats an entry it would have refused as a row without Mirostat.
+ * 114 carries vt_sample_rows_miro and struct vt_miro_row WITHOUT a bump: one new symbol and one new struct, nothing existing changes (see
+ * the note at VT_ABI_VERSION). */
+typedef struct vt_miro_row {
+  float* cell;
+  float tau;
+  float eta;
+} vt_miro_row;
+int vt_sample_rows_miro(const float* logits, int rows, int V, int ldl, const vt_sample_row* params,
+                        const uint32_t* const* allow /* DEVICE array of `rows` device pointers, entries and the array may be NULL */,
+                        const float* const* adjust /* DEVICE array of `rows` device pointers to fp32 [V][2], entries and the array may be NULL */,
+                        const vt_trunc_row* trunc /* DEVICE array [rows], or NULL */,
+                        const vt_miro_row* miro /* DEVICE array [rows], or NULL */,
+                        int* out_ids, int* kept_count, float* logprob, void* stream);
 
 /* BEAM SEARCH (the role of transformers' GenerationMixin beam search: log_softmax + running scores + torch.topk over
  * num_beams * vocab, and the cache reorder behind it).

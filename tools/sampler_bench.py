@@ -15,6 +15,14 @@ vt_sample_rows launch itself) and with all-inactive rows (the trunc kernel, stag
 alone and all four. "host warpers" is what the feature replaces: the [rows, V] fp32 logits read back and transformers' temperature /
 top-p / MinP / Typical / Epsilon / Eta warpers, a softmax and torch.multinomial on the CPU.
 
+The Mirostat arms (vt_sample_rows_miro) run the all-sampled batch through raw ctypes: "miro tau 5" (every row on Mirostat,
+tau 5, eta 0.1, no truncation) beside "trunc all inactive +restore", and "miro tau 5 + all four" beside "trunc all four +restore", on the
+same rows. A Mirostat launch moves its cells, so every launch of these four arms is preceded by the same 8 * rows-byte copy that puts the
+cells back ("+restore": the trunc arms pay it too, so that a pair differs by the kernel and its read-back of the array alone).
+"miro cells NULL" is the entry point with an array whose every cell is NULL: the read-back of the array and the kMiro kernel with its
+stage off, so "miro cells NULL" less "trunc all inactive +restore" is what the validation costs and "miro tau 5" less "miro cells NULL"
+what the stage costs. "miro entry, miro=NULL" is the vt_sample_rows_trunc launch itself. profiles/miro_bench.json is the run of DESIGN.md 9.17.
+
 The arms are alternated inside one process over `--rounds` rounds of `--iters` launches between two device events; per arm the output
 gives every round, the median and the spread (max - min) / median -- two arms are apart only when they differ by more than the spreads.
 `--baseline-lib PATH` adds ANOTHER build of libvitron_hip.so (for instance the parent commit's) to the same alternation: its vt_argmax
@@ -158,6 +166,22 @@ for rows in [int(r) for r in args.rows.split(",")]:
                     arms[f"{who} ops {label}"] = lambda o=o, kw=kw: o.sample_rows(lg, pr_s, **kw)
     arms["trunc entry, trunc=NULL"] = lambda: lib.vt_sample_rows_trunc(lg.data_ptr(), rows, V, V, pr_s.data_ptr(), None, None, None,
                                                                        out.data_ptr(), None, None, stream)
+    # Mirostat beside the truncation launch on the same rows; the cells are put back in front of every launch of the four arms
+    from vitron_amd.sampling import pack_miro_rows
+    miro_cells = torch.tensor([[10.0, 0.0]] * rows, dtype=torch.float32).to(dev)
+    miro_snap = miro_cells.clone()
+    miro_rows = pack_miro_rows([(miro_cells[r], 5.0, 0.1) for r in range(rows)], dev)
+    tr_off, tr_all = pack_trunc_rows([None] * rows, dev), pack_trunc_rows([(0.1, 0.9, 1e-3, 1e-3)] * rows, dev)
+    head = (lg.data_ptr(), rows, V, V, pr_s.data_ptr(), None, None)
+    tail = (out.data_ptr(), None, None, stream)
+    for label, tr in (("all inactive", tr_off), ("all four", tr_all)):
+        arms[f"trunc {label} +restore"] = lambda tr=tr: (miro_cells.copy_(miro_snap), lib.vt_sample_rows_trunc(*head, tr.data_ptr(), *tail))
+    arms["miro tau 5"] = lambda: (miro_cells.copy_(miro_snap), lib.vt_sample_rows_miro(*head, None, miro_rows.data_ptr(), *tail))
+    arms["miro tau 5 + all four"] = lambda: (miro_cells.copy_(miro_snap),
+                                             lib.vt_sample_rows_miro(*head, tr_all.data_ptr(), miro_rows.data_ptr(), *tail))
+    miro_null = pack_miro_rows([None] * rows, dev)
+    arms["miro cells NULL"] = lambda: (miro_cells.copy_(miro_snap), lib.vt_sample_rows_miro(*head, None, miro_null.data_ptr(), *tail))
+    arms["miro entry, miro=NULL"] = lambda: lib.vt_sample_rows_miro(*head, tr_all.data_ptr(), None, *tail)
     stages = {"all inactive": None, "min_p 0.1": (0.1, 1.0, 0.0, 0.0), "typical_p 0.9": (0.0, 0.9, 0.0, 0.0),
               "epsilon 1e-3": (0.0, 1.0, 1e-3, 0.0), "eta 1e-3": (0.0, 1.0, 0.0, 1e-3), "all four": (0.1, 0.9, 1e-3, 1e-3)}
     for label, t in stages.items():
@@ -186,6 +210,12 @@ for rows in [int(r) for r in args.rows.split(",")]:
         shape[name] = {"us": [round(t, 2) for t in ts], "median_us": round(med, 2), "spread": round((max(ts) - min(ts)) / med, 4)}
         print(f"rows={rows:2d} {name:36s} {med:8.1f} us   rounds {[f'{t:.1f}' for t in ts]}  spread {shape[name]['spread']:.3f}")
     result["shapes"][f"{rows}x{V}"] = shape
+    for a_name, b_name in (("miro tau 5", "trunc all inactive +restore"), ("miro tau 5 + all four", "trunc all four +restore")):
+        result.setdefault("miro", {})[f"{rows}x{V} {a_name}"] = {
+            "miro_us": shape[a_name]["median_us"], "trunc_us": shape[b_name]["median_us"],
+            "added_us": round(shape[a_name]["median_us"] - shape[b_name]["median_us"], 2),
+            "cells_null_us": shape["miro cells NULL"]["median_us"]}
+        print(f"rows={rows:2d} {a_name:24s} {shape[a_name]['median_us']:8.1f} us beside {b_name} {shape[b_name]['median_us']:8.1f} us")
     # "new X" against "baseline X": apart only beyond the largest of the two spreads and the spread of the repeated parent run
     again = shape.get("baseline rows sampled (again)", {}).get("spread", 0.0)
     for name in [n for n in shape if n.startswith("new ") and "baseline " + n[4:] in shape]:

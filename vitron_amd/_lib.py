@@ -123,6 +123,7 @@ SIGNATURES = {
     "vt_sample_rows_adj": (_i, [vp, _i, _i, _i, vp, vp, vp, vp, vp, vp, vp]),
     "vt_sample_rows_trunc": (_i, [vp, _i, _i, _i, vp, vp, vp, vp, vp, vp, vp, vp]),
     "vt_sample_rows_wm": (_i, [vp, _i, _i, _i, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "vt_sample_rows_miro": (_i, [vp, _i, _i, _i, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "vt_wm_cell_words": (_sz, [_i]),
     "vt_beam_step_scratch_bytes": (_sz, [_i, _i, _i]),
     "vt_beam_step": (_i, [vp, _i, _i, _i, _i, vp, _i, vp, vp, vp, vp, _sz, vp]),

@@ -501,6 +501,12 @@ int vt_sample_rows_wm(const float* logits, int rows, int V, int ldl, const vt_sa
 
 size_t vt_wm_cell_words(int history_size) { return 12 + (size_t)(history_size > 0 ? history_size : 0); }
 
+int vt_sample_rows_miro(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, const uint32_t* const* allow,
+                        const float* const* adjust, const vt_trunc_row* trunc, const vt_miro_row* miro, int* out_ids, int* kept_count,
+                        float* logprob, void* stream) {
+  return vt_sample_rows_launch(logits, rows, V, ldl, params, allow, out_ids, kept_count, logprob, S(stream), adjust, trunc, nullptr, miro);
+}
+
 // ---- beam search (vt_beam.hip) ----------------------------------------------------------------------------------------
 size_t vt_beam_step_scratch_bytes(int groups, int beams_in, int n_out) { return vt_beam_step_scratch_bytes_impl(groups, beams_in, n_out); }
 

@@ -272,7 +272,8 @@ int vt_sample_rows_launch(const float* logits, int rows, int V, int ldl, const v
                           int* out_ids, int* kept_count, float* logprob, hipStream_t s,    // allow == NULL: vt_sample_rows
                           const float* const* adjust = nullptr,                            // adjust != NULL: vt_sample_rows_adj
                           const vt_trunc_row* trunc = nullptr,                             // trunc != NULL: vt_sample_rows_trunc
-                          const vt_wm_row* wm = nullptr);                                  // wm != NULL: vt_sample_rows_wm
+                          const vt_wm_row* wm = nullptr,                                   // wm != NULL: vt_sample_rows_wm
+                          const vt_miro_row* miro = nullptr);                              // miro != NULL: vt_sample_rows_miro (wm NULL)
 
 // ---- vt_beam.hip ----------------------------------------------------------------------------------
 size_t vt_beam_step_scratch_bytes_impl(int groups, int beams_in, int n_out);

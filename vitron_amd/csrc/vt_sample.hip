@@ -5,6 +5,7 @@
 #include "vt_kernels.h"
 #include "vt_rows.h"
 
+#include <cmath>
 #include <vector>
 
 namespace {
@@ -67,6 +68,15 @@ __device__ __forceinline__ float penalise(float x, float penalty) { return x < 0
 __device__ __forceinline__ float add_rounded(float x, float y) {
 #pragma clang fp contract(off)
   return x + y;
+}
+
+// kMiro (vt_sample_rows_miro): one step of the cutoff, mu - eta * (e - tau), every operation rounded on its own (hipcc
+// would contract the product and the difference into an fma): the test recomputes it bit for bit from the cell's own e
+__device__ __forceinline__ float miro_step(float mu, float eta, float e, float tau) {
+#pragma clang fp contract(off)
+  const float d = e - tau;
+  const float g = eta * d;
+  return mu - g;
 }
 
 // kTrunc (vt_sample_rows_trunc): MinP / Typical / Epsilon / Eta warpers on the survivors of top-k and top-p. Both bodies
@@ -362,12 +372,20 @@ __device__ __forceinline__ void sample_stream_body(const float* __restrict__ row
 // staged into LDS (`wm_tab`, table_size / 32 words, with the low words of layer_add behind it). The sequence's state (struct vt_wm_row's cell) is read by every thread and written
 // by thread 0 alone, behind the last barrier. cnt is not recounted: kept_count stays the truncation's survivors. wm == NULL
 // (block-uniform: a row without a cell) runs nothing of this: p, mine and cnt are the kTrunc body's.
-template <bool kRows, bool kAllow = false, bool kAdj = false, bool kTrunc = false, bool kWm = false>
+// kMiro (vt_sample_rows_miro): Mirostat v2 (Basu et al., ICLR 2021; llama.cpp's mirostat_v2), behind kTrunc and without
+// kWm: where p holds the kept probabilities, q = p / kept replaces it, a slot whose surprise -log2f(q) exceeds the cell's mu is zeroed
+// (when the maximum's own surprise exceeds mu, every slot but the first index of the maximum), cnt is recounted and the walk draws over
+// sum(q) with the uniform it always had. One block sum (kept), one block maximum, one pass over the registers; the arg-max pass runs
+// only where nothing survives. The cell {mu, last_surprise} is read by every thread in front of the stage's barriers and written behind the last
+// barrier by the one thread that owns the drawn slot: it still holds q_x, so nothing is parked in LDS. mu is compared, never used as an
+// index. miro == NULL (block-uniform: a row without a cell or with tau <= 0) runs nothing of this: p, mine and cnt are the kTrunc body's.
+template <bool kRows, bool kAllow = false, bool kAdj = false, bool kTrunc = false, bool kWm = false, bool kMiro = false>
 __device__ __forceinline__ void sample_reg_body(const float* __restrict__ row, int V, const SampleArgs& a, uint32_t* seen,
                                                 int* __restrict__ out_id, int* __restrict__ kept_out, float* __restrict__ logprob,
                                                 const uint32_t* __restrict__ allow = nullptr, const float* __restrict__ adj = nullptr,
                                                 vt_trunc_row tr = vt_trunc_row{}, const vt_wm_row* __restrict__ wm = nullptr,
-                                                uint32_t* wm_tab = nullptr) {
+                                                uint32_t* wm_tab = nullptr, const vt_miro_row* miro = nullptr) {
+  static_assert(!(kWm && kMiro), "sample_reg_body: Mirostat together with the watermark is not built");
   constexpr int NPT = 32;
   __shared__ float sh[2][16];
   __shared__ float sh_scan[16];
@@ -677,6 +695,42 @@ __device__ __forceinline__ void sample_reg_body(const float* __restrict__ row, i
       }
     }
   }
+  bool miro_on = false;    // (kMiro; block-uniform) the stage ran: the cell is written behind the draw
+  if constexpr (kMiro) {
+    if (miro) {          // block-uniform
+      const float kept_p = block_sum(mine);
+      if (kept_p > 0.f) {
+        miro_on = true;
+        const float mu = miro->cell[0];           // (every thread's read lies in front of the barriers below; the write is behind the last)
+        const float inv = 1.f / kept_p;
+        float top = 0.f;
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) {
+          p[j] *= inv;
+          top = fmaxf(top, p[j]);
+        }
+        top = block_max(top);
+        if (-log2f(top) <= mu) {                  // block-uniform. The maximum survives, and with it every slot that equals it
+#pragma unroll
+          for (int j = 0; j < NPT; ++j) p[j] = (p[j] > 0.f && -log2f(p[j]) <= mu) ? p[j] : 0.f;
+        } else {         // (a NaN mu too) nothing survives on its own: the first index of the maximum alone. Indices < 2^15 are exact in fp32
+          float first = -INFINITY;
+#pragma unroll
+          for (int j = NPT - 1; j >= 0; --j) first = p[j] == top ? -(float)(i0 + j) : first;
+          first = block_max(first);
+#pragma unroll
+          for (int j = 0; j < NPT; ++j) p[j] = -(float)(i0 + j) == first ? p[j] : 0.f;
+        }
+        mine = 0.f;
+        cnt = 0.f;
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) {
+          mine += p[j];
+          cnt += p[j] > 0.f ? 1.f : 0.f;
+        }
+      }
+    }
+  }
   const float kept = block_sum(mine);
   cnt = block_sum(cnt);
   if (tid == 0) {
@@ -713,7 +767,7 @@ __device__ __forceinline__ void sample_reg_body(const float* __restrict__ row, i
   __syncthreads();
   if (chosen < 0 && mine > 0.f) {  // u landed on a rounding seam: take the last kept token of the highest owning range
     int last = -1;
-    if constexpr (kWm) {   // the slot, not the id: the 32 ids i0 + j of the loads are not kept across the body for this rare path
+    if constexpr (kWm || kMiro) {   // the slot, not the id: the 32 ids i0 + j of the loads are not kept across the body for this rare path
 #pragma unroll
       for (int j = 0; j < NPT; ++j)
         if (p[j] > 0.f) last = j;
@@ -726,6 +780,22 @@ __device__ __forceinline__ void sample_reg_body(const float* __restrict__ row, i
     atomicMax(&chosen, last);
   }
   __syncthreads();
+  if constexpr (kMiro) {
+    if (miro_on) {       // block-uniform. The owner of the drawn slot holds q_x; the cell has this one writer
+      const int id = chosen;
+      if (id >= 0 && id / NPT == tid) {
+        float qx = 0.f;
+#pragma unroll
+        for (int j = 0; j < NPT; ++j) qx = (id % NPT) == j ? p[j] : qx;
+        float* cell = miro->cell;
+        const float e = -log2f(__fdiv_rn(qx, kept));
+        float2 next;
+        next.x = miro_step(cell[0], miro->eta, e, miro->tau);
+        next.y = e;
+        *(float2*)cell = next;
+      }
+    }
+  }
   if (tid == 0) {
     const int id = chosen;
     *out_id = id;
@@ -789,14 +859,21 @@ __device__ __forceinline__ bool wm_row_ok(const vt_wm_row& w) {
          && w.history_size <= VT_WM_MAX_HISTORY;
 }
 
-// The vt_sample_rows family is ONE kernel in two forms (kReg: the register body, else the streaming one) and five flavours. A flavour is
-// the highest per-row array the launch carries, and holds every flavour below it:
+// A Mirostat entry the launcher would have refused (see wm_row_ok), or one that is off (tau <= 0, a NULL cell), is a row without Mirostat.
+__device__ __forceinline__ bool miro_row_ok(const vt_miro_row& m) {
+  return m.cell && ((uintptr_t)m.cell % 8) == 0 && m.tau > 0.f && m.tau < INFINITY && m.eta >= 0.f && m.eta < INFINITY;
+}
+
+// The vt_sample_rows family is ONE kernel in two forms (kReg: the register body, else the streaming one) and six flavours. A flavour is
+// the highest per-row array the launch carries, and holds every flavour below it (kMiro holds kTrunc and below: not kWm):
 //   kPlain  vt_sample_rows        params[r] alone
 //   kAllow  vt_sample_rows_allow  + allow[r]: the row's allow mask, ceil(V/32) words in global memory in both forms (the LDS is kPlain's)
 //   kAdj    vt_sample_rows_adj    + adjust[r]: the row's additive adjustment, fp32 [V][2]
 //   kTrunc  vt_sample_rows_trunc  + trunc[r]: min_p, typical_p, epsilon_cutoff, eta_cutoff
 //   kWm     vt_sample_rows_wm     + wm[r]: the SynthID watermark, with wm_tab as its LDS. The register form only: the
 //                                 streaming body keeps no per-token state across the rounds.
+//   kMiro   vt_sample_rows_miro   kTrunc + miro[r]: Mirostat v2. The register form only: the stage works on the row's
+//                                 q in registers. Without kWm: the two together are not built.
 // The array that selects the flavour is not NULL (the launcher chose the flavour by it) and is read as it is; every array BELOW it may be
 // NULL and is tested -- adjustments without masks, a watermark without truncation. An ENTRY allow[r] / adjust[r] may be NULL in every
 // flavour (everything allowed / no adjustment); a wm[r] whose cell is NULL is a row without a watermark. An instantiation reads only the
@@ -805,7 +882,7 @@ __device__ __forceinline__ bool wm_row_ok(const vt_wm_row& w) {
 // the register form of kTrunc grew by 4 % in instructions. `allow` stands beside `params`, the other arrays LAST in the
 // flavours' order: what kPlain, kAllow and kAdj read lies within one 64-byte line of the kernel-argument segment, and kAllow's
 // arguments lie where a kernel with allow alone would have them (its register form compiles to that kernel's code).
-enum : int { kPlain, kAllow, kAdj, kTrunc, kWm, kFlavours };
+enum : int { kPlain, kAllow, kAdj, kTrunc, kWm, kMiro, kFlavours };
 template <bool kReg, bool... kFlags, class... Extra>
 __device__ __forceinline__ void sample_rows_body(const float* __restrict__ row, int V, const SampleArgs& a, uint32_t* seen,
                                                  int* __restrict__ out_id, int* __restrict__ kept, float* __restrict__ lp, Extra... extra) {
@@ -820,9 +897,11 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
                                                            const uint32_t* const* __restrict__ allow, int* __restrict__ out_ids,
                                                            int* __restrict__ kept_count, float* __restrict__ logprob,
                                                            const float* const* __restrict__ adjust,
-                                                           const vt_trunc_row* __restrict__ trunc, const vt_wm_row* __restrict__ wm) {
+                                                           const vt_trunc_row* __restrict__ trunc, const vt_wm_row* __restrict__ wm,
+                                                           const vt_miro_row* __restrict__ miro) {
   static_assert(kFlavour >= kPlain && kFlavour < kFlavours, "sample_rows_kernel: unknown flavour");
   static_assert(kReg || kFlavour != kWm, "sample_rows_kernel: the watermark runs in the register form only");
+  static_assert(kReg || kFlavour != kMiro, "sample_rows_kernel: Mirostat runs in the register form only");
   __shared__ uint32_t seen[(kReg ? 32 * 1024 : kSampleRowsMaxV) / 32];
   const int r = blockIdx.x;
   SampleArgs a = row_args(params[r]);
@@ -850,6 +929,11 @@ __global__ __launch_bounds__(1024) void sample_rows_kernel(const float* __restri
     a.greedy = false;
     if constexpr (kFlavour == kTrunc) {
       sample_rows_body<kReg, true, true, true>(row, V, a, seen, out_id, kept, lp, mask, adj, trunc[r]);
+    } else if constexpr (kFlavour == kMiro) {
+      const vt_miro_row* m = miro + r;
+      if (!miro_row_ok(*m)) m = nullptr;
+      sample_reg_body<true, true, true, true, false, true>(row, V, a, seen, out_id, kept, lp, mask, adj, trunc ? trunc[r] : vt_trunc_row{},
+                                                           nullptr, nullptr, m);
     } else {
       __shared__ __attribute__((aligned(8))) uint32_t wm_tab[kWmLdsWords];
       const vt_wm_row* w = wm + r;
@@ -905,9 +989,29 @@ static int wm_rows_check(const vt_wm_row* wm, int rows, hipStream_t s) {
   return VT_OK;
 }
 
+// vt_sample_rows_miro's check of its device array: wm_rows_check's pattern (one read-back of rows * 16 bytes on the launch's own stream
+// and a wait; not on a stream that is being captured, where the kernel's own miro_row_ok stands alone). A row whose cell is NULL runs no
+// Mirostat and its other fields are not looked at.
+static int miro_rows_check(const vt_miro_row* miro, int rows, hipStream_t s) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &cap) != hipSuccess) (void)hipGetLastError();
+  if (cap != hipStreamCaptureStatusNone) return VT_OK;
+  std::vector<vt_miro_row> h((size_t)rows);
+  VT_HIP(hipMemcpyAsync(h.data(), miro, (size_t)rows * sizeof(vt_miro_row), hipMemcpyDeviceToHost, s));
+  VT_HIP(hipStreamSynchronize(s));
+  for (int r = 0; r < rows; ++r) {
+    const vt_miro_row& m = h[(size_t)r];
+    if (!m.cell) continue;
+    VT_REQUIRE(((uintptr_t)m.cell % 8) == 0, "vt_sample_rows_miro: miro[%d]: cell must be 8-byte aligned", r);
+    VT_REQUIRE(std::isfinite(m.tau), "vt_sample_rows_miro: miro[%d].tau=%g (must be finite; <= 0 is off)", r, (double)m.tau);
+    VT_REQUIRE(std::isfinite(m.eta) && m.eta >= 0.f, "vt_sample_rows_miro: miro[%d].eta=%g (must be finite and >= 0)", r, (double)m.eta);
+  }
+  return VT_OK;
+}
+
 int vt_sample_rows_launch(const float* logits, int rows, int V, int ldl, const vt_sample_row* params, const uint32_t* const* allow,
                           int* out_ids, int* kept_count, float* logprob, hipStream_t s, const float* const* adjust,
-                          const vt_trunc_row* trunc, const vt_wm_row* wm) {
+                          const vt_trunc_row* trunc, const vt_wm_row* wm, const vt_miro_row* miro) {
   VT_REQUIRE(logits && params && out_ids, "vt_sample_rows: null pointer (logits, params and out_ids are required)");
   VT_REQUIRE(rows > 0 && V > 0 && ldl >= V, "vt_sample_rows: rows=%d V=%d ldl=%d (rows, V > 0 and ldl >= V)", rows, V, ldl);
   VT_REQUIRE(((uintptr_t)params % 8) == 0, "vt_sample_rows: params must be 8-byte aligned");
@@ -923,17 +1027,26 @@ int vt_sample_rows_launch(const float* logits, int rows, int V, int ldl, const v
     const int st = wm_rows_check(wm, rows, s);
     if (st != VT_OK) return st;
   }
+  if (miro) {
+    VT_REQUIRE(!wm, "vt_sample_rows_miro: Mirostat together with the watermark is not built");
+    VT_REQUIRE(((uintptr_t)miro % 8) == 0, "vt_sample_rows_miro: miro must be 8-byte aligned");
+    VT_REQUIRE(reg,
+               "vt_sample_rows_miro: V=%d ldl=%d: Mirostat runs in the register form only (V <= 32768, ldl %% 4 == 0, logits 16-byte "
+               "aligned)", V, ldl);
+    const int st = miro_rows_check(miro, rows, s);
+    if (st != VT_OK) return st;
+  }
   VT_REQUIRE(reg || V <= VT_SAMPLE_ROWS_MAX_V, "vt_sample_rows: V=%d is beyond the history mask of the streaming form (V <= %d)", V,
              VT_SAMPLE_ROWS_MAX_V);
-  // [form][flavour]; the flavour is the highest array given (sample_rows_kernel), and a watermark has been refused above without `reg`
+  // [form][flavour]; the flavour is the highest array given (sample_rows_kernel); a watermark or Mirostat has been refused above without `reg`
   static const decltype(&sample_rows_kernel<true, kPlain>) kKernels[2][kFlavours] = {
       {sample_rows_kernel<false, kPlain>, sample_rows_kernel<false, kAllow>, sample_rows_kernel<false, kAdj>,
-       sample_rows_kernel<false, kTrunc>, nullptr},
+       sample_rows_kernel<false, kTrunc>, nullptr, nullptr},
       {sample_rows_kernel<true, kPlain>, sample_rows_kernel<true, kAllow>, sample_rows_kernel<true, kAdj>,
-       sample_rows_kernel<true, kTrunc>, sample_rows_kernel<true, kWm>}};
-  const int flavour = wm ? kWm : trunc ? kTrunc : adjust ? kAdj : allow ? kAllow : kPlain;
+       sample_rows_kernel<true, kTrunc>, sample_rows_kernel<true, kWm>, sample_rows_kernel<true, kMiro>}};
+  const int flavour = miro ? kMiro : wm ? kWm : trunc ? kTrunc : adjust ? kAdj : allow ? kAllow : kPlain;
   hipLaunchKernelGGL(kKernels[reg][flavour], dim3(rows), dim3(1024), 0, s, logits, V, ldl, params, allow, out_ids, kept_count, logprob,
-                     adjust, trunc, wm);
+                     adjust, trunc, wm, miro);
   VT_LAUNCH_CHECK();
   return VT_OK;
 }

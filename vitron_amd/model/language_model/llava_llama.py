@@ -609,13 +609,26 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
         vitron_amd.watermark.SynthIDWatermark(config).mean_g(ids, generated_from=prompt length) scores a reply. ValueError /
         NotImplementedError before any device work: what SynthIDWatermark refuses (the green-list WatermarkingConfig, debug_mode, a
         sampling table that is no power of two in [32, 65536], ...). Refused with NotImplementedError before any page is taken:
-        do_sample=False, num_beams > 1, penalty_alpha > 0, padded_batch, vocab_size > 32768."""
+        do_sample=False, num_beams > 1, penalty_alpha > 0, padded_batch, vocab_size > 32768.
+        Mirostat v2 (Basu et al., ICLR 2021; llama.cpp's `mirostat 2`), mirostat_tau, mirostat_eta (default 0.1) and
+        mirostat_mode (default 2) taken from **kwargs: mirostat_tau = the target surprise in bits per token; None or 0 is off and the
+        call runs the launches it always ran. Every sample owns a cell {mu, last_surprise} on the device, {2 * tau, 0} at the first pick; every
+        step's sampler launch is ONE vt_sample_rows_miro: behind everything that shapes the row (guidance, DoLa, bans, automata, bias,
+        top-k, top-p, the truncation stages) the tokens whose surprise under the renormalised row exceeds mu leave, the id is drawn
+        from the rest, and mu moves by -eta * (its surprise - tau) -- all on the device, nothing is read back in the loop. Unlike
+        llama.cpp, top_k / top_p are NOT switched off by Mirostat: leave them off (top_k=0, top_p=1.0) for its behaviour.
+        self.last_generate_stats["mirostat"] = {"mu": [B], "surprise": [B]} is read once behind the loop; the cells are dropped with
+        the call. return_logits, return_logprobs and top_logprobs stay RAW. ValueError before any device work: mirostat_tau outside
+        [0, 64], mirostat_eta outside [0, 1], a mirostat_mode that is not 0, 1 or 2, mirostat_tau with mirostat_mode=0. Refused with
+        NotImplementedError that names mirostat_tau, before any page is taken: mirostat_mode=1 (Mirostat v1), do_sample=False,
+        num_beams > 1, penalty_alpha > 0, padded_batch, watermarking_config, vocab_size > 32768."""
         from ...picker import StepPicker, negative_prompt, resolve_generate_args
         guide = {k: kwargs.pop(k, None) for k in ("guidance_scale", "negative_prompt_ids", "negative_attention_mask", "negative_images",
                                                   "negative_regions", "guidance_plausibility")}
         penalty_alpha = kwargs.pop("penalty_alpha", None)
         dola_layers, dola_relative_top = kwargs.pop("dola_layers", None), kwargs.pop("dola_relative_top", 0.1)
         watermarking_config = kwargs.pop("watermarking_config", None)
+        miro = {k: kwargs.pop(k, d) for k, d in (("mirostat_tau", None), ("mirostat_eta", 0.1), ("mirostat_mode", 2))}
         a = resolve_generate_args(
             self.config, input_ids.shape[1], do_sample=do_sample, temperature=temperature, top_p=top_p, top_k=top_k,
             max_new_tokens=max_new_tokens, max_length=max_length, stopping_criteria=stopping_criteria, eos_token_id=eos_token_id,
@@ -627,7 +640,7 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
             presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p, typical_p=typical_p,
             epsilon_cutoff=epsilon_cutoff, eta_cutoff=eta_cutoff, top_logprobs=top_logprobs, automaton=automaton, choices=choices,
             batch_size=input_ids.shape[0], penalty_alpha=penalty_alpha, dola_layers=dola_layers, dola_relative_top=dola_relative_top,
-            watermarking_config=watermarking_config, **guide)
+            watermarking_config=watermarking_config, **miro, **guide)
         self.last_dola_layers = None
         dev = self.device
         neg_ids = neg_mask = None
@@ -736,6 +749,11 @@ class LlavaLlamaForCausalLM(LlavaMetaForCausalLM):
             for s in nseqs:
                 self.kv.release(s.pages)
         out = out_host[:, :n_out].to(dev)
+        if a.mirostat_tau > 0:       # read once, behind the loop; the cells end with the call
+            state_m = picker.mirostat_state()
+            if state_m is not None:
+                self.last_generate_stats["mirostat"] = state_m
+            picker.drop_mirostat()
         if picker.dola_choice is not None:
             self.last_dola_layers = torch.tensor(a.dola_layers, dtype=torch.long, device=dev)[picker.dola_choice[:n_out - L0].long().t()]
         res = (out,) + ((all_logits,) if a.return_logits else ()) + ((picker.logprobs(n_out - L0),) if a.return_logprobs else ()) \

@@ -653,7 +653,7 @@ def adjust_pointers(adjust, rows: int, V: int, device) -> torch.Tensor:
 
 def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = False, return_logprob: bool = False, allow=None,
                 _allow_ptrs: Optional[torch.Tensor] = None, adjust=None, _adjust_ptrs: Optional[torch.Tensor] = None,
-                trunc: Optional[torch.Tensor] = None, watermark: Optional[torch.Tensor] = None):
+                trunc: Optional[torch.Tensor] = None, watermark: Optional[torch.Tensor] = None, miro: Optional[torch.Tensor] = None):
     """One token id per row (int32, on device) with PER-ROW parameters: greedy and sampled rows, penalties and the chosen token's
     log-probability in one launch; see vt_sample_rows in include/vitron_hip.h. `params`: the device array of vt_sample_row that
     sampling.pack_sample_rows builds (uint8 [rows, 48]). Returns ids, or (ids[, kept_count][, logprob]) when either is asked for.
@@ -668,8 +668,11 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = 
     array of vt_trunc_row that sampling.pack_trunc_rows builds (uint8, rows x 16 bytes). None: exactly the calls above.
     watermark: per-row SynthID text watermark (vt_sample_rows_wm, DESIGN.md 9.16: the tournament behind the truncation stages, the
     sequences' state on the device) -- the device array of vt_wm_row that watermark.pack_wm_rows builds (uint8, rows x 48 bytes).
-    None: exactly the calls above."""
-    from .sampling import ROW_BYTES, TRUNC_ROW_BYTES
+    None: exactly the calls above.
+    miro: per-row Mirostat v2 (vt_sample_rows_miro, DESIGN.md 9.17: the moving surprise cutoff behind the truncation stages, the
+    sequences' {mu, last_surprise} cells on the device) -- the device array of vt_miro_row that sampling.pack_miro_rows builds (uint8,
+    rows x 16 bytes). None: exactly the calls above. Together with `watermark` it is refused: that kernel is not built."""
+    from .sampling import MIRO_ROW_BYTES, ROW_BYTES, TRUNC_ROW_BYTES
     from .watermark import WM_ROW_BYTES
     lib = _lib.load_any()
     _chk_rows(logits, torch.float32, "sample_rows.logits")
@@ -700,12 +703,20 @@ def sample_rows(logits: torch.Tensor, params: torch.Tensor, return_kept: bool = 
                                   or watermark.numel() != rows * WM_ROW_BYTES):
         raise _lib.VitronHipError(f"sample_rows.watermark: expected a contiguous uint8 tensor of {rows} x {WM_ROW_BYTES} bytes on the "
                                   "logits' device (watermark.pack_wm_rows)")
+    if miro is not None and (not isinstance(miro, torch.Tensor) or miro.device != logits.device or miro.dtype != torch.uint8
+                             or not miro.is_contiguous() or miro.numel() != rows * MIRO_ROW_BYTES):
+        raise _lib.VitronHipError(f"sample_rows.miro: expected a contiguous uint8 tensor of {rows} x {MIRO_ROW_BYTES} bytes on the logits' "
+                                  "device (sampling.pack_miro_rows)")
+    if miro is not None and watermark is not None:
+        raise _lib.VitronHipError("sample_rows: miro together with watermark is not built (vt_sample_rows_miro carries no watermark)")
     aptrs = given_ptrs(_allow_ptrs, "_allow_ptrs") if _allow_ptrs is not None else \
         None if allow is None else allow_pointers(allow, rows, V, logits.device)
     jptrs = given_ptrs(_adjust_ptrs, "_adjust_ptrs") if _adjust_ptrs is not None else \
         None if adjust is None else adjust_pointers(adjust, rows, V, logits.device)
     # the narrowest entry point that carries what was given: error texts name it, and the library picks the kernel by the same rule
-    if watermark is not None:
+    if miro is not None:
+        name, extra = "vt_sample_rows_miro", (aptrs, jptrs, trunc, miro)
+    elif watermark is not None:
         name, extra = "vt_sample_rows_wm", (aptrs, jptrs, trunc, watermark)
     elif trunc is not None:
         name, extra = "vt_sample_rows_trunc", (aptrs, jptrs, trunc)

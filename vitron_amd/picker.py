@@ -26,6 +26,7 @@ from .engine import parse_kv_cache_dtype
 from .sampling import (BAN_ROW_BYTES, BIAS_ROW_BYTES, BIAS_ROWS_MAX_V, CFG_ROW_BYTES, DOLA_ROW_BYTES, FSM_ROW_BYTES, ROW_BYTES, allow_mask, check_penalties,
                        check_sampling_values, check_top_logprobs, check_truncation_values, log_beta, mask_words, normalise_bias, pack_ban_rows,
                        pack_bias_rows, pack_cfg_rows, pack_dola_rows, pack_fsm_rows, pack_sample_rows, pack_trunc_rows, truncation_active, check_dola)
+from .sampling import check_mirostat, check_mirostat_request, pack_miro_rows
 
 
 @dataclass(frozen=True, eq=False)
@@ -67,6 +68,8 @@ class GenerateArgs:
     dola_layers: Optional[Tuple[int, ...]] = None   # DoLa (vt_dola_rows): the candidate layers, resolved; None is off
     dola_relative_top: float = 0.1               # a token stays iff p_final >= relative_top * max p_final
     watermark: Any = None                        # a watermark.SynthIDWatermark (vt_sample_rows_wm); None is off
+    mirostat_tau: float = 0.0                    # Mirostat v2 (vt_sample_rows_miro): the target surprise in bits; 0 is off
+    mirostat_eta: float = 0.1                    # its learning rate
 
     @property
     def guided(self) -> bool:
@@ -104,7 +107,7 @@ class GenerateArgs:
         """Does a step need the per-row sampler (vt_sample_rows) instead of vt_argmax / vt_sample_top_p?"""
         return (float(self.repetition_penalty) != 1.0 or bool(self.return_logprobs) or self.constrained or self.ngram > 0
                 or self.adjusted or self.truncated or self.automaton is not None or self.guidance_plausibility > 0
-                or self.dola or self.watermark is not None)
+                or self.dola or self.watermark is not None or self.mirostat_tau > 0)
 
 
 def static_mask_schedule(V: int, steps: int, banned_always, banned_begin, min_new: int, eos, allowed_ids):
@@ -137,7 +140,7 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
                           top_logprobs=0, automaton=None, choices=None, guidance_scale=None, negative_prompt_ids=None,
                           negative_attention_mask=None, negative_images=None, negative_regions=None, guidance_plausibility=0.0,
                           batch_size=None, penalty_alpha=None, dola_layers=None, dola_relative_top=0.1,
-                          watermarking_config=None) -> GenerateArgs:
+                          watermarking_config=None, mirostat_tau=None, mirostat_eta=0.1, mirostat_mode=2) -> GenerateArgs:
     """generate()'s keyword arguments as a GenerateArgs. Raises, in this order and before any device work: the argument errors of
     num_beams / no_repeat_ngram_size, everything a beam call refuses, the padded_batch refusals that depend on arguments alone, the
     sampling values, the constraint arguments, a step the constraints leave no token for, constraints with padded_batch, the values of
@@ -158,7 +161,11 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
     dola_layers None is off. The SynthID watermark: watermarking_config is resolved by watermark.SynthIDWatermark right
     behind dola_layers' values (its ValueError / NotImplementedError, the green-list scheme among them); a beam call refuses it with its
     other optional arguments; do_sample=False, penalty_alpha > 0, padded_batch and a vocabulary beyond the sampler's register form are
-    refused with it (NotImplementedError) right behind the beam refusals. None is off. The sample seed
+    refused with it (NotImplementedError) right behind the beam refusals. None is off. Mirostat v2: the VALUES of
+    mirostat_tau / mirostat_eta / mirostat_mode (sampling.check_mirostat: ValueError; mirostat_mode=1 NotImplementedError) are checked right
+    behind watermarking_config's; with mirostat_tau on, do_sample=False, num_beams > 1, penalty_alpha > 0, padded_batch,
+    watermarking_config and a vocabulary beyond the sampler's register form are refused by name (sampling.check_mirostat_request:
+    NotImplementedError) IN FRONT of the beam refusals, so that each names mirostat_tau. mirostat_tau None or 0 is off. The sample seed
     is drawn from torch's global CPU generator (so torch.manual_seed makes sampling reproducible, as with GenerationMixin.sample) and
     only when sampling without `seed`, after the beam refusals: greedy and refused calls leave the RNG state alone."""
     num_beams = int(num_beams)
@@ -169,6 +176,7 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
                                bool(getattr(config, "tie_word_embeddings", False)))
     from .watermark import as_watermark
     watermark = as_watermark(watermarking_config)
+    miro_tau = check_mirostat(mirostat_tau, mirostat_eta, mirostat_mode, "generate")
     top_k_given = top_k
     if no_repeat_ngram_size is None:
         no_repeat_ngram_size = 0
@@ -209,7 +217,12 @@ def resolve_generate_args(config, input_len: int, *, do_sample, temperature, top
         + (("guidance_scale=...",) if guidance_scale is not None and guidance_scale != 1 else ())
         + (("penalty_alpha=...",) if alpha > 0 else ())
         + (("dola_layers=...",) if dola is not None else ())
-        + (("watermarking_config=...",) if watermark is not None else ()))
+        + (("watermarking_config=...",) if watermark is not None else ())
+        + (("mirostat_tau=...",) if miro_tau > 0 else ()))
+    if miro_tau > 0:
+        check_mirostat_request(not do_sample, num_beams, alpha, bool(padded_batch), watermark is not None, int(config.vocab_size),
+                               "generate(mirostat_tau=...)")
+        a = dataclasses.replace(a, mirostat_tau=miro_tau, mirostat_eta=float(mirostat_eta))
     if num_beams > 1:
         check_beam_arguments(a, int(config.vocab_size))
     elif a.num_return_sequences != 1:
@@ -494,6 +507,9 @@ class StepPicker:
       - with watermarking_config: the watermark's table and layer constants (once per device, kept on the watermark), one
         all-zero cell per sample and the B vt_wm_row entries, the same at every step; the sampler launch is vt_sample_rows_wm then and
         the cells live and change on the device only.
+      - with mirostat_tau: nothing here. The first pick allocates the [B, 2] fp32 cells {2 * tau, 0} and uploads the B
+        vt_miro_row entries, the same at every step; the sampler launch is vt_sample_rows_miro then and the cells change on the device
+        only. `mirostat_state()` reads them back (once, behind the loop); `drop_mirostat()` lets them go.
       - with an automaton: its tables (once per device, kept on the automaton), the [B, 2] cells {start, 0}, the B
         working masks vt_fsm_rows writes, the ids every row has GENERATED (the tail of the penalty history, or the history the
         penalties count over, or one of its own) and the [steps, B] vt_fsm_row array (gen_len = step, base = the step's static mask or
@@ -531,6 +547,7 @@ class StepPicker:
         self.cfg_rows = self.cfg_ptrs = self.cfg_mask_ptr = None
         self.dola_rows = self.dola_choice = None
         self.step_base: List[int] = [0] * max(a.max_new_tokens, 0)
+        self.miro_rows = self.miro_cells = None     # (Mirostat makes the mode per-row; allocated at the first pick)
         if self.mode != "rows":
             return
         dev, steps = self.device, a.max_new_tokens
@@ -677,8 +694,11 @@ class StepPicker:
             ptrs = self.ban_ptrs
         if self.bias_rows is not None:           # the rows' adjustments for this pick, from what they have generated: one launch
             ops.bias_rows(self.bias_rows[step], self.B, self.V)
+        if a.mirostat_tau > 0 and self.miro_rows is None:      # one cell per sample; the array is constant over the steps
+            self.miro_cells = torch.tensor([[2.0 * a.mirostat_tau, 0.0]] * self.B, dtype=torch.float32).to(self.device)
+            self.miro_rows = pack_miro_rows([(self.miro_cells[b], a.mirostat_tau, a.mirostat_eta) for b in range(self.B)], self.device)
         nxt = ops.sample_rows(logits, self.rows[step], return_logprob=bool(a.return_logprobs), _allow_ptrs=ptrs, _adjust_ptrs=self.adj_ptrs,
-                              trunc=self.trunc, watermark=self.wm_rows)
+                              trunc=self.trunc, watermark=self.wm_rows, miro=self.miro_rows)
         if a.return_logprobs:
             nxt, lp = nxt
             self._lp.append(lp)
@@ -689,6 +709,17 @@ class StepPicker:
         if self.gen_hist is not None:
             self.gen_hist.append(nxt)
         return nxt
+
+    def mirostat_state(self) -> Optional[dict]:
+        """{"mu": [B floats], "surprise": [B floats]} read back from the cells (one device -> host copy), or None without Mirostat or
+        before the first pick."""
+        if self.miro_cells is None:
+            return None
+        host = self.miro_cells.cpu()
+        return {"mu": host[:, 0].tolist(), "surprise": host[:, 1].tolist()}
+
+    def drop_mirostat(self) -> None:
+        self.miro_rows = self.miro_cells = None
 
     def logprobs(self, n: int) -> torch.Tensor:
         """fp32 [B, n]: the log-probabilities collected by the first n picks."""

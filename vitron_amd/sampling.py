@@ -31,6 +31,10 @@ DoLa: `SamplingParams(dola_layers=, dola_relative_top=)` contra
 it chooses per step (`dola_candidate_layers`, `check_dola`), in front of everything above: struct vt_dola_row (`pack_dola_rows`,
 ops.dola_rows).
 
+Mirostat v2: `SamplingParams(mirostat_tau=, mirostat_eta=)` steers the surprise of the reply to tau bits per token with a
+cutoff that moves after every pick, inside the sampler behind the truncation stages: struct vt_miro_row (`pack_miro_rows`) names the
+request's two-float cell {mu, last_surprise} on the device (`new_miro_cell`), which only the kernel changes.
+
 Top-N log-probabilities: `SamplingParams(top_logprobs=N)` asks for the N most likely tokens and the chosen token's rank
 at every generated token; they come from one vt_logprob_rows launch behind the pick and need no struct here.
 """
@@ -104,6 +108,16 @@ TRUNC_ROW_DTYPE = np.dtype({
     "itemsize": 16,
 })
 TRUNC_ROW_BYTES = TRUNC_ROW_DTYPE.itemsize
+# struct vt_miro_row: the offsets are part of the ABI (tests/test_miro_ref_host.py checks them against the header's table)
+MIRO_ROW_DTYPE = np.dtype({
+    "names": ["cell", "tau", "eta"],
+    "formats": ["<u8", "<f4", "<f4"],
+    "offsets": [0, 8, 12],
+    "itemsize": 16,
+})
+MIRO_ROW_BYTES = MIRO_ROW_DTYPE.itemsize
+MIRO_MAX_V = 32768                 # the sampler's register form: the only one that carries Mirostat
+MIRO_TAU_MAX = 64.0                # bits: beyond any surprise an fp32 probability over <= 32768 tokens can state
 TRUNC_OFF = (0.0, 1.0, 0.0, 0.0)   # (min_p, typical_p, epsilon_cutoff, eta_cutoff) of a row without truncation: every stage inactive
 
 
@@ -119,6 +133,30 @@ def check_truncation_values(min_p, typical_p, epsilon_cutoff, eta_cutoff, what: 
     for name, x in (("epsilon_cutoff", epsilon_cutoff), ("eta_cutoff", eta_cutoff)):
         if not num(x) or not 0 <= x < 1:
             raise ValueError(f"{what}: {name} must be a finite number in [0, 1) (0 is off), got {x!r}")
+
+
+def check_mirostat(tau, eta, mode=2, what: str = "sampling") -> float:
+    """The values of mirostat_tau / mirostat_eta / mirostat_mode; returns tau as a float, 0.0 when Mirostat is off (tau
+    None or 0). ValueError: a tau that is not a finite number in [0, MIRO_TAU_MAX], an eta that is not a finite number in [0, 1], a mode
+    that is not 0, 1 or 2. With Mirostat on, mode 1 (Mirostat v1: it needs the sorted top of the row for its Zipf estimate) is a
+    NotImplementedError that names it, mode 0 a ValueError (it contradicts mirostat_tau). With tau off the feature is not in use and eta
+    and mode are not looked at, as transformers ignores a warper's arguments when the warper is off."""
+    def num(x):
+        return isinstance(x, numbers.Real) and not isinstance(x, bool) and math.isfinite(x)
+    if tau is not None and (not num(tau) or not 0 <= tau <= MIRO_TAU_MAX):
+        raise ValueError(f"{what}: mirostat_tau must be None or a finite number in [0, {MIRO_TAU_MAX:g}] bits (None and 0 are off), got "
+                         f"{tau!r}")
+    if not tau:
+        return 0.0
+    if not num(eta) or not 0 <= eta <= 1:
+        raise ValueError(f"{what}: mirostat_eta must be a finite number in [0, 1], got {eta!r}")
+    if not isinstance(mode, numbers.Integral) or isinstance(mode, bool) or mode not in (0, 1, 2):
+        raise ValueError(f"{what}: mirostat_mode must be 0, 1 or 2, got {mode!r}")
+    if mode == 1:
+        raise NotImplementedError(f"{what}: mirostat_tau with mirostat_mode=1 (Mirostat v1) is not implemented; mirostat_mode=2 is")
+    if mode == 0:
+        raise ValueError(f"{what}: mirostat_tau={tau!r} with mirostat_mode=0 (off): give mirostat_mode=2 or leave mirostat_tau out")
+    return float(tau)
 
 
 def check_top_logprobs(n, what: str = "sampling") -> None:
@@ -253,7 +291,13 @@ class SamplingParams(_SamplingFields):
     watermarking_config is of the same kind: a transformers SynthIDTextWatermarkingConfig, a dict of its fields or a
     vitron_amd.watermark.SynthIDWatermark, resolved at construction and kept as `.watermark` (None is off). The request's draws go through
     the SynthID tournament inside the sampler (vt_sample_rows_wm), its state in a cell on the device. A sampled request only: with
-    temperature 0 it is refused (NotImplementedError). Compared by the configuration's values; repr shows it when set."""
+    temperature 0 it is refused (NotImplementedError). Compared by the configuration's values; repr shows it when set.
+    mirostat_tau and mirostat_eta are of the same kind: Mirostat v2 (llama.cpp's `mirostat 2`) with the target surprise
+    tau in bits (None and 0 are off) and the learning rate eta (0.1 by default), inside the sampler behind the truncation stages
+    (vt_sample_rows_miro); the request's {mu, last_surprise} lives in a cell on the device (ServingEngine.mirostat_state). ValueError here for a
+    value outside its range; a greedy request and one with watermarking_config are refused at submit() (check_constraints). repr shows
+    them when mirostat_tau is on."""
+    MIRO_NAMES = ("mirostat_tau", "mirostat_eta")
     DOLA_NAMES = ("dola_layers", "dola_relative_top")
     GUIDE_NAMES = ("guidance_scale", "negative_prompt_ids", "guidance_plausibility", "negative_images")
     TRUNC_NAMES = ("min_p", "typical_p", "epsilon_cutoff", "eta_cutoff")
@@ -261,7 +305,8 @@ class SamplingParams(_SamplingFields):
 
     def __init__(self, *args, min_p: float = 0.0, typical_p: float = 1.0, epsilon_cutoff: float = 0.0, eta_cutoff: float = 0.0,
                  top_logprobs: int = 0, automaton=None, guidance_scale=None, negative_prompt_ids=None, guidance_plausibility=0.0,
-                 negative_images=None, dola_layers=None, dola_relative_top=0.1, watermarking_config=None, **kw):
+                 negative_images=None, dola_layers=None, dola_relative_top=0.1, watermarking_config=None, mirostat_tau=None,
+                 mirostat_eta=0.1, **kw):
         for name, value in zip(self.TRUNC_NAMES, (min_p, typical_p, epsilon_cutoff, eta_cutoff)):
             object.__setattr__(self, name, value)
         object.__setattr__(self, "top_logprobs", top_logprobs)
@@ -277,6 +322,8 @@ class SamplingParams(_SamplingFields):
         object.__setattr__(self, "dola_relative_top", dola_relative_top)
         from .watermark import as_watermark      # (its ValueError / NotImplementedError: the green-list scheme, debug_mode, ...)
         object.__setattr__(self, "watermark", as_watermark(watermarking_config))
+        object.__setattr__(self, "mirostat_tau", mirostat_tau)
+        object.__setattr__(self, "mirostat_eta", mirostat_eta)
         super().__init__(*args, **kw)            # (its __post_init__ validates: the four are set by then)
 
     def __setattr__(self, name, value):          # (the frozen base guards its own fields only once it is subclassed)
@@ -319,6 +366,12 @@ class SamplingParams(_SamplingFields):
         if self.watermark is not None and not self.temperature > 0:
             raise NotImplementedError("SamplingParams: watermarking_config on a greedy request (temperature 0) is not implemented: the "
                                       "SynthID tournament reshapes the distribution a token is DRAWN from")
+        check_mirostat(self.mirostat_tau, self.mirostat_eta, 2, "SamplingParams")
+
+    @property
+    def mirostat(self) -> bool:
+        """Does the request run Mirostat v2 (vt_sample_rows_miro, a cell on the device)?"""
+        return bool(self.mirostat_tau)
 
     @property
     def dola(self) -> bool:
@@ -347,7 +400,8 @@ class SamplingParams(_SamplingFields):
             + (None if self.automaton is None else id(self.automaton),) \
             + ((self.guidance_scale, self.negative_prompt_ids) if self.guidance_scale is not None or self.negative_prompt_ids is not None else ()) \
             + (("dola", self.dola_layers, self.dola_relative_top) if self.dola_layers is not None else ()) \
-            + (("watermark", self.watermark.key()) if self.watermark is not None else ())
+            + (("watermark", self.watermark.key()) if self.watermark is not None else ()) \
+            + (("mirostat", float(self.mirostat_tau), float(self.mirostat_eta)) if self.mirostat else ())
 
     def __eq__(self, other):
         return self._key() == other._key() if other.__class__ is self.__class__ else NotImplemented
@@ -364,6 +418,8 @@ class SamplingParams(_SamplingFields):
         names += [n for n, off in zip(self.GUIDE_NAMES, (None, None, 0.0, None)) if getattr(self, n) is not off and getattr(self, n) != off]
         if self.dola_layers is not None:
             names += list(self.DOLA_NAMES)
+        if self.mirostat:
+            names += list(self.MIRO_NAMES)
         wm = "" if self.watermark is None else f", watermarking_config={self.watermark.to_dict()!r}"
         return "SamplingParams(" + ", ".join(f"{n}={getattr(self, n)!r}" for n in names) + wm + ")"
 
@@ -372,6 +428,7 @@ class SamplingParams(_SamplingFields):
         kw = {n: getattr(self, n) for n in list(self.__dataclass_fields__) + list(self.TRUNC_NAMES) + ["top_logprobs", "automaton"]
               + list(self.GUIDE_NAMES) + list(self.DOLA_NAMES)}
         kw["watermarking_config"] = self.watermark
+        kw.update({n: getattr(self, n) for n in self.MIRO_NAMES})
         kw.update(changes)
         return SamplingParams(**kw)
 
@@ -499,7 +556,12 @@ def step_allow_mask(sampling: Optional[SamplingParams], n_generated: int, tokens
 def check_constraints(sampling: Optional[SamplingParams], eos: Iterable[int], V: int) -> None:
     """What submit() refuses before anything is queued: ids outside [0, V) (those of bad_words included), choices without an EOS id in
     [0, V), a combination that leaves nothing to emit (the static masks before / after min_new_tokens and the first step of `choices`;
-    allowed_tokens_fn is not called here, and what no_repeat_ngram_size / bad_words leave is known on the device only)."""
+    allowed_tokens_fn is not called here, and what no_repeat_ngram_size / bad_words leave is known on the device only).
+    First of all, what a request with mirostat_tau refuses (NotImplementedError, by name): a greedy request, one with
+    watermarking_config, a vocabulary beyond the sampler's register form."""
+    if sampling is not None and getattr(sampling, "mirostat", False):
+        check_mirostat_request(not sampling.temperature > 0, 1, 0.0, False, sampling.watermark is not None, V,
+                               "SamplingParams(mirostat_tau=...)", greedy_name="temperature=0")
     if sampling is None or not sampling.constrained:
         return
     sp = sampling.replace(allowed_tokens_fn=None)
@@ -553,6 +615,65 @@ def trunc_rows_array(rows: Sequence[Optional[tuple]]) -> np.ndarray:
 def pack_trunc_rows(rows: Sequence[Optional[tuple]], device):
     """Device form of `trunc_rows_array(rows)`: a uint8 tensor [len(rows), 16] for ops.sample_rows(..., trunc=)."""
     return _upload_rows(trunc_rows_array(rows), device)
+
+
+# ---- Mirostat v2: struct vt_miro_row (the host statement of the contract is tests/miro_ref.py) ----------------------------------------
+def check_mirostat_request(greedy: bool, num_beams: int, penalty_alpha: float, padded_batch: bool, watermark: bool, V: int, what: str,
+                           greedy_name: str = "do_sample=False") -> None:
+    """What a call or request with mirostat_tau refuses, by name and in this order (NotImplementedError): a greedy pick, beams,
+    contrastive search, padded_batch, watermarking_config, a vocabulary beyond the sampler's register form."""
+    for bad, name, why in ((greedy, greedy_name, "Mirostat truncates the distribution a token is DRAWN from"),
+                           (num_beams > 1, "num_beams > 1", "beams are not sampled"),
+                           (penalty_alpha > 0, "penalty_alpha > 0", "contrastive search is not sampled"),
+                           (padded_batch, "padded_batch=True", "use the default packed batch"),
+                           (watermark, "watermarking_config=...", "Mirostat together with the SynthID watermark is not built")):
+        if bad:
+            raise NotImplementedError(f"{what}: mirostat_tau with {name} is not implemented: {why}")
+    if int(V) > MIRO_MAX_V:
+        raise NotImplementedError(f"{what}: mirostat_tau: vocab_size={int(V)} is beyond the sampler's register form ({MIRO_MAX_V}), the only "
+                                  "one that carries Mirostat")
+
+
+def new_miro_cell(tau: float, device):
+    """A fresh Mirostat cell on `device`: fp32 {mu = 2 * tau, last_surprise = 0}. Written here once; after that only the kernel writes it."""
+    import torch
+    return torch.tensor([2.0 * float(tau), 0.0], dtype=torch.float32).to(device)
+
+
+def miro_rows_array(rows: Sequence[Optional[tuple]]) -> np.ndarray:
+    """Host array of vt_miro_row from one entry per row: None (cell = NULL: the row runs no Mirostat) or (cell_ptr, tau, eta). cell_ptr
+    is a DEVICE address (tensor.data_ptr()) of two fp32 words, 8-byte aligned, whose owner the caller keeps alive. Values are validated
+    here (check_mirostat); tau 0 makes the row one without Mirostat."""
+    arr = np.zeros((len(rows),), dtype=MIRO_ROW_DTYPE)
+    for i, r in enumerate(rows):
+        if r is None:
+            continue
+        if len(r) != 3:
+            raise ValueError(f"miro row {i}: expected (cell_ptr, tau, eta), got {r!r}")
+        cell, tau, eta = r
+        check_mirostat(tau, eta, 2, f"miro row {i}")
+        if int(cell) < 0 or int(cell) % 8:
+            raise ValueError(f"miro row {i}: the cell must be an 8-byte aligned device address, got {cell!r}")
+        arr[i] = (int(cell), float(tau or 0.0), float(eta) if tau else 0.0)
+    return arr
+
+
+def pack_miro_rows(rows: Sequence[Optional[tuple]], device):
+    """Device form of vt_miro_row for ops.sample_rows(..., miro=): a uint8 tensor [len(rows), 16]. rows: one entry per row, None (no
+    Mirostat) or (cell, tau, eta) with `cell` a contiguous fp32 device tensor of two elements (new_miro_cell). The array holds addresses
+    only: the caller keeps the cells alive."""
+    import torch
+    out = []
+    for i, r in enumerate(rows):
+        if r is None:
+            out.append(None)
+            continue
+        cell, tau, eta = r
+        if not isinstance(cell, torch.Tensor) or cell.dtype != torch.float32 or not cell.is_contiguous() or cell.numel() != 2 \
+                or cell.device != torch.device(device):
+            raise ValueError(f"miro row {i}: a cell is a contiguous fp32 tensor of two elements on the launch's device (new_miro_cell)")
+        out.append((cell.data_ptr(), tau, eta))
+    return _upload_rows(miro_rows_array(out), device)
 
 
 # ---- history-dependent bans: struct vt_ban_row and the host statement of vt_ban_rows' contract --------------------------------------

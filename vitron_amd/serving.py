@@ -89,6 +89,9 @@ class _Request:
     dola: Optional[tuple] = None                     # a DoLa request's candidate layers, resolved against the model
     wm_cell: Optional[torch.Tensor] = None           # device int64: the SynthID state of sampling.watermark, taken at the
                                                      # request's first pick (its admission), dropped with the masks when it retires
+    miro_cell: Optional[torch.Tensor] = None         # device fp32 {mu, last_surprise}: the Mirostat state of sampling.mirostat_tau,
+                                                     # taken at the request's first pick (its admission), released with the masks
+    miro_final: Optional[tuple] = None               # (mu, last_surprise) read from the cell when the request retires
 
     @property
     def rows(self) -> int:
@@ -143,7 +146,12 @@ class ServingEngine:
         sampling.watermarking_config (None is off): the SynthID text watermark of generate(watermarking_config=). The
         request's state lives in a cell on the device from its first pick to its retirement; its tokens equal
         generate(watermarking_config=) for the request alone, whatever else is in the batch. NotImplementedError here when the
-        vocabulary is beyond the sampler's register form."""
+        vocabulary is beyond the sampler's register form.
+        sampling.mirostat_tau (DESIGN.md 9.17; None or 0 is off): Mirostat v2 with sampling.mirostat_eta. The request's {mu, last_surprise}
+        lives in a cell of its own on the device from its first pick until it retires, fails or is cancelled (mirostat_state(rid));
+        its tokens equal generate(mirostat_tau=, mirostat_eta=) for the request alone, whatever joins or leaves the batch.
+        NotImplementedError here, naming mirostat_tau: a greedy request, watermarking_config, a vocabulary beyond the sampler's register
+        form."""
         ids = input_ids if input_ids.dim() == 2 else input_ids.unsqueeze(0)
         if ids.shape[0] != 1:
             raise ValueError("submit() takes one sequence per request")
@@ -153,7 +161,7 @@ class ServingEngine:
             sampling.validate()
         eos = self.model.config.eos_token_id if eos_token_id is None else eos_token_id
         eos_set = frozenset(eos) if isinstance(eos, (list, tuple, set, frozenset)) else (frozenset([eos]) if eos is not None else frozenset())
-        if sampling is not None and sampling.constrained:
+        if sampling is not None and (sampling.constrained or sampling.mirostat):
             check_constraints(sampling, eos_set, int(self.model.config.vocab_size))     # ValueError: nothing is queued
             if sampling.automaton is not None:
                 sampling.automaton.check(int(self.model.config.vocab_size), sorted(eos_set))
@@ -289,6 +297,7 @@ class ServingEngine:
         r.adj_buf = r.adj_ids = r.adj_vals = r.gen = None
         r.fsm_cell = r.fsm_mask = None
         r.wm_cell = None
+        r.miro_cell = None
 
     def _prepare_allow(self, r: _Request) -> None:
         """The allow mask of r's next pick: a pure host function of (r.sampling, r.tokens, r.eos) -- the host has read back
@@ -341,6 +350,11 @@ class ServingEngine:
         A request with SamplingParams(watermarking_config=) turns the launch into ONE vt_sample_rows_wm: its row names
         its cell, every other row carries cell = NULL, which the kernel treats bit for bit as vt_sample_rows_trunc does. While no active
         request is watermarked the launches are exactly the ones above.
+        A request with SamplingParams(mirostat_tau=) turns the launch into ONE vt_sample_rows_miro: its row names its
+        cell, tau and eta, every other row carries cell = NULL, which the kernel treats bit for bit as vt_sample_rows_trunc does. While
+        no active request runs Mirostat the launches are exactly the ones above. A request cannot carry both (submit() refuses it), but
+        a watermarked request and a Mirostat request can share a step: that step is TWO launches over all rows, one vt_sample_rows_wm and
+        one vt_sample_rows_miro, and every row is taken from the launch that carries its entry.
         A request with SamplingParams(top_logprobs=N > 0): AFTER the pick, ONE vt_logprob_rows launch over the span of
         rows from the first to the last such request, the device ids just picked as targets and the largest N asked for as n_top (a
         shorter list is a prefix of a longer one, bit for bit). Its output stays on the device (r.last_top) until step() reads it back
@@ -445,8 +459,28 @@ class ServingEngine:
                     r.wm_cell = w.new_cell(logits.device)
                 entries.append(None if w is None else (w, r.wm_cell))
             wm = pack_wm_rows(entries, logits.device)
-        res = ops.sample_rows(logits, pack_sample_rows(rows, logits.device), return_logprob=want_lp, allow=allow, adjust=adj, trunc=trunc,
-                              watermark=wm)
+        miro = None
+        if any(r.sampling is not None and r.sampling.mirostat for r in reqs):
+            from .sampling import new_miro_cell, pack_miro_rows
+            entries = []
+            for r in reqs:
+                on = r.sampling is not None and r.sampling.mirostat
+                if on and r.miro_cell is None:
+                    r.miro_cell = new_miro_cell(r.sampling.mirostat_tau, logits.device)
+                entries.append((r.miro_cell, r.sampling.mirostat_tau, r.sampling.mirostat_eta) if on else None)
+            miro = pack_miro_rows(entries, logits.device)
+        params = pack_sample_rows(rows, logits.device)
+        if wm is not None and miro is not None:
+            # Watermarked and Mirostat requests in one step: no kernel carries both, so the step is TWO launches over all rows, one per
+            # array. A row's draw depends on its own entry alone and a launch touches only the cells its array names, so each kind of
+            # row is taken from its own launch (every other row is vt_sample_rows_trunc's in both) and every request gets the ids it
+            # gets alone.
+            first = ops.sample_rows(logits, params, return_logprob=want_lp, allow=allow, adjust=adj, trunc=trunc, watermark=wm)
+            second = ops.sample_rows(logits, params, return_logprob=want_lp, allow=allow, adjust=adj, trunc=trunc, miro=miro)
+            on_miro = torch.tensor([r.sampling is not None and r.sampling.mirostat for r in reqs], dtype=torch.bool).to(logits.device)
+            res = tuple(torch.where(on_miro, b, a) for a, b in zip(first, second)) if want_lp else torch.where(on_miro, second, first)
+        else:
+            res = ops.sample_rows(logits, params, return_logprob=want_lp, allow=allow, adjust=adj, trunc=trunc, watermark=wm, miro=miro)
         ids, lp = res if want_lp else (res, None)
         for i, r in enumerate(reqs):
             if r.sampling is not None and r.sampling.wants_logprobs:
@@ -609,8 +643,19 @@ class ServingEngine:
         self.active += ok
         return rest
 
+    def mirostat_state(self, rid: int) -> Optional[Tuple[float, float]]:
+        """(mu, last_surprise) of a request with SamplingParams(mirostat_tau=): read from its cell while it runs (one 8-byte copy), what the cell held
+        when it retired afterwards. None: no such request, no Mirostat, not picked yet, or failed / cancelled (the cell is gone)."""
+        for r in self.active:
+            if r.rid == rid:
+                return None if r.miro_cell is None else tuple(float(x) for x in r.miro_cell.tolist())
+        r = self.finished.get(rid)
+        return None if r is None else r.miro_final
+
     def _retire(self, r: _Request) -> None:
         r.done = True
+        if r.miro_cell is not None:
+            r.miro_final = tuple(float(x) for x in r.miro_cell.tolist())
         self._release(r)
         r.hist = r.last_lp = r.last_top = None
         self._drop_masks(r)
